@@ -17,14 +17,20 @@ data-path collective); the timed region is bracketed by a barrier + synchronize 
 `torch.distributed.run`, spawned BEFORE this process touches the GPU); rank 0 reports `n_gpus` = the world size and
 `rccl_ranks` = the result of a real all-reduce over RCCL.
 
-Prints ONE JSON line on rank 0 with the driver's contract plus
+Prints ONE JSON line on rank 0 with the driver's contract (metric, value, unit, higher_is_better, dtype, ms_per_step,
+...).  A plain run does only that: set up, warm up, time --steps forwards, print.  Everything else the benchmark measures
+is behind --full (off by default), which adds to the same line
   "roofline":     the encoder MSDA kernel (dominant hand-written kernel): algorithmic bytes per launch / its
                   average duration measured with HIP events on the launch stream, against the 8 TB/s HBM peak;
   "roofline_kernels": the same entry plus the matrix-core kernels; the split-bf16 ("x6") ones are priced against the unit
                   they run on (executed bf16 FLOPs / time against the 2.5 PFLOP/s dense bf16 peak; the fp32-equivalent
                   rate is kept as `achieved_fp32_equiv`, the matrix-pipe busy counter as `mfma_busy`);
   "cpu_baseline": the CPU oracle (the reference's pure-PyTorch fallback semantics) timed on the host cores on a
-                  bounded sample of the same workload (rank 0, N = 1 only).
+                  bounded sample of the same workload (rank 0, N = 1 only), with the logit parity against it;
+and the other workloads (`eager`, `mixed_shapes`, `batched_bs8`, `train_step`, `stress_bf16`, `train_step_ddp`).
+
+--dump-outputs DIR writes what the timed path handed its caller in the last timed step as DIR/<name>.npy (see
+dump_outputs); inputs and weights are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -61,6 +67,52 @@ def build_model(device, cfg_over=None):
     torch.manual_seed(0)
     model = DetrForSceneGraphGeneration(cfg, fg_matrix=fg.astype(np.float64))
     return model.to(device).eval(), cfg, c
+
+
+DUMP_BYTES = 60_000_000   # --dump-outputs: at most this many bytes of array data in all
+
+
+def output_arrays(obj, name=""):
+    """[(name, tensor)] of every tensor in a model output / loss dict, nested tuples and lists as name.<i>, in order."""
+    if torch.is_tensor(obj):
+        return [(name, obj)]
+    if isinstance(obj, (int, float)) and not isinstance(obj, bool):
+        return [(name, torch.tensor(float(obj), dtype=torch.float64))]
+    if isinstance(obj, dict):
+        items = obj.items()
+    elif isinstance(obj, (list, tuple)):
+        items = ((str(i), v) for i, v in enumerate(obj))
+    else:
+        return []
+    return [a for k, v in items for a in output_arrays(v, f"{name}.{k}" if name else str(k))]
+
+
+def dump_outputs(path, arrays):
+    """Write ``arrays`` ([(name, tensor)]) as path/<name>.npy: float64 for float64 and integer / boolean tensors, float32 for
+    the rest.  DUMP_BYTES is shared out smallest array first: an array that fits its equal share of what is left is written
+    whole, a larger one as a fixed sample of its flattened elements (seeded positions that depend only on the element count
+    and the shapes of the other arrays, so every run with the same arguments samples the same positions), as a 1-D array."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    dtypes = [torch.float32 if t.is_floating_point() and t.dtype != torch.float64 else torch.float64 for _, t in arrays]
+    size = [8 if d == torch.float64 else 4 for d in dtypes]
+    keep, left = [0] * len(arrays), DUMP_BYTES
+    order = sorted(range(len(arrays)), key=lambda i: arrays[i][1].numel() * size[i])
+    for n, i in enumerate(order):
+        keep[i] = min(arrays[i][1].numel(), left // (len(order) - n) // size[i])
+        left -= keep[i] * size[i]
+    perms, sampled = {}, []
+    for (name, t), dtype, k in zip(arrays, dtypes, keep):
+        t = t.detach()
+        if t.numel() > k:
+            if t.numel() not in perms:
+                perms[t.numel()] = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))
+            pick = perms[t.numel()][:k].sort().values
+            t = t.reshape(-1)[pick.to(t.device)]
+            sampled.append(name)
+        np.save(os.path.join(path, name + ".npy"), t.to(dtype).cpu().numpy())
+    print(f"[bench] --dump-outputs: {len(arrays)} arrays in {path}"
+          + (f" ({len(sampled)} as fixed samples: {', '.join(sampled)})" if sampled else ""), file=sys.stderr)
 
 
 class MsdaProbe:
@@ -579,7 +631,7 @@ def train_bench(args, world, rank, dev, dist, emit=True):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss, _, _ = tr.training_step(b)
+        loss, loss_dict, _ = tr.training_step(b)
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
@@ -587,6 +639,8 @@ def train_bench(args, world, rank, dev, dist, emit=True):
     dt = time.perf_counter() - t0
     tr.finalize()   # a cost matrix the device matcher refused in the last step would surface here (ValueError)
     dt, spread = rank_times(dt, args.steps, dist, dev, world)
+    if emit and rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, output_arrays({"loss": loss, "loss_dict": loss_dict}))
     result = None
     if rank == 0:
         result = {
@@ -604,7 +658,7 @@ def train_bench(args, world, rank, dev, dist, emit=True):
                                           "LayerNorm, level geometry" if _train_switch("EGTR_ENCODER_TRAIN_FUSED")
                                           else "per-op composition (EGTR_ENCODER_TRAIN_FUSED=0)"),
                        "gemm_tuning": bool(args.tune_gemm), "miopen_find": bool(torch.backends.cudnn.benchmark)}}
-        if bwd_args is not None and not args.no_kernel_probes:
+        if args.full and bwd_args is not None and not args.no_kernel_probes:
             us, alg = time_msda_backward(bwd_args)
             ach = alg / (us * 1e-6) / 1e9
             bwd_kernel = "msda_bwd_q64_f32<no atomics> + msda_bwd_value_tile_f32"
@@ -616,7 +670,7 @@ def train_bench(args, world, rank, dev, dist, emit=True):
                                   "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": bp.get("hbm_bytes_per_launch"),
                                   "traffic_source": bp_src, "l2_hit": bp.get("l2_hit"),
                                   "algorithmic_bytes_per_launch": alg, "avg_launch_us": round(us, 2)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             ncores = usable_cores()
             torch.set_num_threads(ncores)
             labels_cpu = [{k: v.cpu() for k, v in t.items()} for t in b["labels"]]
@@ -1059,11 +1113,11 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=1, help="images per step per GPU (reference FPS path: 1)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and parity check")
     ap.add_argument("--no-kernel-probes", action="store_true",
-                    help="--mode train: skip the stand-alone timing loop of the MSDA backward after the timed steps (used "
+                    help="--full --mode train: skip the stand-alone timing loop of the MSDA backward after the timed steps (used "
                          "for rocprofv3 traces of the steady-state step)")
-    ap.add_argument("--cpu-budget", type=float, default=20.0, help="seconds of CPU-baseline work (bounded sample)")
+    ap.add_argument("--cpu-budget", type=float, default=20.0, help="--full: seconds of CPU-baseline work (bounded sample)")
     ap.add_argument("--graph", type=int, default=1, help="replay the forward from a HIP graph (0 = eager launches)")
     ap.add_argument("--train-graph", type=int, default=0,
                     help="--mode train, one GPU: replay forward / backward of the static part of the step from HIP "
@@ -1078,9 +1132,9 @@ def main():
                     help="infer = BASELINE configs[1] (default, the headline metric); train = configs[2]-style train "
                          "step (forward + SGG loss + backward + DDP all-reduce + AdamW), batch 4/GPU unless --batch")
     ap.add_argument("--extras", type=int, default=1,
-                    help="--mode infer on one GPU: after the timed region also run a short bs = 4 train loop and the bf16 "
+                    help="--full --mode infer on one GPU: after the timed region also run a short bs = 4 train loop and the bf16 "
                          "stress forward and append them to the JSON line as `train_step` / `stress_bf16` (0 = skip)")
-    ap.add_argument("--extra-steps", type=int, default=8, help="timed steps of each extra workload")
+    ap.add_argument("--extra-steps", type=int, default=8, help="--full: timed steps of each extra workload")
     ap.add_argument("--mixed-tune", type=int, default=1,
                     help="mixed_shapes leg: 1 = the untimed first pass keeps MIOpen find / TunableOp tuning on for the new "
                          "shapes (what the reference's cudnn autotuning does on a new shape), 0 = heuristic picks")
@@ -1088,7 +1142,14 @@ def main():
                     help="1: raise when a call falls off a HIP fast path (egtr_amd.ops.FALLBACKS); 0: count and warn")
     ap.add_argument("--launch-check", action="store_true",
                     help="only rendezvous, all-reduce and print n_gpus / rccl_ranks (launcher self-test, runs on CPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run the kernel roofline probes, the CPU baseline + parity check and the "
+                         "other workloads (--extras); a plain run only times the --steps steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32 / float64, <= 60 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(launch_ranks(args.gpus))  # nothing above this line touches the GPU
     if args.launch_check:
@@ -1165,6 +1226,31 @@ def main():
     value = world * args.batch * args.steps / dt
     if args.graph and not fwd.graphed:
         raise SystemExit("[bench] HIP-graph capture did not happen (pass --graph 0 to time eager launches)")
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, output_arrays(out))   # before anything else replays the graph into `out`
+
+    result = {
+        "metric": "images/sec end-to-end SGG, 600x1000 input, N=200 queries",
+        "value": round(value, 3), "unit": "images/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": "VG inference: ResNet-50, N=200, 6 enc/6 dec, 150 classes, 50 predicates, "
+                               f"600x1000, bs={args.batch}/GPU fp32 (BASELINE configs[1])",
+                   "images_per_step_per_gpu": args.batch, "hip_graph": bool(args.graph) and fwd.graphed, "gemm_tuning": bool(args.tune_gemm),
+                   "miopen_find": bool(torch.backends.cudnn.benchmark),
+                   "parallelism": f"replicas x{world} (independent images, no collective)"},
+        "rccl_ranks": args.rccl_ranks, "rank_ms_per_step": spread,
+    }
+    if world > 1 and backend != "nccl":
+        result["config"]["collective_backend"] = f"{backend} (plumbing self-test: ranks share GPUs; not a performance number)"
+    from egtr_amd import ops as _ops
+    if not args.full:
+        result["config"]["fast_path"] = {"strict": bool(_ops.STRICT_FAST_PATH), "fallbacks": dict(_ops.FALLBACKS)}
+        if rank == 0:
+            print(json.dumps(result))
+        if dist is not None:
+            dist.destroy_process_group()
+        return
 
     msda_us, alg_bytes = time_msda_kernel(msda_args, probe.fused, keep_bits=probe.keep_bits)
     achieved = alg_bytes / (msda_us * 1e-6) / 1e9
@@ -1177,36 +1263,22 @@ def main():
     # the kernel that was just timed, otherwise null.
     pmc, pmc_src = newest_pmc("r*_msda_pmc.json", msda_kernel)
     traffic = pmc.get("hbm_bytes_per_launch")
-    result = {
-        "metric": "images/sec end-to-end SGG, 600x1000 input, N=200 queries",
-        "value": round(value, 3), "unit": "images/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": "VG inference: ResNet-50, N=200, 6 enc/6 dec, 150 classes, 50 predicates, "
-                               f"600x1000, bs={args.batch}/GPU fp32 (BASELINE configs[1])",
-                   "images_per_step_per_gpu": args.batch, "hip_graph": bool(args.graph) and fwd.graphed, "gemm_tuning": bool(args.tune_gemm),
-                   "miopen_find": bool(torch.backends.cudnn.benchmark),
-                   "parallelism": f"replicas x{world} (independent images, no collective)"},
-        "roofline": {"bound": "hbm", "kernel": msda_kernel, "launch": "encoder layer, Lq = S = 12537, fused softmax + "
-                     "sampling locations" if probe.fused else "encoder layer, Lq = S = 12537",
-                     "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
-                     "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_us": round(msda_us, 3),
-                     "traffic_source": pmc_src,
-                     "l2_hit": pmc.get("l2_hit"), "l1_gather_bytes": pmc.get("l1_gather_bytes"),
-                     # the vector-L1 return path is what bounds this kernel: its ceiling is MEASURED in this
-                     # run (csrc/probe_l1.hip); the gathered bytes per launch are 4 corners x 16 samples x 128 B per (query,
-                     # head) by construction, the counter figure (incl. the prologue's reads) comes from the PMC file
-                     "l1_gather_ceiling_gbs": round(l1_ceiling_gbs, 1),
-                     "l1_gather_bytes_by_construction": int(msda_args[0].shape[0] * msda_args[3].shape[1] * 8 * 64 * 128),
-                     "frac_of_l1_gather_ceiling": round(
-                         (pmc.get("l1_gather_bytes") or msda_args[0].shape[0] * msda_args[3].shape[1] * 8 * 64 * 128)
-                         / (msda_us * 1e-6) / 1e9 / l1_ceiling_gbs, 3)},
-        "rccl_ranks": args.rccl_ranks, "rank_ms_per_step": spread,
-    }
-    if world > 1 and backend != "nccl":
-        result["config"]["collective_backend"] = f"{backend} (plumbing self-test: ranks share GPUs; not a performance number)"
-    from egtr_amd import ops as _ops
+    result["roofline"] = {
+        "bound": "hbm", "kernel": msda_kernel, "launch": "encoder layer, Lq = S = 12537, fused softmax + "
+        "sampling locations" if probe.fused else "encoder layer, Lq = S = 12537",
+        "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+        "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
+        "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_us": round(msda_us, 3),
+        "traffic_source": pmc_src,
+        "l2_hit": pmc.get("l2_hit"), "l1_gather_bytes": pmc.get("l1_gather_bytes"),
+        # the vector-L1 return path is what bounds this kernel: its ceiling is MEASURED in this
+        # run (csrc/probe_l1.hip); the gathered bytes per launch are 4 corners x 16 samples x 128 B per (query,
+        # head) by construction, the counter figure (incl. the prologue's reads) comes from the PMC file
+        "l1_gather_ceiling_gbs": round(l1_ceiling_gbs, 1),
+        "l1_gather_bytes_by_construction": int(msda_args[0].shape[0] * msda_args[3].shape[1] * 8 * 64 * 128),
+        "frac_of_l1_gather_ceiling": round(
+            (pmc.get("l1_gather_bytes") or msda_args[0].shape[0] * msda_args[3].shape[1] * 8 * 64 * 128)
+            / (msda_us * 1e-6) / 1e9 / l1_ceiling_gbs, 3)}
     split = bool(_ops.REL_HEAD_SPLIT_BF16) and rel_args[1].get("owner") is not None
     busy, busy_src = newest_mfma_busy()
 
