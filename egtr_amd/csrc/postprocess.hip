@@ -2,10 +2,11 @@
 //
 // egtr_bbox_overlaps_f64: the reference's native CPU routine lib/fpn/box_intersections_cpu/bbox.pyx (bbox_overlaps,
 // :21-61, and bbox_intersections, :64-108) -- float64, "+1 pixel" box convention, zero where the boxes do not overlap.
-// One thread per (box n, query k) pair, the same operation order as the Cython loops, so results are bit-identical
-// (IEEE double add / mul / div; no FMA contraction: the products are rounded before they are added).
+// One thread per (box n, query k) pair; the arithmetic is egtr_bbox_overlap_pyx (bbox_f64.h, shared with sgg_eval.hip): the
+// same operation order as the Cython loops, so results are bit-identical (no FMA contraction).
 #include <hip/hip_runtime.h>
 
+#include "bbox_f64.h"
 #include "common.h"
 
 namespace {
@@ -19,21 +20,7 @@ __global__ __launch_bounds__(256) void bbox_overlaps_f64(const double* __restric
   const int n = (int)(idx / K), k = (int)(idx - (long long)n * K);
   const double bx0 = boxes[n * 4 + 0], by0 = boxes[n * 4 + 1], bx1 = boxes[n * 4 + 2], by1 = boxes[n * 4 + 3];
   const double qx0 = query[k * 4 + 0], qy0 = query[k * 4 + 1], qx1 = query[k * 4 + 2], qy1 = query[k * 4 + 3];
-  const double box_area = (qx1 - qx0 + 1) * (qy1 - qy0 + 1);                 // bbox.pyx:44-47
-  double r = 0.0;
-  const double iw = fmin(bx1, qx1) - fmax(bx0, qx0) + 1;                     // :49-52
-  if (iw > 0) {
-    const double ih = fmin(by1, qy1) - fmax(by0, qy0) + 1;                   // :54-57
-    if (ih > 0) {
-      if (mode == 0) {
-        const double ua = (bx1 - bx0 + 1) * (by1 - by0 + 1) + box_area - iw * ih;   // :59-63
-        r = iw * ih / ua;                                                    // :64
-      } else {
-        r = iw * ih / box_area;                                              // :107 (bbox_intersections)
-      }
-    }
-  }
-  out[idx] = r;
+  out[idx] = egtr_bbox_overlap_pyx(bx0, by0, bx1, by1, qx0, qy0, qx1, qy1, mode);
 }
 
 }  // namespace

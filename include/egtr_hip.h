@@ -478,6 +478,28 @@ long long egtr_relation_loss_workspace_bytes(int batch, int num_query);
 int egtr_bbox_overlaps_f64(egtr_stream_t stream, const double* boxes, const double* query_boxes, int num_boxes,
                            int num_query, int mode, double* out);
 
+/* Scene-graph Recall@K / mean Recall@K of the reference's sgdet evaluator (lib/evaluation/sg_eval.py, fed by
+ * train_egtr.py:43-139) for a batch of images, accumulated on the device.
+ *   candidates: cand [batch, num_cand, cand_cols] in rank order, cand_cols = 3 (s, o, p: multiple-predicate mode) or 2
+ *   (s, o: single-predicate mode, p = numpy argmax of rel_scores [batch, num_cand, num_rel]: lowest index among the maxima,
+ *   first NaN if any); pred_boxes [batch, num_obj, 4] xyxy, pred_classes [batch, num_obj].
+ *   ground truth, packed ragged: gt_rels [num_gt_rels, 3] (s, o, p; s / o index the image's own boxes), rel_offsets
+ *   [batch + 1]; gt_boxes [num_gt_boxes, 4] xyxy, gt_classes [num_gt_boxes], box_offsets [batch + 1].
+ *   ks [num_k] (HOST memory, 1 <= num_k <= 8, ascending).  num_cand <= 1024, 1 <= num_rel <= 256.
+ * A GT triplet matches a candidate when both classes and the predicate agree and the bbox.pyx IoU (float64, widened from
+ * the float32 boxes) of the subject and of the object are >= iou_thresh.  first_rank [num_gt_rels] (may be NULL): the
+ * lowest matching candidate index, num_cand if none.  slab [batch, egtr_sgg_eval_width(num_rel, num_k)] receives the
+ * per-image recalls (layout in sgg_eval.hip); acc [width] (may be NULL) is then incremented by the slab rows in image
+ * order (deterministic, independent of the batch size).  An image with no GT relation is skipped and counted in acc's
+ * skipped slot (the reference asserts there).  Candidates or GT entries with out-of-range indices never match. */
+long long egtr_sgg_eval_width(int num_rel, int num_k);
+int egtr_sgg_eval_f32(egtr_stream_t stream, const int64_t* cand, int cand_cols, const float* rel_scores,
+                      const float* pred_boxes, const int64_t* pred_classes, int batch, int num_cand, int num_obj,
+                      int num_rel, const int64_t* gt_rels, const int64_t* rel_offsets, long long num_gt_rels,
+                      const float* gt_boxes, const int64_t* gt_classes, const int64_t* box_offsets,
+                      long long num_gt_boxes, const int* ks, int num_k, double iou_thresh, int* first_rank, double* slab,
+                      double* acc);
+
 /* Sine position embedding of DeformableDetrSinePositionEmbedding(normalize=True) (model/deformable_detr.py:850-876)
  * from y_embed / x_embed = cumsum of the mask along H / W ([B,H,W] fp32) and dim_t [E] (the reference's
  * temperature ** (2*(i//2)/E) table); out [B, 2E, H, W]. */
