@@ -67,6 +67,13 @@ SIGNATURES = {
     "egtr_sgg_eval_width": [_I, _I],
     "egtr_sgg_eval_f32": [_P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P, ctypes.c_longlong, _P, _P, _P, ctypes.c_longlong,
                           _P, _I, ctypes.c_double, _P, _P, _P],
+    "egtr_oi_eval_width": [_I, _I],
+    "egtr_oi_select_workspace_bytes": [_I, _I, _I, _I],
+    "egtr_oi_select_f32": [_P, _P, ctypes.c_longlong, ctypes.c_longlong, _P, _P, ctypes.c_longlong, _I, _I, _I, _I, _I,
+                           _I, _P, _P, _P, _P],
+    "egtr_oi_match_f32": [_P, _P, _P, _I, _I, _P, _P, _I, _I, _P, _P, ctypes.c_longlong, _P, _P, _P, ctypes.c_longlong,
+                          _P, _I, _P, _P, _P],
+    "egtr_oi_ap_f64": [_P, _P, _P, _P, ctypes.c_longlong, _I, _P, _P],
     "egtr_hungarian_match_f32": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, ctypes.c_float, ctypes.c_float,
                                  ctypes.c_float, _I, ctypes.c_float, ctypes.c_float, _P, _P, _P, _P, _P, _P, _P],
     "egtr_hungarian_match_scratch_doubles": [_I, _I, ctypes.c_longlong],
@@ -139,7 +146,8 @@ _RESTYPES = {"egtr_status_string": ctypes.c_char_p, "egtr_last_hip_error": ctype
              "egtr_add_layernorm_backward_workspace_floats": ctypes.c_longlong,
              "egtr_linear_split_bf16_wgrad_workspace_floats": ctypes.c_longlong,
              "egtr_dropout_add_layernorm_backward_workspace_floats": ctypes.c_longlong,
-             "egtr_xs_bytes": ctypes.c_longlong, "egtr_sgg_eval_width": ctypes.c_longlong}
+             "egtr_xs_bytes": ctypes.c_longlong, "egtr_sgg_eval_width": ctypes.c_longlong,
+             "egtr_oi_eval_width": ctypes.c_longlong, "egtr_oi_select_workspace_bytes": ctypes.c_longlong}
 
 _lib = None
 

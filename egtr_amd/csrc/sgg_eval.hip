@@ -29,8 +29,8 @@
 
 #include <stdint.h>
 
-#include "bbox_f64.h"
 #include "common.h"
+#include "sgg_match.h"
 
 namespace {
 
@@ -127,26 +127,8 @@ __global__ __launch_bounds__(kThreads) void sgg_match(const SggArgs a) {
       const long long gcs = a.gt_classes[g0 + gs], gco = a.gt_classes[g0 + go];
       const float* gsb = a.gt_boxes + (g0 + gs) * 4;
       const float* gob = a.gt_boxes + (g0 + go) * 4;
-      const double sx0 = gsb[0], sy0 = gsb[1], sx1 = gsb[2], sy1 = gsb[3];
-      const double ox0 = gob[0], oy0 = gob[1], ox1 = gob[2], oy1 = gob[3];
-      for (int base = 0; base < K; base += 64) {
-        const int c = base + lane;
-        bool m = false;
-        if (c < K) {
-          const int4 lab = s_lab[c];
-          if (lab.w && lab.x == gcs && lab.y == gco && lab.z == gp) {   // label test first (intersect_2d)
-            // bbox_overlaps(gt_box[None], boxes)[0] >= iou_thresh for the subject and the object (sg_eval.py:306-309)
-            const float4 q = s_sbox[c], u = s_obox[c];
-            m = egtr_bbox_overlap_pyx(sx0, sy0, sx1, sy1, q.x, q.y, q.z, q.w, 0) >= a.thr &&
-                egtr_bbox_overlap_pyx(ox0, oy0, ox1, oy1, u.x, u.y, u.z, u.w, 0) >= a.thr;
-          }
-        }
-        const unsigned long long bal = __ballot(m);
-        if (bal) {
-          fr = base + __ffsll(bal) - 1;   // lowest matching rank of this chunk = the wave's min
-          break;
-        }
-      }
+      fr = egtr_first_rank_wave(s_lab, s_sbox, s_obox, K, gcs, gco, gp, gsb[0], gsb[1], gsb[2], gsb[3], gob[0], gob[1],
+                                gob[2], gob[3], a.thr, lane);
     }
     if (lane == 0) {
       if (a.first_rank) a.first_rank[t] = fr;
@@ -187,10 +169,7 @@ __global__ __launch_bounds__(kThreads) void sgg_match(const SggArgs a) {
 __global__ __launch_bounds__(kThreads) void sgg_fold(const double* __restrict__ slab, int B, int W,
                                                      double* __restrict__ acc) {
   const int j = blockIdx.x * kThreads + threadIdx.x;
-  if (j >= W) return;
-  double s = acc[j];
-  for (int b = 0; b < B; ++b) s += slab[(long long)b * W + j];
-  acc[j] = s;
+  if (j < W) egtr_fold_column(slab, B, W, acc, j);
 }
 
 }  // namespace

@@ -500,6 +500,45 @@ int egtr_sgg_eval_f32(egtr_stream_t stream, const int64_t* cand, int cand_cols, 
                       long long num_gt_boxes, const int* ks, int num_k, double iou_thresh, int* first_rank, double* slab,
                       double* acc);
 
+/* Open Images relation metrics of the reference's OI evaluator (lib/evaluation/oi_eval.py eval_rel_results,
+ * lib/evaluation/ap_eval_rel.py; inputs as train_egtr.py:154-174 builds them), in three steps.  Layouts in oi_eval.hip.
+ *
+ * egtr_oi_select_f32: per image, the `topk` largest of spo[m][j] = (obj_scores[s] * obj_scores[o]) * top_j(row m)
+ * (float32), j < kk = min(prd_k, num_rel), among the entries > 1e-5; top_j is the j-th best predicate of the row (NaN
+ * last, equal values to the lower predicate index).  Ties in spo go to the lower flat index m * kk + j.
+ *   pred_scores [batch, num_pairs, num_rel] at img_stride / row_stride floats (row_stride >= num_rel; img_stride > 0 when
+ *   batch > 1), obj_scores [batch, num_obj] (contiguous); pairs [num_pairs, 2] (s, o) int64 at pair_stride elements per
+ *   image (0 = shared), or NULL for the row-major cartesian product (then num_pairs == num_obj^2).  Pairs outside
+ *   [0, num_obj) give no detection.  num_pairs <= 90000, 1 <= num_rel <= 256, 1 <= topk <= 1024, 1 <= prd_k <= 8.
+ *   workspace: egtr_oi_select_workspace_bytes(num_pairs, topk, prd_k, batch) bytes.
+ *   Out: det_sop [batch, topk, 3] int32 (s, o, p) in rank order, det_score [batch, topk], det_count [batch]; slots past
+ *   the count hold -1 / 0.
+ * egtr_oi_match_f32: per image, the recall hits at ks (HOST array, 1 <= num_k <= 8, ascending) of the detections against
+ * the GT triplets (labels (s, p, o) and bbox.pyx IoU >= 0.5 in float64, first-rank matching), the GT count per
+ * predicate class (npos), and the AP TP flags of every detection (tp [2, batch, topk] bytes: rel mode, then phr mode;
+ * greedy VOC assignment with the float32 ap_eval_rel.bbox_iou > 0.5, visited state per image and class).  GT packed
+ * as for egtr_sgg_eval_f32 (predicates must lie in [0, num_rel); at most 4096 GT relations per image take part in the
+ * AP flags).  slab [batch, egtr_oi_eval_width(num_rel, num_k)] receives one row per image; acc [width] (may be NULL) is
+ * then incremented by the rows in image order.  An image without GT relation is skipped and counted.
+ * egtr_oi_ap_f64: AP of every (predicate class, mode) over records sorted by class, then confidence descending:
+ * tp_sorted [2, num_records] (rel flags, then phr flags), seg_offsets [num_rel + 1] int64 (class c owns records
+ * [seg_offsets[c], seg_offsets[c + 1])), npos [num_rel] float64; scratch [4 * num_records] float64; out ap [2, num_rel]
+ * (rel, then phr).  get_ap's all-point interpolation; the area is summed as a left fold in record order.
+ * All three return EGTR_E_ARG for invalid sizes or missing pointers before any HIP call. */
+long long egtr_oi_eval_width(int num_rel, int num_k);
+long long egtr_oi_select_workspace_bytes(int num_pairs, int topk, int prd_k, int batch);
+int egtr_oi_select_f32(egtr_stream_t stream, const float* pred_scores, long long img_stride, long long row_stride,
+                       const float* obj_scores, const int64_t* pairs, long long pair_stride, int batch, int num_pairs,
+                       int num_obj, int num_rel, int topk, int prd_k, void* workspace, int* det_sop, float* det_score,
+                       int* det_count);
+int egtr_oi_match_f32(egtr_stream_t stream, const int* det_sop, const int* det_count, int batch, int topk,
+                      const float* pred_boxes, const int64_t* pred_classes, int num_obj, int num_rel,
+                      const int64_t* gt_rels, const int64_t* rel_offsets, long long num_gt_rels, const float* gt_boxes,
+                      const int64_t* gt_classes, const int64_t* box_offsets, long long num_gt_boxes, const int* ks,
+                      int num_k, unsigned char* tp, double* slab, double* acc);
+int egtr_oi_ap_f64(egtr_stream_t stream, const unsigned char* tp_sorted, const int64_t* seg_offsets, const double* npos,
+                   long long num_records, int num_rel, double* scratch, double* ap);
+
 /* Sine position embedding of DeformableDetrSinePositionEmbedding(normalize=True) (model/deformable_detr.py:850-876)
  * from y_embed / x_embed = cumsum of the mask along H / W ([B,H,W] fp32) and dim_t [E] (the reference's
  * temperature ** (2*(i//2)/E) table); out [B, 2E, H, W]. */
