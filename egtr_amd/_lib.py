@@ -74,6 +74,9 @@ SIGNATURES = {
     "egtr_oi_match_f32": [_P, _P, _P, _I, _I, _P, _P, _I, _I, _P, _P, ctypes.c_longlong, _P, _P, _P, ctypes.c_longlong,
                           _P, _I, _P, _P, _P],
     "egtr_oi_ap_f64": [_P, _P, _P, _P, ctypes.c_longlong, _I, _P, _P],
+    "egtr_coco_match_f32": [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, ctypes.c_longlong, _P, _P, _I, _P, _P, _P,
+                            _P, _P],
+    "egtr_coco_accumulate_f64": [_P, _P, _P, _P, _P, ctypes.c_longlong, _I, _P, _P, _P, _P],
     "egtr_hungarian_match_f32": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, ctypes.c_float, ctypes.c_float,
                                  ctypes.c_float, _I, ctypes.c_float, ctypes.c_float, _P, _P, _P, _P, _P, _P, _P],
     "egtr_hungarian_match_scratch_doubles": [_I, _I, ctypes.c_longlong],

@@ -539,6 +539,32 @@ int egtr_oi_match_f32(egtr_stream_t stream, const int* det_sop, const int* det_c
 int egtr_oi_ap_f64(egtr_stream_t stream, const unsigned char* tp_sorted, const int64_t* seg_offsets, const double* npos,
                    long long num_records, int num_rel, double* scratch, double* ap);
 
+/* COCO box-detection AP / AR of pycocotools COCOeval(iouType="bbox") (evaluateImg + accumulate; the reference's
+ * CocoEvaluator, lib/evaluation/coco_eval.py), in two steps.  T = 10 IoU thresholds, A = 4 area ranges, M = 3 maxDets,
+ * R = 101 recall thresholds; bit t * A + a of a record's bit words belongs to (threshold t, area range a).
+ * egtr_coco_match_f32: per image (one workgroup), the greedy evaluateImg matching of every (category, t, a).
+ *   det_boxes [batch, num_det, 4] fp32 xyxy, det_scores [batch, num_det], det_labels [batch, num_det] int64 (labels
+ *   outside [0, num_classes) are not evaluated); GT packed over the batch: gt_boxes [num_gt, 4] fp64 xywh, gt_area
+ *   [num_gt] fp64, gt_crowd [num_gt] bytes (crowd = also ignored), gt_labels [num_gt] int64, gt_offsets [batch + 1]
+ *   int64.  HOST arrays: iou_thrs [10], area_rngs [4, 2] (inclusive lo, hi).  A detection ranked >= max_det within its
+ *   (image, category) by descending score (ties to the lower index) is not evaluated.
+ *   Out per detection: rec_label [batch, num_det] int32 (-1 = no record), rec_score, rec_rank int32 (-1 = no record),
+ *   rec_bits [batch, num_det, 2] int64 (match bits, ignore bits); npig [num_classes, 4] int32 is incremented by the
+ *   non-ignored GTs (zero it before the first batch).  num_det <= 1024, at most 1024 GTs per image, num_classes <= 1024.
+ * egtr_coco_accumulate_f64: precision [T, R, num_classes, A, M] and recall [T, num_classes, A, M] fp64 over records
+ *   sorted by (category, score descending, image, rank): rank_sorted [num_records] int32, bits_sorted [num_records, 2],
+ *   seg_offsets [num_classes + 1] int64 (category k owns records [seg_offsets[k], seg_offsets[k + 1])), npig
+ *   [num_classes, 4] int32; HOST arrays max_dets [3], rec_thrs [101].  -1 where npig is 0.
+ * Both return EGTR_E_ARG for invalid sizes or missing pointers before any HIP call. */
+int egtr_coco_match_f32(egtr_stream_t stream, const float* det_boxes, const float* det_scores, const int64_t* det_labels,
+                        int batch, int num_det, int num_classes, const double* gt_boxes, const double* gt_area,
+                        const unsigned char* gt_crowd, const int64_t* gt_labels, const int64_t* gt_offsets,
+                        long long num_gt, const double* iou_thrs, const double* area_rngs, int max_det, int* rec_label,
+                        float* rec_score, int* rec_rank, int64_t* rec_bits, int* npig);
+int egtr_coco_accumulate_f64(egtr_stream_t stream, const int* rank_sorted, const int64_t* bits_sorted,
+                             const int64_t* seg_offsets, const int* npig, long long num_records, int num_classes,
+                             const int* max_dets, const double* rec_thrs, double* precision, double* recall);
+
 /* Sine position embedding of DeformableDetrSinePositionEmbedding(normalize=True) (model/deformable_detr.py:850-876)
  * from y_embed / x_embed = cumsum of the mask along H / W ([B,H,W] fp32) and dim_t [E] (the reference's
  * temperature ** (2*(i//2)/E) table); out [B, 2E, H, W]. */
