@@ -116,6 +116,8 @@ SIGNATURES = {
     "egtr_dropout_add_layernorm_backward_f32": [_P, _P, _P, _P, ctypes.c_float, _P, _P, _P, _P, ctypes.c_float, _P, _P, _P,
                                                 _P, _I, _I, ctypes.c_float],
     "egtr_pad_batch_f32": [_P, _P, _P, _I, _I, _I, _I, _P, _P],
+    "egtr_preprocess_f32": [_P, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P],
+    "egtr_preprocess_bf16": [_P, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P],
     "egtr_conv1x1_tail_x6_f32": [_P, _P, _I, _P, _I, _P, _P, _P, _I, _I, _P, _I, _I, _I, _I, _I, _I],
     "egtr_stem_conv7x7_pool_bf16": [_P, _P, _P, _P, _P, _I, _I, _I],
     "egtr_stem_conv7x7_pool_x6_f32": [_P, _P, _P, _P, _P, _I, _I, _I],

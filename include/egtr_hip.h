@@ -963,6 +963,30 @@ int egtr_weighted_column_sum_f32(egtr_stream_t stream, const float* g, const flo
 int egtr_pad_batch_f32(egtr_stream_t stream, const float* const* images, const int* heights_widths, int batch,
                        int channels, int H, int W, float* pixel_values, int64_t* pixel_mask);
 
+/* The whole transformers-4.18 DetrFeatureExtractor path (do_resize + do_normalize) plus the collate's pad, from raw
+ * uint8 RGB images (HWC, rows may be strided), bit-exact: Pillow's 8-bit BILINEAR ImagingResample (horizontal pass,
+ * then vertical, 22-bit fixed-point int32 sums, uint8 in between), then lut[c][u8] (the host-built float32 table of
+ * (f32(u) * f32(1/255) - mean_c) / std_c), zero padding to [H, W] top-left aligned and the int64 mask (1 = real pixel).
+ * All arrays are DEVICE memory; nothing is allocated or synchronised, so the call can be captured into a graph.
+ *   desc      [batch][12] int64: src pointer, src row stride (bytes), in_h, in_w, out_h, out_w, tab_x, kx, tab_y, ky,
+ *             route, ws_offset.  tab_x / tab_y are int32 offsets into `coeffs` of the (in_w -> out_w) / (in_h -> out_h)
+ *             tables; a table for in -> out holds bounds [out][2] = (xmin, n) followed by weights [out][k] (k = kx or
+ *             ky, n <= k; an axis that keeps its size uses the one-tap identity table).  route 1 sends the image through
+ *             the horizontal prepass into workspace + ws_offset ([in_h][out_w][3] bytes); it is required when some
+ *             EGTR_PREPROCESS_TILE_W-column output tile reads more than EGTR_PREPROCESS_STAGE_BYTES bytes of an input
+ *             row (3 * (xmin[last] + n[last] - xmin[first])); such a tile left on route 0 yields NaN pixels.
+ *   prepass_rows / prepass_cols: the largest in_h / out_w among route-1 images (0 / 0: none; workspace may be NULL).
+ *   pixel_values [batch, 3, H, W] (fp32, or bf16 rounded to nearest even), pixel_mask [batch, H, W]; H, W >= every
+ *   out_h, out_w. */
+#define EGTR_PREPROCESS_TILE_W 128
+#define EGTR_PREPROCESS_STAGE_BYTES 16354
+int egtr_preprocess_f32(egtr_stream_t stream, const int64_t* desc, int batch, const int32_t* coeffs, const float* lut,
+                        int H, int W, int prepass_rows, int prepass_cols, uint8_t* workspace, float* pixel_values,
+                        int64_t* pixel_mask);
+int egtr_preprocess_bf16(egtr_stream_t stream, const int64_t* desc, int batch, const int32_t* coeffs, const float* lut,
+                         int H, int W, int prepass_rows, int prepass_cols, uint8_t* workspace, uint16_t* pixel_values,
+                         int64_t* pixel_mask);
+
 #ifdef __cplusplus
 }
 #endif
