@@ -118,6 +118,8 @@ SIGNATURES = {
     "egtr_pad_batch_f32": [_P, _P, _P, _I, _I, _I, _I, _P, _P],
     "egtr_preprocess_f32": [_P, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P],
     "egtr_preprocess_bf16": [_P, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P],
+    "egtr_preprocess_augment_f32": [_P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P],
+    "egtr_preprocess_augment_bf16": [_P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P],
     "egtr_conv1x1_tail_x6_f32": [_P, _P, _I, _P, _I, _P, _P, _P, _I, _I, _P, _I, _I, _I, _I, _I, _I],
     "egtr_stem_conv7x7_pool_bf16": [_P, _P, _P, _P, _P, _I, _I, _I],
     "egtr_stem_conv7x7_pool_x6_f32": [_P, _P, _P, _P, _P, _I, _I, _I],

@@ -271,33 +271,47 @@ def _pinned(array):
 
 class _CoeffCache:
     """The coefficient tables of every (in, out) axis seen on one device, in one int32 buffer (the kernel takes one
-    pointer plus offsets).  New tables are appended with one copy; when the buffer is full a larger one replaces it
-    (batches already prepared keep the old one alive), so a stream of VG sizes uploads each table once."""
-    MAX_INTS = 1 << 26
+    pointer plus offsets).  Only the new tables of a batch are built and uploaded, with one copy, so a lookup costs
+    O(new tables) however many are cached; no host copy of the buffer is kept.  A full buffer is replaced by one of
+    twice the size, filled with a device-to-device copy (batches already prepared keep the old one alive).  At MAX_INTS
+    (64 MB) the cache starts afresh instead: random training sizes, crop windows above all, rarely recur, so the memory
+    stays bounded and a table that does recur is built again."""
+    MAX_INTS = 1 << 24
+    MIN_INTS = 1 << 16
 
     def __init__(self, device):
-        self.device = device
+        self.device = torch.device(device)
         self.index = {}
-        self.host = np.zeros(0, np.int32)
+        self.bounds = {}
+        self.used = 0
         self.buf = None
 
     def lookup(self, pairs):
         new = [p for p in dict.fromkeys(pairs) if p not in self.index]
         if new:
-            start = len(self.host)
-            if start > self.MAX_INTS:
-                self.__init__(self.device)
-                return self.lookup(pairs)
-            parts = []
+            parts, index, bounds, used = [], {}, {}, self.used
             for p in new:
                 flat, k, window = _device_table(*p)
-                self.index[p] = (start + sum(len(x) for x in parts), k, window)
+                index[p] = (used, k, window)
+                bounds[p] = flat[:2 * p[1]].reshape(-1, 2)
                 parts.append(flat)
-            self.host = np.concatenate([self.host] + parts)
-            if self.buf is None or self.buf.numel() < len(self.host):
-                self.buf = torch.empty(max(2 * len(self.host), 1 << 16), dtype=torch.int32, device=self.device)
-                start = 0
-            self.buf[start:len(self.host)].copy_(_pinned(self.host[start:]), non_blocking=True)
+                used += len(flat)
+            if used > self.MAX_INTS and self.used:
+                self.__init__(self.device)
+                return self.lookup(pairs)
+            if self.buf is None or self.buf.numel() < used:
+                size = max(min(max(2 * used, self.MIN_INTS), self.MAX_INTS), used)
+                grown = torch.empty(size, dtype=torch.int32, device=self.device)
+                if self.used:
+                    grown[:self.used].copy_(self.buf[:self.used])
+                self.buf = grown
+            fresh = torch.from_numpy(np.concatenate(parts))
+            if self.device.type == "cuda":
+                fresh = fresh.pin_memory()
+            self.buf[self.used:used].copy_(fresh, non_blocking=True)
+            self.index.update(index)
+            self.bounds.update(bounds)
+            self.used = used
         return self.buf, [self.index[p] for p in pairs]
 
 
@@ -396,8 +410,9 @@ class DeformableDetrDeviceFeatureExtractor(DeformableDetrFeatureExtractor):
             out.append(tgt)
         return out
 
-    def prepare(self, images, device=None):
-        """Upload a batch and everything its launch reads; returns a PreprocessBatch."""
+    def _upload(self, images, device=None):
+        """Resolve the device and put the batch's pixels on it.  Returns the device, the (h, w) of every image, its
+        (address, row stride in bytes) on the device and the tensors that must outlive the launch."""
         if not self.do_normalize:
             raise NotImplementedError("DeformableDetrDeviceFeatureExtractor always normalises (do_normalize=False)")
         if not images:
@@ -412,7 +427,6 @@ class DeformableDetrDeviceFeatureExtractor(DeformableDetrFeatureExtractor):
         if device.index is None:
             device = torch.device("cuda", torch.cuda.current_device())
         orig = [(int(a.shape[0]), int(a.shape[1])) for a in arrs]
-        sizes = [self.output_size(h, w) for h, w in orig]
 
         # host images: one pinned buffer, one copy; device images: in place (HWC with packed pixels, any row stride)
         host_idx = [i for i, a in enumerate(arrs) if not torch.is_tensor(a)]
@@ -430,22 +444,35 @@ class DeformableDetrDeviceFeatureExtractor(DeformableDetrFeatureExtractor):
             staged = pinned.to(device, non_blocking=True)
             keep.append(staged)
             base = staged.data_ptr()
-
-        cache = _COEFF_CACHES.setdefault(device, _CoeffCache(device))
-        pairs = [p for (h, w), (oh, ow) in zip(orig, sizes) for p in ((w, ow), (h, oh))]
-        coeffs, tabs = cache.lookup(pairs)
-        desc = np.zeros((len(arrs), _DESC_WORDS), np.int64)
-        ws_bytes, prepass_rows, prepass_cols = 0, 0, 0
-        for i, (a, (h, w), (oh, ow)) in enumerate(zip(arrs, orig, sizes)):
+        srcs = []
+        for i, a in enumerate(arrs):
             if torch.is_tensor(a):
                 if a.device != device:
                     raise ValueError(f"image {i} is on {a.device}, the batch runs on {device}")
                 if a.stride(2) != 1 or a.stride(1) != 3:
                     a = a.contiguous()
                 keep.append(a)
-                src, stride = a.data_ptr(), a.stride(0)
+                srcs.append((a.data_ptr(), a.stride(0)))
             else:
-                src, stride = base + offs[i], 3 * w
+                srcs.append((base + offs[i], 3 * orig[i][1]))
+        return device, orig, srcs, keep
+
+    def _lut(self, device):
+        key = (device, self.image_mean, self.image_std)
+        if key not in _LUTS:
+            _LUTS[key] = torch.from_numpy(normalize_lut(self.image_mean, self.image_std)).to(device)
+        return _LUTS[key]
+
+    def prepare(self, images, device=None):
+        """Upload a batch and everything its launch reads; returns a PreprocessBatch."""
+        device, orig, srcs, keep = self._upload(images, device)
+        sizes = [self.output_size(h, w) for h, w in orig]
+        cache = _COEFF_CACHES.setdefault(device, _CoeffCache(device))
+        pairs = [p for (h, w), (oh, ow) in zip(orig, sizes) for p in ((w, ow), (h, oh))]
+        coeffs, tabs = cache.lookup(pairs)
+        desc = np.zeros((len(orig), _DESC_WORDS), np.int64)
+        ws_bytes, prepass_rows, prepass_cols = 0, 0, 0
+        for i, ((src, stride), (h, w), (oh, ow)) in enumerate(zip(srcs, orig, sizes)):
             (tx, kx, window), (ty, ky, _) = tabs[2 * i], tabs[2 * i + 1]
             route = int(window > PREPROCESS_STAGE_BYTES)
             desc[i] = (src, stride, h, w, oh, ow, tx, kx, ty, ky, route, ws_bytes if route else 0)
@@ -453,8 +480,284 @@ class DeformableDetrDeviceFeatureExtractor(DeformableDetrFeatureExtractor):
                 ws_bytes += (h * ow * 3 + 15) // 16 * 16
                 prepass_rows, prepass_cols = max(prepass_rows, h), max(prepass_cols, ow)
         workspace = torch.empty(ws_bytes, dtype=torch.uint8, device=device) if ws_bytes else None
-        key = (device, self.image_mean, self.image_std)
-        if key not in _LUTS:
-            _LUTS[key] = torch.from_numpy(normalize_lut(self.image_mean, self.image_std)).to(device)
-        return PreprocessBatch(device, _pinned(desc).to(device, non_blocking=True), coeffs, _LUTS[key], sizes, orig, workspace,
-                               prepass_rows, prepass_cols, keep)
+        return PreprocessBatch(device, _pinned(desc).to(device, non_blocking=True), coeffs, self._lut(device), sizes, orig,
+                               workspace, prepass_rows, prepass_cols, keep)
+
+
+# ---- the reference's training augmentation on the device (csrc/augment.hip, egtr_preprocess_augment_f32 / _bf16) -----
+# dd:322-385 wrap the PIL chain of model/transform.py around the 4.18 extractor:
+#   RandomHorizontalFlip -> RandomSelect(RandomResize(scales, max_size=1333),
+#                                        Compose[RandomResize([400, 500, 600]), RandomSizeCrop(384, 600) (not "NoCrop"),
+#                                                RandomResize(scales, max_size=1333)])
+# Every PIL step is 8-bit.  Here the random draws (sample_augmentation) and the target arithmetic (augment_target) stay
+# on the host and are separate from the pixels, which the kernels produce bit-identically from the raw uint8 image.
+
+AUGMENT_SCALES = (480, 512, 544, 576, 608, 640, 672, 704, 736, 768, 800)
+AUGMENT_MID_SIZES = (400, 500, 600)
+AUGMENT_CROP_RANGE = (384, 600)
+_AUG_DESC_WORDS = 17                                  # include/egtr_hip.h EGTR_AUGMENT_DESC_WORDS
+_AUG_MIRROR, _AUG_SRC_WS, _AUG_PREPASS = 1, 2, 4      # EGTR_AUGMENT_MIRROR / _SRC_WORKSPACE / _PREPASS
+
+
+class AugmentParams:
+    """What the reference's chain drew for one image: flip (bool), size1 ((h, w) of the first resize, None on the
+    one-resize branch), crop ((top, left, h, w) in the first resize's output, or None), size2 ((h, w) of the final
+    resize)."""
+    __slots__ = ("flip", "size1", "crop", "size2")
+
+    def __init__(self, flip=False, size1=None, crop=None, size2=None):
+        self.flip = bool(flip)
+        self.size1 = None if size1 is None else (int(size1[0]), int(size1[1]))
+        self.crop = None if crop is None else tuple(int(v) for v in crop)
+        self.size2 = (int(size2[0]), int(size2[1]))
+        if self.size1 is None and self.crop is not None:
+            raise ValueError("a crop needs the first resize (size1)")
+
+    def _key(self):
+        return self.flip, self.size1, self.crop, self.size2
+
+    def __eq__(self, other):
+        return isinstance(other, AugmentParams) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        return "AugmentParams(flip=%r, size1=%r, crop=%r, size2=%r)" % self._key()
+
+    def window(self):
+        """(top, left, h, w): the part of the first resize that the final resize reads."""
+        return self.crop if self.crop is not None else (0, 0) + self.size1
+
+
+def _random_crop_params(h, w, th, tw):
+    """torchvision 0.13 transforms.RandomCrop.get_params(img, (th, tw)), restated (torchvision is not a dependency,
+    and the restatement is not confirmed against an install): no draw when the crop equals the image, otherwise
+    torch.randint for the top and then for the left."""
+    if h + 1 < th or w + 1 < tw:
+        raise ValueError(f"Required crop size {(th, tw)} is larger then input image size {(h, w)}")
+    if w == tw and h == th:
+        return 0, 0, h, w
+    top = torch.randint(0, h - th + 1, size=(1,)).item()
+    left = torch.randint(0, w - tw + 1, size=(1,)).item()
+    return top, left, th, tw
+
+
+def sample_augmentation(h, w, crop, scales=AUGMENT_SCALES, mid_sizes=AUGMENT_MID_SIZES, crop_range=AUGMENT_CROP_RANGE,
+                        max_size=1333):
+    """Draw one AugmentParams for an h x w image, consuming Python's global `random` and torch's global generator
+    exactly as the reference's chain does: random() (flip), random() (branch), then choice(scales), or
+    choice(mid_sizes), [randint (crop width), randint (crop height), RandomCrop.get_params], choice(scales)."""
+    scales, mid_sizes = list(scales), list(mid_sizes)
+    flip = random.random() < 0.5
+    if random.random() < 0.5:
+        return AugmentParams(flip, None, None, _target_size(h, w, random.choice(scales), max_size))
+    size1 = _target_size(h, w, random.choice(mid_sizes), None)
+    region = None
+    if crop:
+        cw = random.randint(crop_range[0], min(size1[1], crop_range[1]))
+        ch = random.randint(crop_range[0], min(size1[0], crop_range[1]))
+        region = _random_crop_params(size1[0], size1[1], ch, cw)
+    wh, ww = region[2:] if region is not None else size1
+    return AugmentParams(flip, size1, region, _target_size(wh, ww, random.choice(scales), max_size))
+
+
+def augment_target(target, h, w, params, normalize=True):
+    """The reference's target arithmetic (model/transform.py hflip / resize / crop, float32, step by step) for the h x w
+    image `target` belongs to, then the extractor's box normalisation (_normalize_target) unless normalize=False.
+    boxes are absolute xyxy float32; `orig_size` is the raw image's."""
+    if target is None:
+        return None
+    target = {k: torch.as_tensor(v) for k, v in target.items()}
+    if "orig_size" not in target:
+        target["orig_size"] = torch.tensor([h, w])
+    ch, cw = h, w                                            # the current image size
+    if params.flip and "boxes" in target:
+        target["boxes"] = (target["boxes"][:, [2, 1, 0, 3]] * torch.as_tensor([-1, 1, -1, 1])
+                           + torch.as_tensor([cw, 0, cw, 0]))
+
+    def resize(nh, nw):
+        ratio_width, ratio_height = float(nw) / float(cw), float(nh) / float(ch)
+        if "boxes" in target:
+            target["boxes"] = target["boxes"] * torch.as_tensor([ratio_width, ratio_height, ratio_width, ratio_height])
+        if "area" in target:
+            target["area"] = target["area"] * (ratio_width * ratio_height)
+        target["size"] = torch.tensor([nh, nw])
+        return nh, nw
+
+    if params.size1 is not None:
+        ch, cw = resize(*params.size1)
+        if params.crop is not None:
+            i, j, rh, rw = params.crop
+            target["size"] = torch.tensor([rh, rw])
+            if "boxes" in target:
+                max_size = torch.as_tensor([rw, rh], dtype=torch.float32)
+                cropped = target["boxes"] - torch.as_tensor([j, i, j, i])
+                cropped = torch.min(cropped.reshape(-1, 2, 2), max_size).clamp(min=0)
+                target["area"] = (cropped[:, 1, :] - cropped[:, 0, :]).prod(dim=1)
+                target["boxes"] = cropped.reshape(-1, 4)
+                keep = torch.all(cropped[:, 1, :] > cropped[:, 0, :], dim=1)
+                for f in ("class_labels", "area", "iscrowd", "boxes"):
+                    if f in target:
+                        target[f] = target[f][keep]
+            ch, cw = rh, rw
+    ch, cw = resize(*params.size2)
+    if normalize:
+        target = DeformableDetrFeatureExtractor._normalize_target(target, ch, cw)
+    return target
+
+
+def _window_bytes(bounds, off, n):
+    """The widest input window (bytes of an RGB row) any PREPROCESS_TILE_W-column tile of the output columns
+    [off, off + n) reads."""
+    first = np.arange(off, off + n, PREPROCESS_TILE_W)
+    last = np.minimum(first + PREPROCESS_TILE_W - 1, off + n - 1)
+    return int((bounds[last, 0].astype(np.int64) + bounds[last, 1] - bounds[first, 0]).max()) * 3
+
+
+class AugmentBatch:
+    """A prepared augmented batch, like PreprocessBatch: run() is one C call of at most four launches (one when every
+    image is on the one-resize branch), with no allocation when the outputs are given and no synchronisation."""
+
+    def __init__(self, device, first, final, coeffs, lut, params, orig_sizes, workspace, extents, keep):
+        self.device, self.first, self.final, self.coeffs, self.lut = device, first, final, coeffs, lut
+        self.params, self.orig_sizes, self.workspace, self.extents = params, orig_sizes, workspace, extents
+        self.sizes = [p.size2 for p in params]
+        self._keep = keep
+        self.H = max(h for h, _ in self.sizes)
+        self.W = max(w for _, w in self.sizes)
+
+    def run(self, pixel_values=None, pixel_mask=None, dtype=torch.float32):
+        from . import _lib
+        from .load_custom import _stream
+        B, H, W = len(self.sizes), self.H, self.W
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"dtype must be torch.float32 or torch.bfloat16, got {dtype}")
+        if pixel_values is None:
+            pixel_values = torch.empty(B, 3, H, W, dtype=dtype, device=self.device)
+        if pixel_mask is None:
+            pixel_mask = torch.empty(B, H, W, dtype=torch.int64, device=self.device)
+        if (tuple(pixel_values.shape) != (B, 3, H, W) or pixel_values.dtype != dtype or not pixel_values.is_contiguous()
+                or tuple(pixel_mask.shape) != (B, H, W) or pixel_mask.dtype != torch.int64
+                or not pixel_mask.is_contiguous()):
+            raise ValueError("pixel_values / pixel_mask must be contiguous [B, 3, H, W] / [B, H, W] int64 tensors")
+        entry = "egtr_preprocess_augment_f32" if dtype == torch.float32 else "egtr_preprocess_augment_bf16"
+        ws = self.workspace.data_ptr() if self.workspace is not None else None
+        first = self.first.data_ptr() if self.first is not None else None
+        with torch.cuda.device(self.device):
+            _lib.check(getattr(_lib.lib(), entry)(_stream(), first, self.final.data_ptr(), B, self.coeffs.data_ptr(),
+                                                  self.lut.data_ptr(), H, W, *self.extents, ws,
+                                                  pixel_values.data_ptr(), pixel_mask.data_ptr()), entry)
+        return {"pixel_values": pixel_values, "pixel_mask": pixel_mask}
+
+
+class DeformableDetrDeviceFeatureExtractorWithAugmentorNoCrop(DeformableDetrDeviceFeatureExtractor):
+    """The reference's DeformableDetrFeatureExtractorWithAugmentorNoCrop (dd:355-385) + collate pad on the device:
+    pixel_values bit-identical to its PIL chain for the same image and the same random draws.
+
+    images as for DeformableDetrDeviceFeatureExtractor (raw uint8; no flip or resize is done by the caller).  `params`
+    is one AugmentParams per image; None samples them in batch order with sample_augmentation, from Python's global
+    `random` and torch's global generator like the reference.  Sampling happens per batch in the calling process, so a
+    seeded run is comparable with the reference per draw sequence, not per epoch of a multi-worker loader (whose
+    workers each hold their own generator state).  `size` is ignored, as in the reference's override; `max_size` caps
+    the random-scale resizes."""
+    use_crop = False
+
+    def __init__(self, size=800, max_size=1333, scales=AUGMENT_SCALES, mid_sizes=AUGMENT_MID_SIZES,
+                 crop_range=AUGMENT_CROP_RANGE, **kwargs):
+        super().__init__(size=size, max_size=max_size, **kwargs)
+        self.scales, self.mid_sizes, self.crop_range = tuple(scales), tuple(mid_sizes), tuple(crop_range)
+
+    def sample(self, h, w):
+        return sample_augmentation(h, w, self.use_crop, self.scales, self.mid_sizes, self.crop_range, self.max_size)
+
+    def __call__(self, images, annotations=None, params=None, return_tensors="pt", device=None, dtype=torch.float32,
+                 **kwargs):
+        single = not isinstance(images, (list, tuple))
+        images = [images] if single else list(images)
+        annotations = [annotations] if (single and annotations is not None) else annotations
+        if single and isinstance(params, AugmentParams):
+            params = [params]
+        batch = self.prepare(images, device, params)
+        enc = batch.run(dtype=dtype)
+        if annotations is not None:
+            enc["labels"] = [augment_target(t, h, w, p)
+                             for t, (h, w), p in zip(annotations, batch.orig_sizes, batch.params)]
+        return enc
+
+    @staticmethod
+    def _check(p):
+        for name, s in (("size1", p.size1), ("size2", p.size2)):
+            if s is not None and (s[0] < 1 or s[1] < 1):
+                raise ValueError(f"{name} {s} must be positive")
+        if p.crop is not None:
+            top, left, ch, cw = p.crop
+            if top < 0 or left < 0 or ch < 1 or cw < 1 or top + ch > p.size1[0] or left + cw > p.size1[1]:
+                raise ValueError(f"crop {p.crop} leaves the first resize {p.size1}")
+
+    def prepare(self, images, device=None, params=None):
+        """Upload a batch and everything its launches read; returns an AugmentBatch."""
+        device, orig, srcs, keep = self._upload(images, device)
+        if params is None:
+            params = [self.sample(h, w) for h, w in orig]
+        params = list(params)
+        if len(params) != len(orig):
+            raise ValueError(f"{len(params)} AugmentParams for {len(orig)} images")
+        pairs = []
+        for (h, w), p in zip(orig, params):
+            self._check(p)
+            if p.size1 is None:
+                pairs += [(w, p.size2[1]), (h, p.size2[0])] * 2
+            else:
+                _, _, wh, ww = p.window()
+                pairs += [(w, p.size1[1]), (h, p.size1[0]), (ww, p.size2[1]), (wh, p.size2[0])]
+        cache = _COEFF_CACHES.setdefault(device, _CoeffCache(device))
+        coeffs, tabs = cache.lookup(pairs)
+        first = np.zeros((len(orig), _AUG_DESC_WORDS), np.int64)
+        final = np.zeros((len(orig), _AUG_DESC_WORDS), np.int64)
+        ws = [0]
+        ext = [0] * 6      # first rows / cols, prepass rows / cols of the first pass, of the final pass
+
+        def region(nbytes):
+            off = ws[0]
+            ws[0] += (nbytes + 15) // 16 * 16
+            return off
+
+        def one_pass(src, stride, in_h, in_w, full, window, flags, tab_x, tab_y, pair_x, pair_y, e):
+            """The descriptor of one resize pass; routes it through the horizontal prepass (of the input rows the window
+            reads) when a tile's input window does not fit the LDS stage."""
+            top, left, oh, ow = window
+            pre = 0
+            if _window_bytes(cache.bounds[pair_x], left, ow) > PREPROCESS_STAGE_BYTES:
+                flags |= _AUG_PREPASS
+                by = cache.bounds[pair_y]
+                rows = int(by[top + oh - 1, 0]) + int(by[top + oh - 1, 1]) - int(by[top, 0])
+                pre = region(rows * ow * 3)
+                ext[e], ext[e + 1] = max(ext[e], rows), max(ext[e + 1], ow)
+            return (src, stride, in_h, in_w, oh, ow, tab_x[0], tab_x[1], tab_y[0], tab_y[1], left, top, full[1], full[0],
+                    flags, pre, 0)
+
+        for i, ((src, stride), (h, w), p) in enumerate(zip(srcs, orig, params)):
+            t = tabs[4 * i:4 * i + 4]
+            pp = pairs[4 * i:4 * i + 4]
+            mirror = _AUG_MIRROR if p.flip else 0
+            if p.size1 is None:
+                final[i] = one_pass(src, stride, h, w, p.size2, (0, 0) + p.size2, mirror, t[0], t[1], pp[0], pp[1], 4)
+                continue
+            window = p.window()
+            d = list(one_pass(src, stride, h, w, p.size1, window, mirror, t[0], t[1], pp[0], pp[1], 2))
+            d[16] = region(window[2] * window[3] * 3)
+            first[i] = d
+            ext[0], ext[1] = max(ext[0], window[2]), max(ext[1], window[3])
+            final[i] = one_pass(d[16], 3 * window[3], window[2], window[3], p.size2, (0, 0) + p.size2, _AUG_SRC_WS,
+                                t[2], t[3], pp[2], pp[3], 4)
+        workspace = torch.empty(ws[0], dtype=torch.uint8, device=device) if ws[0] else None
+        descs = _pinned(np.stack([first, final])).to(device, non_blocking=True)
+        return AugmentBatch(device, descs[0] if ext[0] else None, descs[1], coeffs, self._lut(device), params, orig,
+                            workspace, tuple(ext), keep + [descs])
+
+
+class DeformableDetrDeviceFeatureExtractorWithAugmentor(DeformableDetrDeviceFeatureExtractorWithAugmentorNoCrop):
+    """The reference's DeformableDetrFeatureExtractorWithAugmentor (dd:322-352): the chain above with
+    RandomSizeCrop(384, 600) between the two resizes of the second branch."""
+    use_crop = True

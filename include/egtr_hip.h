@@ -987,6 +987,45 @@ int egtr_preprocess_bf16(egtr_stream_t stream, const int64_t* desc, int batch, c
                          int H, int W, int prepass_rows, int prepass_cols, uint8_t* workspace, uint16_t* pixel_values,
                          int64_t* pixel_mask);
 
+/* The reference's training augmentation (model/deformable_detr.py:322-385: RandomHorizontalFlip, then one random-scale
+ * PIL resize, or a resize to 400/500/600, an optional crop and a second random-scale resize) followed by the rescale /
+ * normalise / pad above, bit-exact, from raw uint8 RGB images.  The random draws are the caller's: the descriptors say
+ * what to execute.  Same coefficient tables, lut, outputs and capture rules as the entries above; at most four launches
+ * (prepass, first resize, prepass, final resize), of which an all-one-resize batch needs one.
+ * A pass is one Pillow resize of an in_h x in_w source to full_h x full_w of which only the window of out_h rows from
+ * off_y and out_w columns from off_x is produced (a crop after a resize is that window; no crop: the offsets are 0 and
+ * out = full).  Its descriptor is EGTR_AUGMENT_DESC_WORDS int64:
+ *   src, src row stride (bytes), in_h, in_w, out_h, out_w, tab_x, kx, tab_y, ky, off_x, off_y, full_w, full_h, flags,
+ *   prepass_offset, dst_offset.
+ * tab_x / tab_y are the (in_w -> full_w) / (in_h -> full_h) tables of the UNFLIPPED sizes.  flags:
+ *   EGTR_AUGMENT_MIRROR         the source is read mirrored left-right (pixel x of the pass's input is stored pixel
+ *                               in_w - 1 - x); the flipped image is never written anywhere
+ *   EGTR_AUGMENT_SRC_WORKSPACE  src is a byte offset into `workspace` (the first pass's window) and not a pointer
+ *   EGTR_AUGMENT_PREPASS        the pass runs its horizontal part into workspace + prepass_offset first, for the
+ *                               input rows the window reads only: [rows][out_w][3] bytes with rows = ymin[off_y +
+ *                               out_h - 1] + n[off_y + out_h - 1] - ymin[off_y] of tab_y; required when some
+ *                               EGTR_PREPROCESS_TILE_W-column tile of the window reads more than
+ *                               EGTR_PREPROCESS_STAGE_BYTES bytes of an input row
+ * first_desc [batch][17]: the first resize of the two-resize branch, written as uint8 [out_h][out_w][3] to workspace +
+ *   dst_offset; out_h = 0 for an image on the one-resize branch.  May be NULL when first_rows is 0.
+ * final_desc [batch][17]: the resize into pixel_values (dst_offset unused); its source is the raw image or the first
+ *   pass's window.
+ * first_rows / first_cols: the largest out_h / out_w in first_desc (0 / 0: no first pass).  pre1_* / pre2_*: the largest
+ *   rows / out_w among the PREPASS images of first_desc / final_desc (0 / 0: none).  Workspace offsets are multiples of
+ *   16 and the regions do not overlap; workspace may be NULL when nothing uses it. */
+#define EGTR_AUGMENT_DESC_WORDS 17
+#define EGTR_AUGMENT_MIRROR 1
+#define EGTR_AUGMENT_SRC_WORKSPACE 2
+#define EGTR_AUGMENT_PREPASS 4
+int egtr_preprocess_augment_f32(egtr_stream_t stream, const int64_t* first_desc, const int64_t* final_desc, int batch,
+                                const int32_t* coeffs, const float* lut, int H, int W, int first_rows, int first_cols,
+                                int pre1_rows, int pre1_cols, int pre2_rows, int pre2_cols, uint8_t* workspace,
+                                float* pixel_values, int64_t* pixel_mask);
+int egtr_preprocess_augment_bf16(egtr_stream_t stream, const int64_t* first_desc, const int64_t* final_desc, int batch,
+                                 const int32_t* coeffs, const float* lut, int H, int W, int first_rows, int first_cols,
+                                 int pre1_rows, int pre1_cols, int pre2_rows, int pre2_cols, uint8_t* workspace,
+                                 uint16_t* pixel_values, int64_t* pixel_mask);
+
 #ifdef __cplusplus
 }
 #endif
