@@ -152,3 +152,138 @@ def det_inputs(g, seed):
     pm[1, :, vw:] = 0
     pv[1] = pv[1] * pm[1][None].float()
     return pv, pm
+
+
+# ---- the split-bf16 ("x6") arithmetic restated on the host (egtr_amd/csrc/xs_format.h, x6_common.h) -------------------------
+# A piece is an fp32 tensor whose low 16 bits are zero, i.e. a bf16 value.  bf16 shares fp32's exponent range, so its smallest
+# step is 2^-133: three 8-bit pieces hold all 24 bits of an fp32 x exactly only while x's last bit is >= 2^-133, i.e.
+# |x| >= 2^-110.  Below that (fp32 denormals included) the bits under 2^-133 are lost by any three-bf16 representation.
+SIX_TERMS = ((2, 0), (0, 2), (1, 1), (1, 0), (0, 1), (0, 0))      # (weight piece, activation piece), x6::mfma6's order
+SMALL_TERMS = ((2, 0), (0, 2), (1, 1))                             # w_lo a_hi, w_hi a_lo, w_mid a_mid
+# the small terms a paired operand family (``paired_operands``) resolves.  The third is exactly ZERO there -- "act": a_hi is equal
+# and w_lo opposite within a pair, "wgt": w_hi equal and a_lo opposite -- so leaving it out changes nothing; the two families
+# together cover all three.
+RESOLVED_TERMS = {"act": ((0, 2), (1, 1)), "wgt": ((2, 0), (1, 1))}
+
+
+def _f32_bits(x):
+    return x.contiguous().view(torch.int32).to(torch.int64) & 0xffffffff
+
+
+def _bits_f32(u):
+    u = u & 0xffffffff
+    return torch.where(u >= 2 ** 31, u - 2 ** 32, u).to(torch.int32).view(torch.float32)
+
+
+def _trunc_bf16(x):
+    return _bits_f32(_f32_bits(x) & 0xffff0000)
+
+
+def _rne_bf16(x):
+    u = _f32_bits(x)
+    mag = u & 0x7fffffff
+    r = (u + 0x7fff + ((u >> 16) & 1)) & 0xffff0000
+    r = torch.where(mag > 0x7f800000, torch.full_like(u, 0x7fc00000), torch.where(mag == 0x7f800000, u, r))
+    return _bits_f32(r)
+
+
+def split3_trunc(x):
+    """xs::split3 of an activation: hi = the upper 16 bits of x, mid = the upper 16 bits of the exact residual x - hi, lo = the
+    rest (x - hi) - mid as the bf16 that is stored (its upper 16 bits: the whole of it while |x| >= 2^-110).  A non-finite x
+    keeps the inf / a quiet NaN in hi alone."""
+    assert x.dtype == torch.float32
+    u = _f32_bits(x)
+    fin = (u & 0x7f800000) != 0x7f800000
+    hi = _bits_f32(torch.where((u & 0x7fffffff) > 0x7f800000, torch.full_like(u, 0x7fc00000), u & 0xffff0000))
+    r = torch.where(fin, x - hi, torch.zeros_like(x))            # exact: hi is x with its low bits cleared
+    mid = _trunc_bf16(r)
+    lo = _trunc_bf16(r - mid)                                      # r - mid: exact
+    return hi, mid, lo
+
+
+def split3_rne(w):
+    """xs::split3_rne of a weight: every piece the bf16 nearest (ties to even) to what the pieces before it left over; the
+    residuals are exact in fp32."""
+    assert w.dtype == torch.float32
+    fin = (_f32_bits(w) & 0x7f800000) != 0x7f800000
+    hi = _rne_bf16(w)
+    r1 = torch.where(fin, w - hi, torch.zeros_like(w))
+    mid = _rne_bf16(r1)
+    lo = _rne_bf16(r1 - mid)
+    return hi, mid, lo
+
+
+def term_sum(op, a_pieces, w_pieces, terms, cache=None):
+    """sum over (wi, ai) in ``terms`` of op(a_pieces[ai], w_pieces[wi]) in fp64, ``op`` a LINEAR operator of each argument (a
+    matrix product, a convolution).  ``cache``: a dict that keeps the single products between calls on the same pieces."""
+    total = None
+    for wi, ai in terms:
+        if cache is not None and (wi, ai) in cache:
+            t = cache[(wi, ai)]
+        else:
+            t = op(a_pieces[ai].double(), w_pieces[wi].double())
+            if cache is not None:
+                cache[(wi, ai)] = t
+        total = t if total is None else total + t
+    return total
+
+
+def rel_fro(y, ref):
+    return float((y.double() - ref).norm() / ref.norm())
+
+
+def split_error_model(op, a, w, post=None, lost=SMALL_TERMS):
+    """(ref, E_model, E_loss) of one case: the fp64 result of the intact fp32 operands, the relative Frobenius error of the
+    six-term sum against it, and the smallest such error among the five-term sums that leave out one of ``lost`` in turn.
+    ``post``: a map applied to every restatement before the errors are taken (the stem's ReLU + max-pool)."""
+    post = post or (lambda t: t)
+    ap, wp, cache = split3_trunc(a), split3_rne(w), {}
+    ref = post(op(a.double(), w.double()))
+    e_model = rel_fro(post(term_sum(op, ap, wp, SIX_TERMS, cache)), ref)
+    e_loss = min(rel_fro(post(term_sum(op, ap, wp, [t for t in SIX_TERMS if t != out], cache)), ref) for out in lost)
+    return ref, e_model, e_loss
+
+
+def paired_operands(family, a_shape, w_shape, gen):
+    """(a, w) fp32 CPU tensors of the given shapes, the LAST dimension of both being the kernels' innermost K index (the
+    channel), whose leading products cancel in adjacent k pairs (2i, 2i + 1), so that the result is carried by the small pieces
+    alone.  w ~ N(0, 1 / fan-in).
+    "act": w[..., 2i+1] = -w[..., 2i]; a[..., 2i+1] has the leading bf16 piece (by truncation, as activations are split) of
+    a[..., 2i] and fresh random lower 16 bits: what remains is w (r - r'), carried by a_mid / a_lo.
+    "wgt": a[..., 2i+1] = -a[..., 2i]; w[..., 2i+1] has the leading bf16 piece (to nearest even, as weights are split) of
+    w[..., 2i] and a fresh residual within half a bf16 step of it: what remains is a (r - r'), carried by w_mid / w_lo."""
+    assert a_shape[-1] == w_shape[-1] and a_shape[-1] % 2 == 0
+    fan_in = 1
+    for d in w_shape[1:]:
+        fan_in *= d
+    a = torch.randn(*a_shape, generator=gen)
+    w = torch.randn(*w_shape, generator=gen) / fan_in ** 0.5
+    if family == "act":
+        w[..., 1::2] = -w[..., 0::2]
+        low = torch.randint(0, 1 << 16, a[..., 0::2].shape, generator=gen)
+        a[..., 1::2] = _bits_f32((_f32_bits(a[..., 0::2]) & 0xffff0000) | low)
+        assert torch.equal(split3_trunc(a[..., 1::2].contiguous())[0], split3_trunc(a[..., 0::2].contiguous())[0])
+    elif family == "wgt":
+        a[..., 1::2] = -a[..., 0::2]
+        hi = split3_rne(w[..., 0::2].contiguous())[0]
+        low = torch.randint(-0x7fff, 0x8000, hi.shape, generator=gen)
+        w[..., 1::2] = _bits_f32(_f32_bits(hi) + low)             # bit arithmetic: fp32 steps, also across a binade
+        assert torch.equal(split3_rne(w[..., 1::2].contiguous())[0], hi)
+    else:
+        raise ValueError(family)
+    return a, w
+
+
+def xs_decode(buf, rows, K):
+    """The three pieces [rows, K] (fp32 tensors holding bf16 values) of an XS operand stream ``buf`` (flat uint8), from the
+    layout description of xs_format.h: fragment (row // 32, k // 16, piece p) at byte ((rb * (K / 16) + ks) * 3 + p) * 1024,
+    element (row % 32, k % 16) inside it at byte (kk // 8) * 512 + r * 16 + (kk % 8) * 2, little-endian bf16."""
+    assert buf.dtype == torch.uint8 and K % 16 == 0 and buf.numel() == ((rows + 31) // 32) * (K // 16) * 3 * 1024
+    half = buf.cpu().contiguous().view(torch.int16).to(torch.int64) & 0xffff
+    row, k = torch.arange(rows).view(-1, 1), torch.arange(K).view(1, -1)
+    rb, r, ks, kk = row // 32, row % 32, k // 16, k % 16
+    pieces = []
+    for p in range(3):
+        byte = ((rb * (K // 16) + ks) * 3 + p) * 1024 + (kk // 8) * 512 + r * 16 + (kk % 8) * 2
+        pieces.append(_bits_f32(half[byte // 2] << 16))
+    return tuple(pieces)
