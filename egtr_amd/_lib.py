@@ -7,6 +7,8 @@ entry point raises.  Build it with ``python -c "import __graft_entry__ as g; g.b
 import ctypes
 import os
 
+import torch
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # EGTR_HIP_LIBRARY: another build of the same library (same-box A/B of kernel builds: tools/*_bench.py, bench.py); there is
 # still no fallback -- a path that does not exist raises like a missing in-tree build
@@ -195,3 +197,49 @@ def check(status, what):
         if status == -2:
             msg += ": " + h.egtr_last_hip_error().decode()
         raise EgtrHipError(f"{what} failed: {msg} (status {status})")
+
+
+def _chk(t, name, dtype=None):
+    if not t.is_cuda:
+        raise RuntimeError(f"{name} must be a CUDA/HIP tensor")
+    if not t.is_contiguous():
+        raise RuntimeError(f"{name} tensor has to be contiguous")
+    if dtype is not None and t.dtype != dtype:
+        raise RuntimeError(f"{name} must be {dtype}, got {t.dtype}")
+    if t.data_ptr() % 16 != 0:
+        raise RuntimeError(f"{name} must be 16-byte aligned")
+    return t
+
+
+_RAW_STREAM = getattr(torch._C, "_cuda_getCurrentRawStream", None)
+
+
+def _stream():
+    """The raw handle of torch's current stream on the current device.  Every launch through the C ABI asks for it (~60 per
+    eager forward): the private raw accessor answers in ~0.3 us, ``torch.cuda.current_stream().cuda_stream`` builds a Stream
+    object first (~6 us: 0.4 ms of host time per forward, and the eager forward is host-bound)."""
+    if _RAW_STREAM is not None:
+        return _RAW_STREAM(torch.cuda.current_device())
+    return torch.cuda.current_stream().cuda_stream
+
+
+def launch(name, *args, what=None):
+    """Call the entry ``name`` of the library on torch's current stream (its first argument); a non-zero status raises what
+    ``check(status, what or name)`` raises.  A plain call with no per-argument work: the eager forward is host-bound."""
+    st = getattr(lib(), name)(_stream(), *args)
+    if st != 0:
+        check(st, what or name)
+
+
+def ptr(t):
+    """The device address of an OPTIONAL operand: None (a NULL pointer for the C entry) when the tensor is absent."""
+    return None if t is None else t.data_ptr()
+
+
+def row_view(t, K):
+    """t [..., K] as the [rows, K] matrix the row-strided entries walk: a view when the inner stride is 1, the row stride a
+    multiple of 4 floats and the base 16-byte aligned (a column block of a wider buffer is fine), else a contiguous copy."""
+    t2 = t.reshape(-1, K)
+    if t2.stride(1) != 1 or t2.stride(0) % 4 or t2.data_ptr() % 16:
+        t2 = t2.contiguous()
+    return t2

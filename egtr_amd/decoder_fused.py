@@ -15,7 +15,6 @@ import os
 import torch
 
 from . import _lib
-from .load_custom import _stream
 
 # "0": the per-operation decoder (eight launches per layer) -- the A/B switch of tools/forward_breakdown.py
 ENABLED = os.environ.get("EGTR_DECODER_CLUSTER", "1") != "0"
@@ -169,7 +168,6 @@ def run(decoder, hidden_states, position_embeddings, reference_input, values, va
     q[0] / k[0] may be stride-0 expansions over the batch).  ``keep_bits``: the bit-packed copy of ``keep_mask``
     (``ops.level_geometry``'s fifth result), handed down explicitly; packed here when absent."""
     from . import ops
-    lib = _lib.lib()
     dev = hidden_states.device
     B, N, _ = hidden_states.shape
     nl = len(decoder.layers)
@@ -230,7 +228,6 @@ def run(decoder, hidden_states, position_embeddings, reference_input, values, va
         kbits = _check_keep_bits(keep_bits, B, S) if keep_bits is not None else pack_keep_bits(keep_mask, B, S)
     vals = values if values.is_contiguous() else values.contiguous()
     vb = value_bias.contiguous() if value_bias is not None else None
-    stream = _stream()
     nclusters = B * ((N + 7) // 8)
     for i, layer in enumerate(decoder.layers):
         c = consts[i]
@@ -244,10 +241,10 @@ def run(decoder, hidden_states, position_embeddings, reference_input, values, va
                                          B * N)
         a.pos, a.pos_rows = pos.data_ptr(), pos_rows
         a.reference_points = ref.data_ptr()
-        a.valid_ratios, a.ref_rows = (vr.data_ptr() if vr is not None else None), ref_rows
+        a.valid_ratios, a.ref_rows = _lib.ptr(vr), ref_rows
         a.value = vals[i].data_ptr()
-        a.value_bias = vb[i].data_ptr() if vb is not None else None
-        a.keep_bits = kbits.data_ptr() if kbits is not None else None
+        a.value_bias = _lib.ptr(None if vb is None else vb[i])
+        a.keep_bits = _lib.ptr(kbits)
         a.spatial_shapes, a.level_start_index = spatial_shapes.data_ptr(), level_start_index.data_ptr()
         a.x_out = states[i].data_ptr()
         if i + 1 < nl:
@@ -269,7 +266,7 @@ def run(decoder, hidden_states, position_embeddings, reference_input, values, va
         a.q_scale, a.ln_eps = scale, float(layer.self_attn_layer_norm.eps)
         a.batch, a.num_query, a.spatial_size, a.num_clusters = B, N, S, nclusters
         a.generation = 0
-        _lib.check(lib.egtr_decoder_layer_f32(stream, ctypes.byref(a)), "egtr_decoder_layer_f32")
+        _lib.launch("egtr_decoder_layer_f32", ctypes.byref(a))
     if not torch.cuda.is_current_stream_capturing():
         if dev.index not in _CHECKED:
             st = int(status.item())   # one synchronisation, on the first eager run per device

@@ -311,11 +311,11 @@ class SceneGraphRecall:
         ks = (ctypes.c_int * len(self.ks))(*self.ks)
         stream = torch.cuda.current_stream(dev.device).cuda_stream
         _lib.check(_lib.lib().egtr_sgg_eval_f32(
-            stream, inds.data_ptr(), inds.shape[2], scores.data_ptr() if scores is not None else None, boxes.data_ptr(),
+            stream, inds.data_ptr(), inds.shape[2], _lib.ptr(scores), boxes.data_ptr(),
             classes.data_ptr(), B, K, N, self.num_rel, d64[2 * B + 2:].data_ptr() if T else None, d64.data_ptr(), T,
             d_boxes.data_ptr() if G else None, d64[2 * B + 2 + 3 * T:].data_ptr() if G else None,
             d64[B + 1:].data_ptr(), G, ks, len(self.ks), self.iou_thresh, first_rank.data_ptr(), slab.data_ptr(),
-            acc.data_ptr() if acc is not None else None), "egtr_sgg_eval_f32")
+            _lib.ptr(acc)), "egtr_sgg_eval_f32")
         self.last_first_rank = first_rank[:T]
         return slab
 
@@ -780,7 +780,7 @@ class OpenImagesRelationMetrics:
         score = torch.empty(B, topk, dtype=torch.float32, device=device)
         count = torch.empty(B, dtype=torch.int32, device=device)
         _lib.check(h.egtr_oi_select_f32(stream, scores.data_ptr(), img_stride, row_stride, obj.data_ptr(),
-                                        pairs.data_ptr() if pairs is not None else None, pair_stride, B, M, N, R, topk,
+                                        _lib.ptr(pairs), pair_stride, B, M, N, R, topk,
                                         self.prd_k, ws.data_ptr(), sop.data_ptr(), score.data_ptr(), count.data_ptr()),
                    "egtr_oi_select_f32")
         # ragged GT packed into one pinned buffer, as SceneGraphRecall:

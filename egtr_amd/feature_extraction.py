@@ -114,15 +114,13 @@ class DeformableDetrFeatureExtractor:
         c = pixel_values_list[0].shape[0]
         if all(torch.is_tensor(x) and x.is_cuda for x in pixel_values_list):
             from . import _lib
-            from .load_custom import _stream
             dev = pixel_values_list[0].device
             imgs = [x.to(dtype=torch.float32).contiguous() for x in pixel_values_list]
             ptrs = torch.tensor([x.data_ptr() for x in imgs], dtype=torch.int64).to(dev, non_blocking=True)
             hw = torch.tensor([[int(x.shape[-2]), int(x.shape[-1])] for x in imgs], dtype=torch.int32).to(dev, non_blocking=True)
             pv = torch.empty(b, c, mh, mw, dtype=torch.float32, device=dev)
             pm = torch.empty(b, mh, mw, dtype=torch.int64, device=dev)
-            _lib.check(_lib.lib().egtr_pad_batch_f32(_stream(), ptrs.data_ptr(), hw.data_ptr(), b, c, mh, mw,
-                                                     pv.data_ptr(), pm.data_ptr()), "egtr_pad_batch_f32")
+            _lib.launch("egtr_pad_batch_f32", ptrs.data_ptr(), hw.data_ptr(), b, c, mh, mw, pv.data_ptr(), pm.data_ptr())
             del imgs   # (alive until the launch was enqueued on the stream that also frees them)
             return {"pixel_values": pv, "pixel_mask": pm}
         pv = torch.zeros(b, c, mh, mw, dtype=torch.float32)
@@ -353,7 +351,6 @@ class PreprocessBatch:
 
     def run(self, pixel_values=None, pixel_mask=None, dtype=torch.float32):
         from . import _lib
-        from .load_custom import _stream
         B, H, W = len(self.sizes), self.H, self.W
         if dtype not in (torch.float32, torch.bfloat16):
             raise ValueError(f"dtype must be torch.float32 or torch.bfloat16, got {dtype}")
@@ -366,11 +363,10 @@ class PreprocessBatch:
                 or not pixel_mask.is_contiguous()):
             raise ValueError("pixel_values / pixel_mask must be contiguous [B, 3, H, W] / [B, H, W] int64 tensors")
         entry = "egtr_preprocess_f32" if dtype == torch.float32 else "egtr_preprocess_bf16"
-        ws = self.workspace.data_ptr() if self.workspace is not None else None
+        ws = _lib.ptr(self.workspace)
         with torch.cuda.device(self.device):
-            _lib.check(getattr(_lib.lib(), entry)(_stream(), self.desc.data_ptr(), B, self.coeffs.data_ptr(),
-                                                  self.lut.data_ptr(), H, W, self.prepass_rows, self.prepass_cols, ws,
-                                                  pixel_values.data_ptr(), pixel_mask.data_ptr()), entry)
+            _lib.launch(entry, self.desc.data_ptr(), B, self.coeffs.data_ptr(), self.lut.data_ptr(), H, W, self.prepass_rows,
+                        self.prepass_cols, ws, pixel_values.data_ptr(), pixel_mask.data_ptr())
         return {"pixel_values": pixel_values, "pixel_mask": pixel_mask}
 
 
@@ -629,7 +625,6 @@ class AugmentBatch:
 
     def run(self, pixel_values=None, pixel_mask=None, dtype=torch.float32):
         from . import _lib
-        from .load_custom import _stream
         B, H, W = len(self.sizes), self.H, self.W
         if dtype not in (torch.float32, torch.bfloat16):
             raise ValueError(f"dtype must be torch.float32 or torch.bfloat16, got {dtype}")
@@ -642,12 +637,11 @@ class AugmentBatch:
                 or not pixel_mask.is_contiguous()):
             raise ValueError("pixel_values / pixel_mask must be contiguous [B, 3, H, W] / [B, H, W] int64 tensors")
         entry = "egtr_preprocess_augment_f32" if dtype == torch.float32 else "egtr_preprocess_augment_bf16"
-        ws = self.workspace.data_ptr() if self.workspace is not None else None
-        first = self.first.data_ptr() if self.first is not None else None
+        ws = _lib.ptr(self.workspace)
+        first = _lib.ptr(self.first)
         with torch.cuda.device(self.device):
-            _lib.check(getattr(_lib.lib(), entry)(_stream(), first, self.final.data_ptr(), B, self.coeffs.data_ptr(),
-                                                  self.lut.data_ptr(), H, W, *self.extents, ws,
-                                                  pixel_values.data_ptr(), pixel_mask.data_ptr()), entry)
+            _lib.launch(entry, first, self.final.data_ptr(), B, self.coeffs.data_ptr(), self.lut.data_ptr(), H, W, *self.extents,
+                        ws, pixel_values.data_ptr(), pixel_mask.data_ptr())
         return {"pixel_values": pixel_values, "pixel_mask": pixel_mask}
 
 

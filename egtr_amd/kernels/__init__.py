@@ -1,0 +1,3 @@
+"""The binding layer below ``egtr_amd.ops``: one thin Python function per C entry of libegtr_hip.so, grouped the way csrc/ is
+grouped.  Nothing in this package reads a route switch or imports ``ops``; ``ops`` star-imports every module here and stays
+the public namespace."""

@@ -1,0 +1,163 @@
+"""Bindings of the relation-head forward kernels and their weight packers (csrc/rel_head*.hip), the device matcher
+(csrc/matcher.hip) and the target packing of the loss kernels.  No routing decisions here -- ``egtr_amd.ops`` decides and
+re-exports every name below."""
+import torch
+
+from .. import _lib
+from .._lib import _chk
+from .linear import _split3_bf16
+
+__all__ = ["rel_head_split_weights", "rel_head_streams", "relation_head_split_bf16", "hungarian_match",
+           "pack_detection_targets"]
+
+
+def rel_head_split_weights(w2r, w3r, w2c):
+    """The MFMA operand streams of rel_head_fwd_x6 (layouts documented in csrc/rel_head.hip):
+    w2x [8 nt][16 t][3 piece][64 lane][8] per MLP, w3x [8 nt][2 kb][OT][3 piece][64 lane][8] (relation MLP)."""
+    def w2x(w2):
+        p = _split3_bf16(w2).view(3, 8, 32, 16, 2, 8)         # [piece, nt, pi, t, hf, e]
+        return p.permute(1, 3, 0, 4, 2, 5).contiguous()        # [nt, t, piece, hf, pi, e]; lane = 32 hf + pi
+
+    R = w3r.shape[0]
+    OT = 1 if R <= 32 else 2
+    w3p = torch.zeros(32 * OT, w3r.shape[1], dtype=torch.float32, device=w3r.device)
+    w3p[:R] = w3r.detach().float()
+    q = _split3_bf16(w3p).view(3, OT, 32, w3r.shape[1])       # [piece, ot, pi, n]
+    dev = w3r.device
+    nt = torch.arange(8, device=dev).view(8, 1, 1, 1)
+    kb = torch.arange(2, device=dev).view(1, 2, 1, 1)
+    hf = torch.arange(2, device=dev).view(1, 1, 2, 1)
+    e = torch.arange(8, device=dev).view(1, 1, 1, 8)
+    nidx = 32 * nt + 16 * kb + (e & 3) + 8 * (e >> 2) + 4 * hf  # [nt, kb, hf, e]
+    g = q[:, :, :, nidx]                                        # [piece, ot, pi, nt, kb, hf, e]
+    w3x = g.permute(3, 4, 1, 0, 5, 2, 6).contiguous()           # [nt, kb, ot, piece, hf, pi, e]
+    return w2x(w2r), w3x, w2x(w2c)
+
+
+def rel_head_streams(w2r, w3r, w2c):
+    """``rel_head_split_weights`` as ONE launch (egtr_rel_head_streams_f32): the same three streams, bit for bit; what the
+    training forward rebuilds after every optimizer step."""
+    w2r_, w3r_, w2c_ = (_chk(t.detach().contiguous(), n, torch.float32)
+                        for t, n in ((w2r, "w2r"), (w3r, "w3r"), (w2c, "w2c")))
+    R = w3r_.shape[0]
+    OT = 1 if R <= 32 else 2
+    dev = w2r_.device
+    w2xr = torch.empty(8, 16, 3, 2, 32, 8, dtype=torch.bfloat16, device=dev)
+    w2xc = torch.empty(8, 16, 3, 2, 32, 8, dtype=torch.bfloat16, device=dev)
+    w3x = torch.empty(8, 2, OT, 3, 2, 32, 8, dtype=torch.bfloat16, device=dev)
+    _lib.launch("egtr_rel_head_streams_f32", w2r_.data_ptr(), w2c_.data_ptr(), w3r_.data_ptr(), w2r_.shape[1], R,
+                w2xr.data_ptr(), w2xc.data_ptr(), w3x.data_ptr())
+    return w2xr, w3x, w2xc
+
+
+def relation_head_split_bf16(gate_q, gate_k, uq, uk, b1, w2x_rel, b2r, w3x_rel, b3r, w2x_conn, b2c, w3c, b3c,
+                             num_rel, triplet_dist=None, node_cls=None, want_gate_mean=False, sigmoid=False):
+    """Inference forward, fp32 in / fp32 out, layers 2 and 3 on the bf16 matrix cores from split operands
+    (egtr_rel_head_forward_bf16x6_f32; ``w2x_*`` / ``w3x_rel`` from ``rel_head_split_weights``).  No autograd."""
+    B, N, T = gate_q.shape
+    dev = gate_q.device
+    f32 = [_chk(t.detach().contiguous(), n, torch.float32)
+           for t, n in ((gate_q, "gate_q"), (gate_k, "gate_k"), (uq, "uq"), (uk, "uk"), (b1, "b1"), (b2r, "b2r"),
+                        (b3r, "b3r"), (b2c, "b2c"), (w3c, "w3c"), (b3c, "b3c"))]
+    gq, gk, uq_, uk_, b1_, b2r_, b3r_, b2c_, w3c_, b3c_ = f32
+    R = int(num_rel)
+    OT = 1 if R <= 32 else 2
+    for t, n, shape in ((w2x_rel, "w2x_rel", (8, 16, 3, 2, 32, 8)), (w2x_conn, "w2x_conn", (8, 16, 3, 2, 32, 8)),
+                        (w3x_rel, "w3x_rel", (8, 2, OT, 3, 2, 32, 8))):
+        _chk(t, n, torch.bfloat16)
+        if tuple(t.shape) != shape:
+            raise RuntimeError(f"{n} must have shape {shape}, got {tuple(t.shape)}")
+    rel = torch.empty(B, N, N, R, dtype=torch.float32, device=dev)
+    conn = torch.empty(B, N, N, dtype=torch.float32, device=dev)
+    gm = torch.zeros(T, dtype=torch.float32, device=dev) if want_gate_mean else None
+    td = None
+    c1 = 0
+    if triplet_dist is not None:
+        td = _chk(triplet_dist.detach().contiguous(), "triplet_dist", torch.float32)
+        _chk(node_cls, "node_cls", torch.int64)
+        c1 = td.shape[0]
+    _lib.launch("egtr_rel_head_forward_bf16x6_f32", gq.data_ptr(), gk.data_ptr(), uq_.data_ptr(), uk_.data_ptr(),
+                b1_.data_ptr(), w2x_rel.data_ptr(), b2r_.data_ptr(), w3x_rel.data_ptr(), b3r_.data_ptr(), w2x_conn.data_ptr(),
+                b2c_.data_ptr(), w3c_.data_ptr(), b3c_.data_ptr(), _lib.ptr(td), _lib.ptr(node_cls if td is not None else None),
+                B, N, T, 256, R, c1, rel.data_ptr(), conn.data_ptr(), _lib.ptr(gm), 1 if sigmoid else 0)
+    return rel, conn.unsqueeze(-1), gm
+
+
+@torch.no_grad()
+def hungarian_match(logits, pred_boxes, targets, class_cost, bbox_cost, giou_cost, cost_min=None,
+                    inverse_sigmoid_smoothing=None, cost_in=None, want_cost=False, want_status=False):
+    """DeformableDetrHungarianMatcher.forward on the device (egtr_hungarian_match_f32): cost matrix + linear sum
+    assignment per image in one launch, nothing copied to the host (the reference's ``.cpu()`` at dd:2985 is a device
+    synchronisation per step).  ``targets``: list of dicts with "class_labels" / "boxes" (device tensors); their COUNTS
+    are host integers (tensor shapes), so output shapes are static.  ``cost_min`` / ``inverse_sigmoid_smoothing``: the two
+    fp32 scalars of the adaptive-smoothing offset (dd:2992-2998) or None.  ``cost_in``: per-image [N, T_b] cost matrices
+    to solve instead (tests).  Returns (pred_idx, tgt_idx, match_cost) flat device tensors + the per-image counts
+    [+ cost blocks] [+ status]: entries of image b are sorted by query index, i.e. scipy's output order."""
+    lib = _lib.lib()
+    if cost_in is not None:
+        B = len(cost_in)
+        N = cost_in[0].shape[0]
+        dev = cost_in[0].device
+        sizes = [int(c.shape[1]) for c in cost_in]
+        cin = torch.cat([_chk(c.contiguous(), "cost_in", torch.float32).reshape(-1) for c in cost_in]) \
+            if sum(sizes) else torch.zeros(1, device=dev)
+        K = 0
+        lg = bx = ti = tb = None
+    else:
+        B, N, K = logits.shape
+        dev = logits.device
+        sizes = [int(t["boxes"].shape[0]) for t in targets]
+        lg = _chk(logits.detach().contiguous(), "logits", torch.float32)
+        bx = _chk(pred_boxes.detach().contiguous(), "pred_boxes", torch.float32)
+        ti = torch.cat([t["class_labels"] for t in targets]).to(device=dev, dtype=torch.int64).contiguous()
+        tb = torch.cat([t["boxes"] for t in targets]).to(device=dev, dtype=torch.float32).contiguous()
+        cin = None
+    n_out = [min(N, t) for t in sizes]
+    offs = [0]
+    for t in sizes:
+        offs.append(offs[-1] + t)
+    ooffs = [0]
+    for t in n_out:
+        ooffs.append(ooffs[-1] + t)
+    meta = torch.tensor(offs + ooffs, dtype=torch.int32).to(dev, non_blocking=True)   # two small host -> device copies
+    tot = max(ooffs[-1], 1)
+    pred_idx = torch.empty(tot, dtype=torch.int64, device=dev)
+    tgt_idx = torch.empty(tot, dtype=torch.int64, device=dev)
+    mcost = torch.empty(tot, dtype=torch.float32, device=dev)
+    cost_out = torch.empty(max(N * offs[-1], 1), dtype=torch.float32, device=dev) if want_cost else None
+    status = torch.zeros(B, dtype=torch.int32, device=dev) if want_status else None
+    smooth = 1 if cost_min is not None else 0
+    n_scr = lib.egtr_hungarian_match_scratch_doubles(N, max(sizes) if sizes else 0, offs[-1])
+    scratch = torch.empty(n_scr, dtype=torch.float64, device=dev) if n_scr > 0 else None
+    if max(sizes, default=0) > 0:
+        _lib.launch("egtr_hungarian_match_f32", _lib.ptr(lg), _lib.ptr(bx),
+                    ti.data_ptr() if ti is not None and ti.numel() else None,
+                    tb.data_ptr() if tb is not None and tb.numel() else None, meta.data_ptr(), meta.data_ptr() + 4 * (B + 1),
+                    B, N, K, max(sizes) if sizes else 0, float(class_cost), float(bbox_cost), float(giou_cost), smooth,
+                    float(cost_min) if smooth else 0.0, float(inverse_sigmoid_smoothing) if smooth else 0.0,
+                    pred_idx.data_ptr(), tgt_idx.data_ptr(), mcost.data_ptr(), _lib.ptr(cost_out), _lib.ptr(cin),
+                    _lib.ptr(status), _lib.ptr(scratch))
+    out = [pred_idx[:ooffs[-1]], tgt_idx[:ooffs[-1]], mcost[:ooffs[-1]], n_out]
+    if want_cost:
+        out.append([cost_out[N * offs[i]: N * offs[i + 1]].view(N, sizes[i]) for i in range(B)])
+    if want_status:
+        out.append(status)
+    return tuple(out)
+
+
+def pack_detection_targets(targets, device):
+    """Concatenated class labels / boxes of a batch + per-image offsets, built once per step and shared by the output
+    sets (main + auxiliary) of ``detection_losses``."""
+    sizes = [int(t["class_labels"].shape[0]) for t in targets]
+    offs = [0]
+    for n in sizes:
+        offs.append(offs[-1] + n)
+    if offs[-1]:
+        labels = torch.cat([t["class_labels"] for t in targets]).to(device=device, dtype=torch.int64).contiguous()
+        boxes = torch.cat([t["boxes"] for t in targets]).to(device=device, dtype=torch.float32).contiguous()
+    else:   # keep the kernel's pointers valid
+        labels = torch.zeros(1, dtype=torch.int64, device=device)
+        boxes = torch.zeros(1, 4, dtype=torch.float32, device=device)
+    toff = torch.tensor(offs, dtype=torch.int32).to(device, non_blocking=True)
+    lengths = torch.tensor(sizes, dtype=torch.float32).to(device, non_blocking=True)
+    return labels, boxes, toff, lengths

@@ -13,30 +13,7 @@ fallback (deformable_detr.py:1096-1101 swallows every exception): a failure here
 import torch
 
 from . import _lib
-
-
-def _chk(t, name, dtype=None):
-    if not t.is_cuda:
-        raise RuntimeError(f"{name} must be a CUDA/HIP tensor")
-    if not t.is_contiguous():
-        raise RuntimeError(f"{name} tensor has to be contiguous")
-    if dtype is not None and t.dtype != dtype:
-        raise RuntimeError(f"{name} must be {dtype}, got {t.dtype}")
-    if t.data_ptr() % 16 != 0:
-        raise RuntimeError(f"{name} must be 16-byte aligned")
-    return t
-
-
-_RAW_STREAM = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-
-
-def _stream():
-    """The raw handle of torch's current stream on the current device.  Every launch through the C ABI asks for it (~60 per
-    eager forward): the private raw accessor answers in ~0.3 us, ``torch.cuda.current_stream().cuda_stream`` builds a Stream
-    object first (~6 us: 0.4 ms of host time per forward, and the eager forward is host-bound)."""
-    if _RAW_STREAM is not None:
-        return _RAW_STREAM(torch.cuda.current_device())
-    return torch.cuda.current_stream().cuda_stream
+from ._lib import _chk, _stream  # noqa: F401  (both lived here first; importers keep working)
 
 
 def pack_keep_bits(mask, B, S):
@@ -60,7 +37,6 @@ class _MultiScaleDeformableAttention:
 
     @staticmethod
     def ms_deform_attn_forward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, im2col_step):
-        lib = _lib.lib()
         B, S, M, D = value.shape
         L = spatial_shapes.shape[0]
         Lq, P = sampling_loc.shape[1], sampling_loc.shape[4]
@@ -70,28 +46,19 @@ class _MultiScaleDeformableAttention:
             for t, n in ((value, "value"), (sampling_loc, "sampling_loc"), (attn_weight, "attn_weight")):
                 _chk(t, n, torch.float64)
             out = torch.empty(B, Lq, M * D, dtype=value.dtype, device=value.device)
-            st = lib.egtr_msda_forward_f64(_stream(), value.data_ptr(), spatial_shapes.data_ptr(),
-                                           level_start_index.data_ptr(), sampling_loc.data_ptr(),
-                                           attn_weight.data_ptr(), B, S, M, D, L, Lq, P, out.data_ptr())
-            _lib.check(st, "ms_deform_attn_forward")
+            _lib.launch("egtr_msda_forward_f64", value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(),
+                        sampling_loc.data_ptr(), attn_weight.data_ptr(), B, S, M, D, L, Lq, P, out.data_ptr(),
+                        what="ms_deform_attn_forward")
             return out
         _chk(sampling_loc, "sampling_loc", torch.float32)
         _chk(attn_weight, "attn_weight", torch.float32)
-        if value.dtype == torch.float32:
-            _chk(value, "value")
-            out = torch.empty(B, Lq, M * D, dtype=value.dtype, device=value.device)
-            st = lib.egtr_msda_forward_f32(_stream(), value.data_ptr(), spatial_shapes.data_ptr(),
-                                           level_start_index.data_ptr(), sampling_loc.data_ptr(),
-                                           attn_weight.data_ptr(), B, S, M, D, L, Lq, P, out.data_ptr())
-        elif value.dtype == torch.bfloat16:
-            _chk(value, "value")
-            out = torch.empty(B, Lq, M * D, dtype=value.dtype, device=value.device)
-            st = lib.egtr_msda_forward_bf16(_stream(), value.data_ptr(), spatial_shapes.data_ptr(),
-                                            level_start_index.data_ptr(), sampling_loc.data_ptr(),
-                                            attn_weight.data_ptr(), B, S, M, D, L, Lq, P, out.data_ptr())
-        else:
+        if value.dtype not in (torch.float32, torch.bfloat16):
             raise RuntimeError(f"ms_deform_attn_forward: unsupported dtype {value.dtype}")
-        _lib.check(st, "ms_deform_attn_forward")
+        _chk(value, "value")
+        out = torch.empty(B, Lq, M * D, dtype=value.dtype, device=value.device)
+        _lib.launch("egtr_msda_forward_f32" if value.dtype == torch.float32 else "egtr_msda_forward_bf16", value.data_ptr(),
+                    spatial_shapes.data_ptr(), level_start_index.data_ptr(), sampling_loc.data_ptr(), attn_weight.data_ptr(),
+                    B, S, M, D, L, Lq, P, out.data_ptr(), what="ms_deform_attn_forward")
         return out
 
     @staticmethod
@@ -108,7 +75,6 @@ class _MultiScaleDeformableAttention:
         value_bias [M*D]: ``value`` is the bias-free value projection and the bias is applied inside the kernel (times the
         sum of the in-range, unpadded corner weights).
         Returns (out [B,Lq,M*D], attention weights [B,Lq,M,L,P] or None)."""
-        lib = _lib.lib()
         B, S, M, D = value.shape
         L = spatial_shapes.shape[0]
         Lq, P = sampling_offsets.shape[1], sampling_offsets.shape[4]
@@ -120,8 +86,7 @@ class _MultiScaleDeformableAttention:
             raise RuntimeError(f"ms_deform_attn_forward_fused: reference_points must be [B, Lq, L, 2] or "
                                f"[B, Lq, L, 4], got {tuple(reference_points.shape)}")
         # 4-d reference boxes: loc = box.xy + offset / P * box.wh * 0.5 (deformable_detr.py:1074-1081)
-        entry = (lib.egtr_msda_forward_fused_box_f32 if reference_points.shape[-1] == 4
-                 else lib.egtr_msda_forward_fused_vbias_f32)
+        entry = "egtr_msda_forward_fused_box_f32" if reference_points.shape[-1] == 4 else "egtr_msda_forward_fused_vbias_f32"
 
         def rows(t, width, name):  # [B, Lq, width...] -> row stride in floats (dense inner dims, uniform row stride)
             if not t.is_cuda or t.dtype != torch.float32:
@@ -147,12 +112,9 @@ class _MultiScaleDeformableAttention:
             vb = _chk(value_bias.detach().contiguous(), "value_bias", torch.float32)
             if vb.numel() != M * D:
                 raise RuntimeError(f"value_bias must have {M * D} elements, got {vb.numel()}")
-        st = entry(_stream(), value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(),
-                   off2.data_ptr(), log2.data_ptr(), reference_points.data_ptr(), B, S, M, D, L, Lq, P, out.data_ptr(),
-                   wts.data_ptr() if want_weights else None, ld_off, ld_log,
-                   km.data_ptr() if km is not None else None, kbits.data_ptr() if kbits is not None else None,
-                   vb.data_ptr() if vb is not None else None)
-        _lib.check(st, "ms_deform_attn_forward_fused")
+        _lib.launch(entry, value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(), off2.data_ptr(),
+                    log2.data_ptr(), reference_points.data_ptr(), B, S, M, D, L, Lq, P, out.data_ptr(), _lib.ptr(wts), ld_off,
+                    ld_log, _lib.ptr(km), _lib.ptr(kbits), _lib.ptr(vb), what="ms_deform_attn_forward_fused")
         return out, wts
 
     @staticmethod
@@ -160,7 +122,6 @@ class _MultiScaleDeformableAttention:
                                           reference_points, keep_mask=None, keep_bits=None):
         """bf16 counterpart of ``ms_deform_attn_forward_fused`` (M = 8, D = 32, L*P = 16): every tensor bf16, softmax and
         sampling locations formed in fp32 inside the kernel.  Returns out [B, Lq, M*D] bf16."""
-        lib = _lib.lib()
         B, S, M, D = value.shape
         L = spatial_shapes.shape[0]
         Lq, P = sampling_offsets.shape[1], sampling_offsets.shape[4]
@@ -188,11 +149,9 @@ class _MultiScaleDeformableAttention:
         elif keep_mask is not None:  # packed here, per call (the kernel keeps the bits of its image in LDS)
             kbits = pack_keep_bits(keep_mask, B, S)
         out = torch.empty(B, Lq, M * D, dtype=bf, device=value.device)
-        st = lib.egtr_msda_forward_fused_bf16(_stream(), value.data_ptr(), spatial_shapes.data_ptr(),
-                                              level_start_index.data_ptr(), off2.data_ptr(), log2.data_ptr(),
-                                              ref.data_ptr(), B, S, M, D, L, Lq, P, out.data_ptr(), ld_off, ld_log, None,
-                                              kbits.data_ptr() if kbits is not None else None)
-        _lib.check(st, "ms_deform_attn_forward_fused_bf16")
+        _lib.launch("egtr_msda_forward_fused_bf16", value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(),
+                    off2.data_ptr(), log2.data_ptr(), ref.data_ptr(), B, S, M, D, L, Lq, P, out.data_ptr(), ld_off, ld_log,
+                    None, _lib.ptr(kbits), what="ms_deform_attn_forward_fused_bf16")
         return out
 
     @staticmethod
@@ -211,11 +170,9 @@ class _MultiScaleDeformableAttention:
             grad_value = torch.zeros_like(value)
             grad_loc = torch.empty_like(sampling_loc)
             grad_attn = torch.empty_like(attn_weight)
-            st = lib.egtr_msda_backward_f64(_stream(), grad_output.data_ptr(), value.data_ptr(),
-                                            spatial_shapes.data_ptr(), level_start_index.data_ptr(),
-                                            sampling_loc.data_ptr(), attn_weight.data_ptr(), B, S, M, D, L, Lq, P,
-                                            grad_value.data_ptr(), grad_loc.data_ptr(), grad_attn.data_ptr())
-            _lib.check(st, "ms_deform_attn_backward")
+            _lib.launch("egtr_msda_backward_f64", grad_output.data_ptr(), value.data_ptr(), spatial_shapes.data_ptr(),
+                        level_start_index.data_ptr(), sampling_loc.data_ptr(), attn_weight.data_ptr(), B, S, M, D, L, Lq, P,
+                        grad_value.data_ptr(), grad_loc.data_ptr(), grad_attn.data_ptr(), what="ms_deform_attn_backward")
             return grad_value, grad_loc, grad_attn
         if value.dtype == torch.bfloat16:     # bf16 values / upstream gradient, fp32 geometry and gradients
             _chk(value, "value", torch.bfloat16)
@@ -228,12 +185,10 @@ class _MultiScaleDeformableAttention:
             # (0 for the model's shapes: the kernels read the bf16 operands directly; other shapes widen them into a workspace)
             nws = int(lib.egtr_msda_backward_bf16_workspace_floats(B, S, M, D, L, Lq, P))
             ws = torch.empty(nws, dtype=torch.float32, device=value.device) if nws else None
-            st = lib.egtr_msda_backward_bf16(_stream(), grad_output.data_ptr(), value.data_ptr(),
-                                             spatial_shapes.data_ptr(), level_start_index.data_ptr(),
-                                             sampling_loc.data_ptr(), attn_weight.data_ptr(), B, S, M, D, L, Lq, P,
-                                             gv32.data_ptr(), grad_loc.data_ptr(), grad_attn.data_ptr(),
-                                             ws.data_ptr() if ws is not None else None)
-            _lib.check(st, "ms_deform_attn_backward")
+            _lib.launch("egtr_msda_backward_bf16", grad_output.data_ptr(), value.data_ptr(), spatial_shapes.data_ptr(),
+                        level_start_index.data_ptr(), sampling_loc.data_ptr(), attn_weight.data_ptr(), B, S, M, D, L, Lq, P,
+                        gv32.data_ptr(), grad_loc.data_ptr(), grad_attn.data_ptr(), _lib.ptr(ws),
+                        what="ms_deform_attn_backward")
             return gv32.to(torch.bfloat16), grad_loc, grad_attn
         for t, n in ((value, "value"), (sampling_loc, "sampling_loc"), (attn_weight, "attn_weight"),
                      (grad_output, "grad_output")):
@@ -243,11 +198,9 @@ class _MultiScaleDeformableAttention:
         grad_value = torch.empty_like(value)
         grad_loc = torch.empty_like(sampling_loc)
         grad_attn = torch.empty_like(attn_weight)
-        st = lib.egtr_msda_backward_out_f32(_stream(), grad_output.data_ptr(), value.data_ptr(),
-                                        spatial_shapes.data_ptr(), level_start_index.data_ptr(),
-                                        sampling_loc.data_ptr(), attn_weight.data_ptr(), B, S, M, D, L, Lq,
-                                        P, grad_value.data_ptr(), grad_loc.data_ptr(), grad_attn.data_ptr())
-        _lib.check(st, "ms_deform_attn_backward")
+        _lib.launch("egtr_msda_backward_out_f32", grad_output.data_ptr(), value.data_ptr(), spatial_shapes.data_ptr(),
+                    level_start_index.data_ptr(), sampling_loc.data_ptr(), attn_weight.data_ptr(), B, S, M, D, L, Lq, P,
+                    grad_value.data_ptr(), grad_loc.data_ptr(), grad_attn.data_ptr(), what="ms_deform_attn_backward")
         return grad_value, grad_loc, grad_attn
 
 

@@ -306,8 +306,9 @@ class DataParallelTrainer:
         (torch.cuda.make_graphed_callables over ``model.forward_tensors``) and replayed; the Hungarian matcher and the
         loss stay eager in between (they have data-dependent shapes).  Measured SLOWER than the eager step: the
         untraced eager step is GPU-bound with the host 25-40 ms ahead of the device, so a replay has no launch gaps to close,
-        and it adds copies out of the graphs' static buffers (forward 15.1 vs 14.2 ms, backward 35.4 vs 29.9 ms).  Opt-in."""
-        """``grad_compression``: None (fp32 all-reduce, the reference's DDP), "bf16" or "fp16" -- DDP's communication hook that
+        and it adds copies out of the graphs' static buffers (forward 15.1 vs 14.2 ms, backward 35.4 vs 29.9 ms).  Opt-in.
+
+        ``grad_compression``: None (fp32 all-reduce, the reference's DDP), "bf16" or "fp16" -- DDP's communication hook that
         casts every gradient bucket to 16 bits for the all-reduce and back (torch's ``bf16_compress_hook`` / ``fp16_compress_hook``):
         half the bytes per link for the bandwidth-bound stress configuration (SURVEY 2b; 165 MB fp32 per step otherwise).  The
         averaged gradient is then rounded to 8 / 11 significant bits before clipping -- opt-in, not the parity configuration."""

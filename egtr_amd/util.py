@@ -99,9 +99,7 @@ def _bbox_pairs(boxes, query_boxes, mode):
         from . import _lib
         a, q = a.contiguous(), q.contiguous()
         out = torch.empty(a.shape[0], q.shape[0], dtype=torch.float64, device=a.device)
-        st = _lib.lib().egtr_bbox_overlaps_f64(torch.cuda.current_stream().cuda_stream, a.data_ptr(), q.data_ptr(),
-                                               a.shape[0], q.shape[0], mode, out.data_ptr())
-        _lib.check(st, "egtr_bbox_overlaps_f64")
+        _lib.launch("egtr_bbox_overlaps_f64", a.data_ptr(), q.data_ptr(), a.shape[0], q.shape[0], mode, out.data_ptr())
         return out
     # host tensors (the reference's own habitat for this routine): the same arithmetic, vectorised
     iw = torch.minimum(a[:, None, 2], q[None, :, 2]) - torch.maximum(a[:, None, 0], q[None, :, 0]) + 1
