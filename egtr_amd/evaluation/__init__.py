@@ -1,0 +1,88 @@
+"""Evaluation metrics accumulated where the model outputs live, one module per metric, each with its HIP kernels and a
+host implementation of the same semantics (the module docstrings state them):
+  * ``sgg``   scene-graph Recall@K / mean Recall@K (``SceneGraphRecall``; csrc/sgg_eval.hip);
+  * ``oi``    Open Images relation mAP / recall / score (``OpenImagesRelationMetrics``; csrc/oi_eval.hip);
+  * ``coco``  COCO box-detection AP / AR (``CocoDetectionMetrics``; csrc/coco_eval.hip);
+  * ``_common``  what they share: the GT entry, the first-rank matching, staging, accumulator, checks, record exchange.
+``evaluate`` below drives a model over batches and scores whichever of them are enabled.
+"""
+import types
+
+import torch
+
+from ._common import (_MAX_CAND, _MAX_K, _MAX_REL, _bbox_iou_pyx, _tensor, first_ranks_host, gt_entry, numpy_argmax,  # noqa: F401
+                      rescale_bboxes)
+from .coco import (_COCO_MAX_CLS, _COCO_MAX_DET, _COCO_MAX_GT, _EPS, COCO_AREA_RNGS, COCO_IOU_THRS, COCO_MAX_DETS,  # noqa: F401
+                   COCO_REC_THRS, COCO_STATS, CocoDetectionMetrics, _coco_gt, _score_key, _segment_rank,
+                   coco_accumulate_host, coco_gt_entry, coco_iou_host, coco_match_host, coco_summarize)
+from .oi import (_OI_MAX_GT, _OI_MAX_PAIRS, _OI_MAX_PRDK, _OI_MAX_TOPK, OpenImagesRelationMetrics, _union,  # noqa: F401
+                 bbox_iou_f32, oi_ap_host, oi_select_host, oi_tp_host)
+from .sgg import SceneGraphRecall, _check_candidate  # noqa: F401
+
+
+@torch.no_grad()
+def evaluate(model, batches, num_labels, num_rel_labels, single=True, multiple=False, max_topk=100, graphed=True,
+             forward=None, oi=False, coco=False, feature_extractor=None):
+    """The Visual Genome path of the reference's ``evaluate`` (evaluate_egtr.py:40-127): run the model over ``batches``
+    (the reference's collate_fn format: pixel_values, pixel_mask, labels), build the candidates on the device
+    (``runtime.triplet_candidates``) and score them.  Returns the reference's ``metric_dict`` keys: ``R@k`` / ``mR@k``
+    of the multiple-predicate evaluator and ``(single)R@k`` / ``(single)mR@k`` of the single-predicate one.  The
+    model runs through a ``GraphedForward`` when ``graphed`` (and a GPU is present); one created here is released before
+    returning (``forward``: an existing ``GraphedForward`` to reuse instead, left as it is).  ``oi``: also score the
+    Open Images branch (``OpenImagesRelationMetrics`` on ``triplet_candidates(mode="oi")``) and add its keys --
+    w_rel_mAP, w_phr_mAP, microR@50, score, rel_mAP, phr_mAP, microR@k, and the per-image mean recalls as (oi)R@k.
+    ``coco``: also score the boxes (``feature_extractor.post_process`` with the targets' orig_size, default a
+    ``DeformableDetrFeatureExtractor``, into ``CocoDetectionMetrics(num_labels)``) and add the reference's "AP50"."""
+    from ..runtime import GraphedForward, triplet_candidates
+    if not (single or multiple or oi or coco):
+        raise ValueError("enable at least one of single / multiple / oi / coco")
+    model.eval()
+    device = next(model.parameters()).device
+    ev_s = SceneGraphRecall(num_rel_labels, multiple_preds=False) if single else None
+    ev_m = SceneGraphRecall(num_rel_labels, multiple_preds=True) if multiple else None
+    ev_oi = OpenImagesRelationMetrics(num_rel_labels) if oi else None
+    ev_coco = CocoDetectionMetrics(num_labels) if coco else None
+    if coco and feature_extractor is None:
+        from ..feature_extraction import DeformableDetrFeatureExtractor
+        feature_extractor = DeformableDetrFeatureExtractor()
+    fwd = forward
+    own = fwd is None and graphed and device.type == "cuda"
+    if own:
+        fwd = GraphedForward(model, enabled=True, strict=False)
+    try:
+        for batch in batches:
+            pv = batch["pixel_values"].to(device, non_blocking=True)
+            pm = batch["pixel_mask"].to(device, non_blocking=True)
+            if fwd is not None:
+                outputs = fwd(pv, pm)
+            else:
+                outputs = model(pixel_values=pv, pixel_mask=pm, output_attentions=False, output_attention_states=True,
+                                output_hidden_states=True)
+            targets = batch["labels"]
+            sizes = torch.stack([torch.as_tensor(t["orig_size"]).cpu() for t in targets])
+            if device.type == "cuda":   # a pageable host -> device copy would wait for the stream
+                sizes = sizes.pin_memory().to(device, non_blocking=True)
+            if ev_m is not None:
+                ev_m.update(triplet_candidates(outputs, num_labels, sizes, max_topk, mode="multiple"), targets)
+            if ev_s is not None:
+                ev_s.update(triplet_candidates(outputs, num_labels, sizes, max_topk, mode="single"), targets)
+            if ev_oi is not None:
+                ev_oi.update(triplet_candidates(outputs, num_labels, sizes, max_topk, mode="oi"), targets)
+            if ev_coco is not None:
+                boxes_out = types.SimpleNamespace(logits=outputs["logits"], pred_boxes=outputs["pred_boxes"])
+                ev_coco.update(feature_extractor.post_process(boxes_out, sizes), targets)
+    finally:
+        if own:
+            fwd.close()
+    metrics = {}
+    if ev_m is not None:
+        metrics.update(ev_m.compute())
+        metrics.update(ev_m.mean_recall())
+    if ev_s is not None:
+        metrics.update({f"(single){k}": v for k, v in ev_s.compute().items()})
+        metrics.update({f"(single){k}": v for k, v in ev_s.mean_recall().items()})
+    if ev_oi is not None:
+        metrics.update({(f"(oi){k}" if k.startswith("R@") else k): v for k, v in ev_oi.compute().items()})
+    if ev_coco is not None:
+        metrics["AP50"] = ev_coco.compute()["AP50"]
+    return metrics

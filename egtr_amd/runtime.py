@@ -164,6 +164,13 @@ class GraphedForward:
     def _drop_all(self):
         self._entries.clear()
 
+    def close(self):
+        """Release this object: take its hooks off the model and drop every captured graph."""
+        for h in self._hooks:
+            h.remove()
+        self._hooks.clear()
+        self._drop_all()
+
     # ---- capture / replay ----------------------------------------------------------------------------------------
     def _eager(self, pv, pm):
         return self.model(pixel_values=pv, pixel_mask=pm, output_attentions=False, output_attention_states=True,

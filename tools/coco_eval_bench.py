@@ -105,7 +105,7 @@ def main():
         e1.synchronize()
         pp_update_us = e0.elapsed_time(e1) * 1e3 / n
     finally:
-        fwd._drop_all()
+        fwd.close()
 
     big = CocoDetectionMetrics(C)
     synthetic_records(big, args.images, C, dev, seed=7)

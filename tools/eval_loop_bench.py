@@ -92,7 +92,7 @@ def main():
             e1.synchronize()
             kern[mode] = e0.elapsed_time(e1) * 1e3 / n
     finally:
-        fwd._drop_all()
+        fwd.close()
     print(json.dumps({"tool": "eval_loop_bench", "shape": [1, 3, bench.H_IMG, bench.W_IMG], "num_queries": cfg.num_queries,
                       "num_rel_labels": R, "batches": len(batches), "calculate_fps_images_s": round(fps, 2),
                       "evaluate_single_images_s": round(ev_single, 2), "evaluate_both_images_s": round(ev_both, 2),

@@ -68,7 +68,7 @@ def main():
         ev.compute()
         compute_ms = (time.perf_counter() - t0) * 1e3
     finally:
-        fwd._drop_all()
+        fwd.close()
     print(json.dumps({"tool": "oi_eval_bench", "shape": [1, 3, bench.H_IMG, bench.W_IMG],
                       "num_queries": cfg.num_queries, "num_labels": C, "num_rel_labels": R, "batches": len(batches),
                       "calculate_fps_images_s": round(fps, 2), "evaluate_oi_images_s": round(ev_oi, 2),

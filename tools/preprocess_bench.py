@@ -135,7 +135,7 @@ def model_bench(args, dev):
         ev_u8 = timed(uint8_batches)
         ev_f32_again = timed(lambda n: batches[:n])
     finally:
-        fwd._drop_all()
+        fwd.close()
     return {"calculate_fps_images_s": round(fps, 2), "evaluate_fp32_images_s": round(ev_f32, 2),
             "evaluate_fp32_again_images_s": round(ev_f32_again, 2), "evaluate_uint8_images_s": round(ev_u8, 2),
             "uint8_vs_fp32": round(ev_u8 / max(ev_f32, ev_f32_again), 3)}
