@@ -14,6 +14,8 @@
 // is reached (ties have equal logits; which of them the reference's topk returns is unspecified too).
 // Launches: prep | 3 x (histogram, find) | final (loss terms, dense d loss / d pred_rel, pair flags) | connectivity.
 // All counts stay on the device; the only inputs from the host are tensor shapes.
+// The passes that read the target are templates on a target accessor: dense fp32 [N, N, R] per image (the reference's format,
+// egtr_relation_loss_f32) or one 64-bit word per (subject, object) pair (egtr_relation_loss_bits_f32).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -51,13 +53,67 @@ __device__ __forceinline__ float bce_logits(float x, float y) {   // BCEWithLogi
   return fmaxf(x, 0.f) - x * y + log1pf(expf(-fabsf(x)));
 }
 
+// ---- target accessors: what the prep / histogram / final passes read the 0 / 1 relation target through -------------------
+// image(b) -> pair(row * N + col) -> at(r) = the target of predicate r between target rows `row` and `col`; count_block():
+// (number of non-zero targets, number of targets != 1) over the T x T block of matched target rows, this thread's share.
+struct DenseTarget {   // DEVICE array of per-image pointers to dense fp32 [N, N, R] tensors (the reference's format)
+  const float* const* rel;
+  struct Pair {
+    const float* p;
+    __device__ __forceinline__ float at(int r) const { return p[r]; }
+  };
+  struct Image {
+    const float* p;
+    int R;
+    __device__ __forceinline__ Pair pair(size_t rc) const { return Pair{p + rc * R}; }
+    __device__ __forceinline__ void count_block(const int64_t* tg, int T, int N, int tid, int nthreads, int& nt,
+                                                int& nf) const {
+      const int tot = T * T * R;
+      for (int e = tid; e < tot; e += nthreads) {
+        const int a = e / (T * R), rem = e - a * T * R, c = rem / R, r = rem - c * R;
+        const float t = p[((size_t)tg[a] * N + (size_t)tg[c]) * R + r];
+        nt += (t != 0.f);
+        nf += (t != 1.0f);
+      }
+    }
+  };
+  __device__ __forceinline__ Image image(int b, int N, int R) const { return Image{rel[b], R}; }
+};
+
+struct PackedTarget {   // [B, N, N] 64-bit words, bit r of word (row, col) = the target of predicate r (R <= 64): ONE load per pair
+  const unsigned long long* bits;
+  struct Pair {
+    unsigned long long w;
+    __device__ __forceinline__ float at(int r) const { return ((w >> r) & 1ull) ? 1.0f : 0.0f; }
+  };
+  struct Image {
+    const unsigned long long* w;
+    int R;
+    __device__ __forceinline__ Pair pair(size_t rc) const { return Pair{w[rc]}; }
+    __device__ __forceinline__ void count_block(const int64_t* tg, int T, int N, int tid, int nthreads, int& nt,
+                                                int& nf) const {
+      // popcount over the T x T words, masked to the low R bits; a false candidate is every element that is not true
+      const unsigned long long mask = R >= 64 ? ~0ull : ((1ull << R) - 1ull);
+      int n = 0;
+      for (int e = tid; e < T * T; e += nthreads) {
+        const int a = e / T, c = e - a * T;
+        n += __popcll(w[(size_t)tg[a] * N + (size_t)tg[c]] & mask);
+      }
+      nt += n;
+      nf += (tid == 0 ? T * T * R : 0) - n;   // summed over the workgroup: T T R - n_true
+    }
+  };
+  __device__ __forceinline__ Image image(int b, int N, int R) const { return Image{bits + (size_t)b * N * N, R}; }
+};
+
 constexpr int kPrepT = 1024;   // one workgroup per image, sixteen waves: the T x T x R count below is ~500 dependent gathers per thread with four
 // ---- prep: per image  tq (query -> target row), wq (1 - sigmoid(matching cost)), mq (matched), block counts ------------
+template <class Tgt>
 __global__ __launch_bounds__(kPrepT) void rel_loss_prep(const int64_t* __restrict__ pred_idx,
                                                      const int64_t* __restrict__ tgt_idx,
                                                      const float* __restrict__ match_cost,
                                                      const int* __restrict__ out_off,
-                                                     const float* const* __restrict__ target_rel, int N, int R,
+                                                     const Tgt target_rel, int N, int R,
                                                      float nonmatching_cost, int k_neg, int k_nm, ImgState* st,
                                                      int* tq, float* wq, unsigned char* mq, int* total_sel) {
   __shared__ int s_cnt[2];
@@ -106,15 +162,8 @@ __global__ __launch_bounds__(kPrepT) void rel_loss_prep(const int64_t* __restric
     __syncthreads();
   }
   // counts over the matched block: true = target != 0, false candidates = target != 1 (egtr:838-840)
-  const float* rel = target_rel[b];
   int nt = 0, nf = 0;
-  const int tot = T * T * R;
-  for (int e = tid; e < tot; e += kPrepT) {
-    const int a = e / (T * R), rem = e - a * T * R, c = rem / R, r = rem - c * R;
-    const float t = rel[((size_t)tgt_idx[o0 + a] * N + (size_t)tgt_idx[o0 + c]) * R + r];
-    nt += (t != 0.f);
-    nf += (t != 1.0f);
-  }
+  target_rel.image(b, N, R).count_block(tgt_idx + o0, T, N, tid, kPrepT, nt, nf);
   for (int o = 32; o > 0; o >>= 1) { nt += __shfl_xor(nt, o); nf += __shfl_xor(nf, o); }
   if ((tid & 63) == 0) { atomicAdd(&s_cnt[0], nt); atomicAdd(&s_cnt[1], nf); }
   __syncthreads();
@@ -141,9 +190,9 @@ __global__ __launch_bounds__(kPrepT) void rel_loss_prep(const int64_t* __restric
 }
 
 // ---- histogram pass: digit PASS (0: bits 31..21, 1: bits 20..10, 2: bits 9..0) of the candidates under the prefix --------
-template <int PASS>
+template <int PASS, class Tgt>
 __global__ __launch_bounds__(kLT) void rel_loss_hist(const float* __restrict__ pred_rel,
-                                                     const float* const* __restrict__ target_rel, int N, int R,
+                                                     const Tgt target_rel, int N, int R,
                                                      const ImgState* __restrict__ st, const int* __restrict__ tq,
                                                      const unsigned char* __restrict__ mq, unsigned* __restrict__ hist) {
   __shared__ unsigned s_h[2][kBins];
@@ -154,7 +203,7 @@ __global__ __launch_bounds__(kLT) void rel_loss_hist(const float* __restrict__ p
   __syncthreads();
   const int* tq_b = tq + (size_t)b * N;
   const unsigned char* mq_b = mq + (size_t)b * N;
-  const float* rel = target_rel[b];
+  const typename Tgt::Image rel = target_rel.image(b, N, R);
   const float* pr = pred_rel + (size_t)b * N * N * R;
   const int NR = N * R;
   const float invR = 1.0f / (float)R;
@@ -172,7 +221,7 @@ __global__ __launch_bounds__(kLT) void rel_loss_hist(const float* __restrict__ p
       int prob;
       if (blk) {
         if (s.krem[0] <= 0) continue;
-        const float t = rel[(trow + tq_b[qb]) * R + (e - qb * R)];
+        const float t = rel.pair(trow + tq_b[qb]).at(e - qb * R);
         if (!(t != 1.0f)) continue;
         prob = 0;
       } else {
@@ -240,8 +289,9 @@ __global__ __launch_bounds__(kLT) void rel_loss_find(ImgState* st, const unsigne
 }
 
 // ---- final pass: loss terms, dense gradient, pair flags (target connectivity in query order) ---------------------------
+template <class Tgt>
 __global__ __launch_bounds__(kLT) void rel_loss_final(const float* __restrict__ pred_rel,
-                                                      const float* const* __restrict__ target_rel, int N, int R,
+                                                      const Tgt target_rel, int N, int R,
                                                       ImgState* st, const int* __restrict__ tq,
                                                       const float* __restrict__ wq, const unsigned char* __restrict__ mq,
                                                       const int* __restrict__ total_sel, float* __restrict__ grad_rel,
@@ -252,7 +302,7 @@ __global__ __launch_bounds__(kLT) void rel_loss_final(const float* __restrict__ 
   const int* tq_b = tq + (size_t)b * N;
   const float* wq_b = wq + (size_t)b * N;
   const unsigned char* mq_b = mq + (size_t)b * N;
-  const float* rel = target_rel[b];
+  const typename Tgt::Image rel = target_rel.image(b, N, R);
   const float* pr = pred_rel + (size_t)b * N * N * R;
   float* gr = grad_rel + (size_t)b * N * N * R;
   unsigned char* pf = pairflag + (size_t)b * N * N;
@@ -268,7 +318,7 @@ __global__ __launch_bounds__(kLT) void rel_loss_final(const float* __restrict__ 
     const float wa = wq_b[qa];
     for (int e = tid; e < NR; e += kLT) {
       const int qb = (int)(((float)e + 0.5f) * invR);
-      const float t = rel[(trow + tq_b[qb]) * R + (e - qb * R)];
+      const float t = rel.pair(trow + tq_b[qb]).at(e - qb * R);
       if (t != 0.f) pf[(size_t)qa * N + qb] = 1;      // benign race: every writer stores 1
       const bool blk = ma && mq_b[qb];
       const float x = pr[(size_t)qa * NR + e];
@@ -374,17 +424,17 @@ extern "C" long long egtr_relation_loss_workspace_bytes(int batch, int num_query
   return bytes + 256;
 }
 
-// target_rel: DEVICE array of `batch` device pointers (image b's dense [N, N, R] target).  pred_idx / tgt_idx /
-// match_cost / out_offsets: the matcher's packed outputs (egtr_hungarian_match_f32).  workspace: device,
-// egtr_relation_loss_workspace_bytes() bytes, contents irrelevant (zeroed here).  loss_out[0] = loss_rel,
-// loss_out[1] = loss_connectivity; grad_rel [B,N,N,R] / grad_conn [B,N,N] = d loss / d logits.
-extern "C" int egtr_relation_loss_f32(egtr_stream_t stream, const float* pred_rel, const float* pred_conn,
-                                      const float* const* target_rel, const int64_t* pred_idx, const int64_t* tgt_idx,
-                                      const float* match_cost, const int* out_offsets, int batch, int num_query,
-                                      int num_rel, float nonmatching_cost, int sample_negatives, int sample_nonmatching,
-                                      float* loss_out, float* grad_rel, float* grad_conn, void* workspace) {
-  if (!pred_rel || !pred_conn || !target_rel || !pred_idx || !tgt_idx || !match_cost || !out_offsets || !loss_out ||
-      !grad_rel || !grad_conn || !workspace)
+// The launches of both entries.  pred_idx / tgt_idx / match_cost / out_offsets: the matcher's packed outputs
+// (egtr_hungarian_match_f32).  workspace: device, egtr_relation_loss_workspace_bytes() bytes, contents irrelevant (zeroed
+// here).  loss_out[0] = loss_rel, loss_out[1] = loss_connectivity; grad_rel [B,N,N,R] / grad_conn [B,N,N] = d loss / d logits.
+template <class Tgt>
+static int relation_loss_launch(egtr_stream_t stream, const float* pred_rel, const float* pred_conn, const Tgt target_rel,
+                                const int64_t* pred_idx, const int64_t* tgt_idx, const float* match_cost,
+                                const int* out_offsets, int batch, int num_query, int num_rel, float nonmatching_cost,
+                                int sample_negatives, int sample_nonmatching, float* loss_out, float* grad_rel,
+                                float* grad_conn, void* workspace) {
+  if (!pred_rel || !pred_conn || !pred_idx || !tgt_idx || !match_cost || !out_offsets || !loss_out || !grad_rel ||
+      !grad_conn || !workspace)
     return EGTR_E_ARG;
   if (batch <= 0 || num_query <= 0 || num_rel <= 0 || sample_negatives < 0 || sample_nonmatching < 0) return EGTR_E_ARG;
   if ((long long)num_query * num_rel >= (1 << 22) || num_query > 4096) return EGTR_E_UNSUPPORTED;
@@ -412,23 +462,55 @@ extern "C" int egtr_relation_loss_f32(egtr_stream_t stream, const float* pred_re
   p = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(p) + 7) & ~(uintptr_t)7);
   double* partial_rel = reinterpret_cast<double*>(p);
   double* partial_conn = partial_rel + B * rows;
-  hipLaunchKernelGGL(rel_loss_prep, dim3(batch), dim3(kPrepT), 0, st, pred_idx, tgt_idx, match_cost, out_offsets, target_rel,
-                     num_query, num_rel, nonmatching_cost, sample_negatives, sample_nonmatching, state, tq, wq, mq,
-                     total_sel);
+  hipLaunchKernelGGL(rel_loss_prep<Tgt>, dim3(batch), dim3(kPrepT), 0, st, pred_idx, tgt_idx, match_cost, out_offsets,
+                     target_rel, num_query, num_rel, nonmatching_cost, sample_negatives, sample_nonmatching, state, tq, wq,
+                     mq, total_sel);
   const dim3 gh(rows, batch), gf(2, batch);
-  hipLaunchKernelGGL(rel_loss_hist<0>, gh, dim3(kLT), 0, st, pred_rel, target_rel, num_query, num_rel, state, tq, mq, hist);
+  hipLaunchKernelGGL((rel_loss_hist<0, Tgt>), gh, dim3(kLT), 0, st, pred_rel, target_rel, num_query, num_rel, state, tq, mq,
+                     hist);
   hipLaunchKernelGGL(rel_loss_find<0>, gf, dim3(kLT), 0, st, state, hist);
-  hipLaunchKernelGGL(rel_loss_hist<1>, gh, dim3(kLT), 0, st, pred_rel, target_rel, num_query, num_rel, state, tq, mq, hist);
+  hipLaunchKernelGGL((rel_loss_hist<1, Tgt>), gh, dim3(kLT), 0, st, pred_rel, target_rel, num_query, num_rel, state, tq, mq,
+                     hist);
   hipLaunchKernelGGL(rel_loss_find<1>, gf, dim3(kLT), 0, st, state, hist);
-  hipLaunchKernelGGL(rel_loss_hist<2>, gh, dim3(kLT), 0, st, pred_rel, target_rel, num_query, num_rel, state, tq, mq, hist);
+  hipLaunchKernelGGL((rel_loss_hist<2, Tgt>), gh, dim3(kLT), 0, st, pred_rel, target_rel, num_query, num_rel, state, tq, mq,
+                     hist);
   hipLaunchKernelGGL(rel_loss_find<2>, gf, dim3(kLT), 0, st, state, hist);
-  hipLaunchKernelGGL(rel_loss_final, gh, dim3(kLT), 0, st, pred_rel, target_rel, num_query, num_rel, state, tq, wq, mq,
+  hipLaunchKernelGGL(rel_loss_final<Tgt>, gh, dim3(kLT), 0, st, pred_rel, target_rel, num_query, num_rel, state, tq, wq, mq,
                      total_sel, grad_rel, pairflag, partial_rel);
   const long long n_pairs = B * N * N;
   const int cblocks = (int)std::min<long long>((n_pairs + kLT - 1) / kLT, 1024);
   hipLaunchKernelGGL(conn_loss, dim3(cblocks), dim3(kLT), 0, st, pred_conn, pairflag, n_pairs, grad_conn, partial_conn,
                      partial_rel, (int)(B * rows), total_sel, done, loss_out);
   return egtr_check_launch();
+}
+
+// target_rel: DEVICE array of `batch` device pointers (image b's dense [N, N, R] target).
+extern "C" int egtr_relation_loss_f32(egtr_stream_t stream, const float* pred_rel, const float* pred_conn,
+                                      const float* const* target_rel, const int64_t* pred_idx, const int64_t* tgt_idx,
+                                      const float* match_cost, const int* out_offsets, int batch, int num_query,
+                                      int num_rel, float nonmatching_cost, int sample_negatives, int sample_nonmatching,
+                                      float* loss_out, float* grad_rel, float* grad_conn, void* workspace) {
+  if (!target_rel) return EGTR_E_ARG;
+  return relation_loss_launch(stream, pred_rel, pred_conn, DenseTarget{target_rel}, pred_idx, tgt_idx, match_cost,
+                              out_offsets, batch, num_query, num_rel, nonmatching_cost, sample_negatives,
+                              sample_nonmatching, loss_out, grad_rel, grad_conn, workspace);
+}
+
+// rel_bits: [batch, N, N] 64-bit words (egtr_pack_relations_u64), bit r of word (s, o) = the target of predicate r.  The same
+// passes, order and arithmetic as egtr_relation_loss_f32 on the dense form of the same target -- the results are bit-identical --
+// with one 8-byte load per (subject, object) pair where the dense accessor gathers one float per logit.
+extern "C" int egtr_relation_loss_bits_f32(egtr_stream_t stream, const float* pred_rel, const float* pred_conn,
+                                           const uint64_t* rel_bits, const int64_t* pred_idx, const int64_t* tgt_idx,
+                                           const float* match_cost, const int* out_offsets, int batch, int num_query,
+                                           int num_rel, float nonmatching_cost, int sample_negatives,
+                                           int sample_nonmatching, float* loss_out, float* grad_rel, float* grad_conn,
+                                           void* workspace) {
+  if (!rel_bits) return EGTR_E_ARG;
+  if (num_rel > 64) return EGTR_E_UNSUPPORTED;
+  return relation_loss_launch(stream, pred_rel, pred_conn,
+                              PackedTarget{reinterpret_cast<const unsigned long long*>(rel_bits)}, pred_idx, tgt_idx,
+                              match_cost, out_offsets, batch, num_query, num_rel, nonmatching_cost, sample_negatives,
+                              sample_nonmatching, loss_out, grad_rel, grad_conn, workspace);
 }
 
 // ---- detection losses of one output set (labels / boxes / cardinality, egtr:611-659, 661-670, 692-712) ------------------

@@ -18,6 +18,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import ops
+from . import targets as rel_targets
 from .deformable_detr import (DeformableDetrHungarianMatcher, DeformableDetrMLPPredictionHead, DeformableDetrModel,
                               MatchedIndices, detection_heads,
                               DeformableDetrPreTrainedModel, inverse_sigmoid)
@@ -422,6 +423,7 @@ class SceneGraphGenerationLoss(nn.Module):
                                  + 2 * matcher.giou_cost - torch.log(torch.tensor((1.0 / smoothing) - 1.0)))
         self.connectivity_loss = torch.nn.BCEWithLogitsLoss(reduction="none")
         self.force_device_relations = False  # tests: take the sync-light relation-loss path on CPU tensors too
+        self._rel_bits_cache = None          # (targets, device, words) of the step in flight, see _rel_bits()
 
     def loss_labels(self, outputs, targets, indices, matching_costs, num_boxes):
         """Focal classification loss (egtr:611-659)."""
@@ -447,14 +449,44 @@ class SceneGraphGenerationLoss(nn.Module):
         card_pred = (logits.argmax(-1) != logits.shape[-1] - 1).sum(1)
         return {"cardinality_error": F.l1_loss(card_pred.float(), tgt_lengths.float())}
 
+    def _rel_bits(self, targets, device):
+        """The packed words [B, N, N] of a batch of ``rel_triplets`` targets (egtr_amd.targets.pack_relations): packed once
+        per step by ``forward`` and shared by the loss terms; packed here when a term is called on its own."""
+        c = self._rel_bits_cache
+        if c is not None and c[0] is targets and c[1] == device:
+            return c[2]
+        return rel_targets.pack_relations(targets, self.num_object_queries, self.num_rel_labels, device)
+
+    def _dense_targets(self, targets, device):
+        """The targets with a dense fp32 [N, N, R] ``rel`` each -- what the routes that evaluate the reference's tensor
+        composition read: ``rel_triplets`` targets are MATERIALISED here (egtr_amd.targets.unpack_relations), N N R floats
+        per image on ``device``; targets that carry ``rel`` pass through untouched."""
+        if rel_targets.has_dense(targets):
+            return targets
+        bits = self._rel_bits(targets, device) if not any("rel" in t for t in targets) else None
+        return rel_targets.dense_targets(targets, self.num_object_queries, self.num_rel_labels, device, bits)
+
     @torch.no_grad()
     def loss_uncertainty(self, outputs, targets, indices, matching_costs, num_boxes):
         # egtr:671-690: mean of u[s] * u[o] over the non-zero target triplets of the matched block.  Evaluated as
         # (sum over pairs of count * u u^T) / (number of triplets): no nonzero() index list, no host synchronisation.
+        # ``rel_triplets`` targets: the count of a pair is the popcount of its packed word -- the distinct triplets whose
+        # subject and object are both matched; no dense target is built.
         num, den = [], []
-        for target, index, matching_cost in zip(targets, indices, matching_costs):
-            tidx = index[1].to(target["rel"].device)
-            cnt = (target["rel"][tidx][:, tidx] != 0).sum(-1).to(matching_cost.dtype)   # [T, T]
+        bits = None
+        if not any("rel" in t for t in targets):
+            bits = self._rel_bits(targets, matching_costs[0].device)
+        else:
+            targets = self._dense_targets(targets, matching_costs[0].device)
+        for b, (target, index, matching_cost) in enumerate(zip(targets, indices, matching_costs)):
+            if bits is not None:
+                tidx = index[1].to(bits.device)
+                shifts = torch.arange(self.num_rel_labels, dtype=torch.int64, device=bits.device)
+                words = bits[b][tidx][:, tidx]                                              # [T, T]
+                cnt = ((words.unsqueeze(-1) >> shifts) & 1).sum(-1).to(matching_cost.dtype)
+            else:
+                tidx = index[1].to(target["rel"].device)
+                cnt = (target["rel"][tidx][:, tidx] != 0).sum(-1).to(matching_cost.dtype)   # [T, T]
             u = matching_cost.sigmoid()
             num.append((cnt * torch.outer(u, u)).sum())
             den.append(cnt.sum())
@@ -472,6 +504,7 @@ class SceneGraphGenerationLoss(nn.Module):
         return losses
 
     def loss_masks(self, outputs, targets, indices, matching_costs, num_boxes):
+        # (the API stub of the reference: it reads ``masks`` only, never a relation target -- either target form passes)
         assert "pred_masks" in outputs, "No predicted masks found in outputs"
         src_idx = self._get_src_permutation_idx(indices)
         tgt_idx = self._get_tgt_permutation_idx(indices)
@@ -487,16 +520,24 @@ class SceneGraphGenerationLoss(nn.Module):
     def loss_relations(self, outputs, targets, indices, matching_costs, num_boxes):
         """egtr:754-815.  Index tensors are moved to the logits' device once per image (the reference indexes
         device tensors with CPU index tensors, egtr:761-785; same values)."""
+        dense = rel_targets.has_dense(targets)
+        packed = not dense and not any("rel" in t for t in targets)   # every target carries ``rel_triplets`` only
         if (self.model_training and outputs["pred_rel"].is_cuda and outputs["pred_rel"].dtype == torch.float32
                 and self.rel_sample_negatives is not None and self.rel_sample_nonmatching is not None
                 and self.rel_sample_negatives_largest and self.rel_sample_nonmatching_largest
                 and not self.force_device_relations
-                and all(t["rel"].is_cuda and t["rel"].dtype == torch.float32 for t in targets)):
-            # the training configuration (train_egtr.py:514-527): value and gradient in one HIP pass, no host sync
+                and ((dense and all(t["rel"].is_cuda and t["rel"].dtype == torch.float32 for t in targets))
+                     or packed)):
+            # the training configuration (train_egtr.py:514-527): value and gradient in one HIP pass, no host sync;
+            # ``rel_triplets`` targets as packed words (no dense target is built), dense ``rel`` targets as they are
             loss_rel, loss_conn = ops.relation_losses(
                 outputs["pred_rel"], outputs["pred_connectivity"], targets, indices, matching_costs,
-                float(self.nonmatching_cost), self.rel_sample_negatives, self.rel_sample_nonmatching)
+                float(self.nonmatching_cost), self.rel_sample_negatives, self.rel_sample_nonmatching,
+                rel_bits=self._rel_bits(targets, outputs["pred_rel"].device) if packed else None)
             return {"loss_rel": loss_rel, "loss_connectivity": loss_conn}
+        # every other route evaluates the reference's tensor composition on the dense target: ``rel_triplets`` targets are
+        # materialised per image (see _dense_targets) -- the reference's values
+        targets = self._dense_targets(targets, outputs["pred_rel"].device)
         if (self.model_training and (outputs["pred_rel"].is_cuda or self.force_device_relations)
                 and (self.rel_sample_negatives is not None or self.rel_sample_nonmatching is not None)
                 and (self.rel_sample_negatives is None or self.rel_sample_negatives_largest)
@@ -671,6 +712,19 @@ class SceneGraphGenerationLoss(nn.Module):
         return loss_map[loss](outputs, targets, indices, matching_costs, num_boxes)
 
     def forward(self, outputs, targets, matched=None):
+        """``_forward`` with the words of ``rel_triplets`` targets packed ONCE for the step (egtr_amd.targets.pack_relations)
+        and shared by the terms that read relation targets."""
+        if (any(name in self.losses for name in ("relations", "uncertainty")) and "pred_rel" in outputs
+                and not any("rel" in t for t in targets)):
+            dev = outputs["pred_rel"].device
+            self._rel_bits_cache = (targets, dev, rel_targets.pack_relations(
+                targets, self.num_object_queries, self.num_rel_labels, dev))
+        try:
+            return self._forward(outputs, targets, matched)
+        finally:
+            self._rel_bits_cache = None
+
+    def _forward(self, outputs, targets, matched=None):
         """egtr:953-1034.  ``num_boxes`` is per-rank (the reference's all-reduce is commented out, :976-980).
         ``matched``: the (indices, matching_costs) of the main outputs when the caller already ran the matcher."""
         outputs_without_aux = {k: v for k, v in outputs.items() if k not in ("auxiliary_outputs", "enc_outputs")}

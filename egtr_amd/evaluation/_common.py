@@ -18,9 +18,16 @@ def rescale_bboxes(boxes, orig_size):
 
 
 def gt_entry(target):
-    """The reference's ``gt_entry`` of one target dict (train_egtr.py:69-80), on the host."""
+    """The reference's ``gt_entry`` of one target dict (train_egtr.py:69-80), on the host.  A target with ``rel_triplets``
+    and no dense ``rel`` (egtr_amd.targets) gives its distinct rows in lexicographic order: what ``nonzero()`` returns on
+    the dense tensor of the same triplets."""
     t = {k: (v.cpu() if torch.is_tensor(v) else torch.as_tensor(v)) for k, v in target.items()}
-    return {"gt_relations": t["rel"].nonzero(),
+    if "rel" in t:
+        rels = t["rel"].nonzero()
+    else:
+        rels = t["rel_triplets"].long().reshape(-1, 3)
+        rels = torch.unique(rels, dim=0) if rels.shape[0] else rels
+    return {"gt_relations": rels,
             "gt_boxes": rescale_bboxes(t["boxes"].float(), t["orig_size"]),
             "gt_classes": t["class_labels"].long()}
 

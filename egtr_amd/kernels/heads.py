@@ -1,5 +1,6 @@
 """Bindings of the relation-head forward kernels and their weight packers (csrc/rel_head*.hip), the device matcher
-(csrc/matcher.hip) and the target packing of the loss kernels.  No routing decisions here -- ``egtr_amd.ops`` decides and
+(csrc/matcher.hip), the target packing of the loss kernels and the relation loss on dense / bit-packed targets (csrc/loss.hip,
+csrc/rel_targets.hip).  No routing decisions here -- ``egtr_amd.ops`` decides and
 re-exports every name below."""
 import torch
 
@@ -8,7 +9,7 @@ from .._lib import _chk
 from .linear import _split3_bf16
 
 __all__ = ["rel_head_split_weights", "rel_head_streams", "relation_head_split_bf16", "hungarian_match",
-           "pack_detection_targets"]
+           "pack_detection_targets", "pack_relation_bits", "relation_loss_launch"]
 
 
 def rel_head_split_weights(w2r, w3r, w2c):
@@ -161,3 +162,34 @@ def pack_detection_targets(targets, device):
     toff = torch.tensor(offs, dtype=torch.int32).to(device, non_blocking=True)
     lengths = torch.tensor(sizes, dtype=torch.float32).to(device, non_blocking=True)
     return labels, boxes, toff, lengths
+
+
+def pack_relation_bits(triplets, offsets, batch, total, num_query, num_rel):
+    """egtr_pack_relations_u64: concatenated device triplets int64 [total, 3] + int32 offsets [batch + 1] -> the words
+    int64 [batch, N, N] (bit p of word (s, o) set iff (s, o, p) is a triplet).  ``egtr_amd.targets.pack_relations`` is the
+    public route (host checks, the single pinned copy)."""
+    _chk(triplets, "triplets", torch.int64)
+    _chk(offsets, "offsets", torch.int32)
+    bits = torch.empty(batch, num_query, num_query, dtype=torch.int64, device=triplets.device)
+    _lib.launch("egtr_pack_relations_u64", triplets.data_ptr(), offsets.data_ptr(), int(batch), int(total), int(num_query),
+                int(num_rel), bits.data_ptr())
+    return bits
+
+
+def relation_loss_launch(pred_rel, pred_conn, target, packed, pred_idx, tgt_idx, match_cost, out_off, nonmatching_cost,
+                         sample_negatives, sample_nonmatching):
+    """egtr_relation_loss_f32 (``target``: the device table of per-image pointers to dense fp32 targets) or, with
+    ``packed``, egtr_relation_loss_bits_f32 (``target``: the words int64 [B, N, N]).  Returns (loss [2], grad_rel, grad_conn)."""
+    B, N, _, R = pred_rel.shape
+    dev = pred_rel.device
+    if packed and tuple(_chk(target, "rel_bits", torch.int64).shape) != (B, N, N):
+        raise RuntimeError(f"rel_bits must have shape {(B, N, N)}, got {tuple(target.shape)}")
+    loss = torch.empty(2, dtype=torch.float32, device=dev)
+    grad_rel = torch.empty_like(pred_rel)
+    grad_conn = torch.empty_like(pred_conn)
+    ws = torch.empty(int(_lib.lib().egtr_relation_loss_workspace_bytes(B, N)), dtype=torch.uint8, device=dev)
+    _lib.launch("egtr_relation_loss_bits_f32" if packed else "egtr_relation_loss_f32", pred_rel.data_ptr(),
+                pred_conn.data_ptr(), target.data_ptr(), pred_idx.data_ptr(), tgt_idx.data_ptr(), match_cost.data_ptr(),
+                out_off.data_ptr(), B, N, R, float(nonmatching_cost), int(sample_negatives), int(sample_nonmatching),
+                loss.data_ptr(), grad_rel.data_ptr(), grad_conn.data_ptr(), ws.data_ptr())
+    return loss, grad_rel, grad_conn

@@ -17,6 +17,7 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from . import _lib
+from . import targets as rel_targets
 from ._lib import _chk, _stream  # noqa: F401  (``_stream``: part of this namespace since the first round)
 from .kernels.backbone import *  # noqa: F401,F403
 from .kernels.derived import *  # noqa: F401,F403
@@ -1325,24 +1326,16 @@ def _relation_head(gate_q, gate_k, uq, uk, b1, w2r, b2r, w3r, b3r, w2c, b2c, w3c
 
 class RelationLossFunction(Function):
     """loss_rel / loss_connectivity of the SGG criterion (training mode, largest-score sampling) with their gradients
-    from one pass over the logits (csrc/loss.hip, egtr_relation_loss_f32); backward only scales the stored gradients."""
+    from one pass over the logits (csrc/loss.hip, egtr_relation_loss_f32; egtr_relation_loss_bits_f32 when ``packed``:
+    ``target`` is then the words [B, N, N] instead of the pointer table); backward only scales the stored gradients."""
 
     @staticmethod
-    def forward(ctx, pred_rel, pred_conn, target_ptrs, pred_idx, tgt_idx, match_cost, out_off, nonmatching_cost,
-                sample_negatives, sample_nonmatching):
-        lib = _lib.lib()
-        B, N, _, R = pred_rel.shape
+    def forward(ctx, pred_rel, pred_conn, target, pred_idx, tgt_idx, match_cost, out_off, nonmatching_cost,
+                sample_negatives, sample_nonmatching, packed=False):
         pr = _chk(pred_rel.detach().contiguous(), "pred_rel", torch.float32)
         pc = _chk(pred_conn.detach().contiguous(), "pred_connectivity", torch.float32)
-        dev = pr.device
-        loss = torch.empty(2, dtype=torch.float32, device=dev)
-        grad_rel = torch.empty_like(pr)
-        grad_conn = torch.empty_like(pc)
-        ws = torch.empty(int(lib.egtr_relation_loss_workspace_bytes(B, N)), dtype=torch.uint8, device=dev)
-        _lib.launch("egtr_relation_loss_f32", pr.data_ptr(), pc.data_ptr(), target_ptrs.data_ptr(), pred_idx.data_ptr(),
-                    tgt_idx.data_ptr(), match_cost.data_ptr(), out_off.data_ptr(), B, N, R, float(nonmatching_cost),
-                    int(sample_negatives), int(sample_nonmatching), loss.data_ptr(), grad_rel.data_ptr(), grad_conn.data_ptr(),
-                    ws.data_ptr())
+        loss, grad_rel, grad_conn = relation_loss_launch(pr, pc, target, packed, pred_idx, tgt_idx, match_cost, out_off,
+                                                         nonmatching_cost, sample_negatives, sample_nonmatching)
         ctx.save_for_backward(grad_rel, grad_conn)
         return loss[0], loss[1]
 
@@ -1350,7 +1343,7 @@ class RelationLossFunction(Function):
     @once_differentiable
     def backward(ctx, g_rel, g_conn):
         grad_rel, grad_conn = ctx.saved_tensors
-        return grad_rel * g_rel, grad_conn * g_conn, None, None, None, None, None, None, None, None
+        return grad_rel * g_rel, grad_conn * g_conn, None, None, None, None, None, None, None, None, None
 
 
 class ClampNonFiniteFunction(Function):
@@ -1443,13 +1436,24 @@ def detection_losses(logits, pred_boxes, flat_match, packed_targets, focal_alpha
 
 
 def relation_losses(pred_rel, pred_conn, targets, indices, matching_costs, nonmatching_cost, sample_negatives,
-                    sample_nonmatching):
+                    sample_nonmatching, rel_bits=None):
     """(loss_rel, loss_connectivity) for device tensors: see RelationLossFunction.  ``indices`` / ``matching_costs``: the
-    matcher's per-image device tensors; ``targets[b]["rel"]``: dense fp32 [N, N, R] on the device."""
+    matcher's per-image device tensors; ``targets[b]["rel"]``: dense fp32 [N, N, R] on the device.  Targets that carry
+    ``"rel_triplets"`` and no ``"rel"`` take the packed entry: ``rel_bits`` (``egtr_amd.targets.pack_relations``) when the
+    caller packed the batch already, else packed here -- no dense target exists on that route."""
     dev = pred_rel.device
-    rels = [_chk(t["rel"] if t["rel"].is_contiguous() else t["rel"].contiguous(), "target rel", torch.float32)
-            for t in targets]
-    ptrs = torch.tensor([r.data_ptr() for r in rels], dtype=torch.int64).to(dev, non_blocking=True)
+    packed = not rel_targets.has_dense(targets)
+    if packed:
+        if any("rel" in t for t in targets):
+            raise ValueError('a batch mixes dense "rel" targets and "rel_triplets" targets: convert one kind '
+                             "(egtr_amd.targets.dense_targets)")
+        if rel_bits is None:
+            rel_bits = rel_targets.pack_relations(targets, pred_rel.shape[1], pred_rel.shape[3], dev)
+        target = rel_bits
+    else:
+        rels = [_chk(t["rel"] if t["rel"].is_contiguous() else t["rel"].contiguous(), "target rel", torch.float32)
+                for t in targets]
+        target = torch.tensor([r.data_ptr() for r in rels], dtype=torch.int64).to(dev, non_blocking=True)
     offs = [0]
     for src, _ in indices:
         offs.append(offs[-1] + int(src.shape[0]))
@@ -1461,7 +1465,8 @@ def relation_losses(pred_rel, pred_conn, targets, indices, matching_costs, nonma
         pi = torch.zeros(1, dtype=torch.int64, device=dev)
         ti = torch.zeros(1, dtype=torch.int64, device=dev)
         mc = torch.zeros(1, dtype=torch.float32, device=dev)
-    out = RelationLossFunction.apply(pred_rel, pred_conn, ptrs, pi, ti, mc, out_off, nonmatching_cost,
-                                     sample_negatives, sample_nonmatching)
-    del rels   # (kept alive until the launches were enqueued; the caller's targets own the storage)
+    out = RelationLossFunction.apply(pred_rel, pred_conn, target, pi, ti, mc, out_off, nonmatching_cost,
+                                     sample_negatives, sample_nonmatching, packed)
+    if not packed:
+        del rels   # (kept alive until the launches were enqueued; the caller's targets own the storage)
     return out

@@ -1,0 +1,126 @@
+"""Relation targets as triplet lists and bit-packed words.
+
+The reference's dataset turns an image's relation triplets into a dense fp32 ``[num_queries, num_queries, 50]`` tensor on
+the host (data/visual_genome.py:74-80): 8 MB per image at N = 200 for a few dozen ones.  A target dict may carry the triplets
+themselves instead:
+
+  ``"rel_triplets"``  int64 [K, 3] rows (subject, object, predicate); the predicate is zero-based after the ``no_relation``
+                      category is removed (the values ``_get_rel_tensor`` indexes with).  K may be 0; a duplicated row means
+                      the same as one occurrence (the reference's indexed assignment).
+
+A dict that has ``"rel"`` is read as before, whatever else it carries.  Below the public interface the triplets become
+``rel_bits``: int64 [B, N, N] read as unsigned, bit p of word [b, s, o] set iff (s, o, p) is a triplet of image b (a target
+value is 0 or 1 and R <= 64 for every supported dataset).  The loss kernels read the words (csrc/loss.hip,
+egtr_relation_loss_bits_f32); ``unpack_relations`` gives the dense tensor back to the routes that evaluate the reference's
+tensor composition."""
+import torch
+
+from .kernels.heads import pack_relation_bits
+
+__all__ = ["MAX_REL_LABELS", "relation_triplets", "has_dense", "pack_relations", "unpack_relations", "dense_targets"]
+
+MAX_REL_LABELS = 64
+_INT64_MIN = -(1 << 63)
+
+
+def relation_triplets(rel_list):
+    """A ``rel.json`` entry (rows (subject, object, predicate) with ONE-based predicates, 0 = ``no_relation``) as the
+    ``"rel_triplets"`` tensor: int64 [K, 3], zero-based predicates."""
+    t = torch.as_tensor(rel_list, dtype=torch.int64).reshape(-1, 3).clone()
+    t[:, 2] -= 1
+    return t
+
+
+def has_dense(targets):
+    """Every target of the batch carries the dense ``"rel"`` tensor (which wins over ``"rel_triplets"``)."""
+    return all("rel" in t for t in targets)
+
+
+def _triplets_of(target):
+    if "rel_triplets" not in target:
+        raise KeyError('a target needs "rel" (dense fp32 [N, N, R]) or "rel_triplets" (int64 [K, 3])')
+    t = target["rel_triplets"]
+    if t.dim() != 2 or t.shape[1] != 3 or t.dtype != torch.int64:
+        raise ValueError(f"rel_triplets must be int64 [K, 3], got {t.dtype} {tuple(t.shape)}")
+    return t
+
+
+def _check_host(t, b, N, R):
+    if t.numel() == 0:
+        return
+    lo, hi = t.min(0).values.tolist(), t.max(0).values.tolist()
+    if min(lo) < 0 or hi[0] >= N or hi[1] >= N or hi[2] >= R:
+        raise ValueError(f"rel_triplets of image {b}: an index is outside [0, {N}) x [0, {N}) x [0, {R})")
+
+
+def _bit(p):
+    """1 << p as int64 for p in [0, 64): bit 63 is the sign bit (a shift by 63 would overflow)."""
+    return torch.where(p == 63, torch.full_like(p, _INT64_MIN), torch.ones_like(p) << p.clamp(max=62))
+
+
+def pack_relations(targets, num_queries, num_rel_labels, device):
+    """``rel_bits`` int64 [B, N, N] on ``device`` from the targets' ``"rel_triplets"``.  Host triplets are checked on the host
+    (ValueError for an index out of range), concatenated with their offsets in ONE pinned buffer and copied once; triplets
+    that already live on a device are not read back -- the pack kernel drops a row with an index out of range.  On a GPU
+    the words are built by egtr_pack_relations_u64 (one memset, one launch, no synchronisation), on the CPU by the tensor
+    composition of the same words."""
+    N, R = int(num_queries), int(num_rel_labels)
+    if not 1 <= R <= MAX_REL_LABELS:
+        raise ValueError(f"packed relation targets hold at most {MAX_REL_LABELS} predicates per pair, got {R}")
+    device = torch.device(device)
+    trips = [_triplets_of(t) for t in targets]
+    B = len(trips)
+    offs = [0]
+    for t in trips:
+        offs.append(offs[-1] + int(t.shape[0]))
+    total = offs[-1]
+    for b, t in enumerate(trips):
+        if not t.is_cuda:
+            _check_host(t, b, N, R)
+    if device.type != "cuda":
+        bits = torch.zeros(B * N * N, dtype=torch.int64, device=device)
+        if total:
+            t = torch.cat([x.to(device) for x in trips])
+            img = torch.repeat_interleave(torch.arange(B, device=device),
+                                          torch.tensor([x.shape[0] for x in trips], device=device))
+            ok = ((t >= 0).all(1) & (t[:, 0] < N) & (t[:, 1] < N) & (t[:, 2] < R))   # (device rows moved here: the kernel's guard)
+            rows = torch.unique(torch.cat([img[ok, None], t[ok]], 1), dim=0)         # distinct (b, s, o, p): a sum of bits is an OR
+            if rows.numel():
+                bits.index_add_(0, (rows[:, 0] * N + rows[:, 1]) * N + rows[:, 2], _bit(rows[:, 3]))
+        return bits.view(B, N, N)
+    if all(not t.is_cuda for t in trips):
+        n_off = 2 * ((B + 4) // 4)   # int32 [B + 1] at the head of the int64 buffer, padded to 16 bytes
+        host = torch.zeros(n_off + max(total, 1) * 3, dtype=torch.int64, pin_memory=True)
+        host[:n_off].view(torch.int32)[:B + 1] = torch.tensor(offs, dtype=torch.int32)
+        if total:
+            torch.cat(trips, out=host[n_off:].view(total, 3))
+        buf = host.to(device, non_blocking=True)
+        off_d, trip_d = buf[:n_off].view(torch.int32), buf[n_off:]
+    else:
+        trip_d = (torch.cat([t.to(device) for t in trips]) if total
+                  else torch.zeros(1, 3, dtype=torch.int64, device=device)).contiguous()
+        off_d = torch.tensor(offs, dtype=torch.int32).to(device, non_blocking=True)
+    with torch.cuda.device(device):
+        return pack_relation_bits(trip_d, off_d, B, total, N, R)
+
+
+def unpack_relations(rel_bits, b, num_rel_labels):
+    """The dense fp32 [N, N, R] target of image ``b`` (what ``_get_rel_tensor`` builds), on the device of ``rel_bits``."""
+    shifts = torch.arange(int(num_rel_labels), dtype=torch.int64, device=rel_bits.device)
+    return ((rel_bits[b].unsqueeze(-1) >> shifts) & 1).to(torch.float32)
+
+
+def dense_targets(targets, num_queries, num_rel_labels, device, rel_bits=None):
+    """The targets with a dense ``"rel"`` each: a target that already has one is passed through, the others get theirs from
+    the packed words (``rel_bits`` of the whole batch when the caller already packed it).  For the routes that evaluate the
+    reference's tensor composition; N N R floats per image."""
+    if has_dense(targets):
+        return targets
+    if rel_bits is None:
+        missing = [i for i, t in enumerate(targets) if "rel" not in t]
+        rel_bits = pack_relations([targets[i] for i in missing], num_queries, num_rel_labels, device)
+        where = {i: j for j, i in enumerate(missing)}
+    else:
+        where = {i: i for i in range(len(targets))}
+    return [t if "rel" in t else dict(t, rel=unpack_relations(rel_bits, where[i], num_rel_labels))
+            for i, t in enumerate(targets)]

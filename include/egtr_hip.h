@@ -470,6 +470,23 @@ int egtr_relation_loss_f32(egtr_stream_t stream, const float* pred_rel, const fl
                            float* grad_rel, float* grad_conn, void* workspace);
 long long egtr_relation_loss_workspace_bytes(int batch, int num_query);
 
+/* Relation targets as bit-packed words: rel_bits [batch, N, N] uint64, bit p of word (s, o) of image b set iff (s, o, p) is
+ * one of the image's relation triplets (the dense fp32 [N, N, R] target of the reference holds R <= 64 zeros / ones per
+ * pair: 8 bytes instead of 4 R).  triplets int64 [total, 3] rows (subject, object, predicate), the images' rows
+ * concatenated; offsets int32 [batch + 1]; both DEVICE memory.  rel_bits is fully overwritten (one memset + one launch,
+ * one 64-bit atomic OR per triplet; duplicates are harmless).  A triplet with an index outside [0, N) / [0, num_rel) is
+ * dropped, never written.  num_rel > 64: EGTR_E_UNSUPPORTED. */
+int egtr_pack_relations_u64(egtr_stream_t stream, const int64_t* triplets, const int* offsets, int batch, int total,
+                            int num_query, int num_rel, uint64_t* rel_bits);
+/* egtr_relation_loss_f32 on packed targets (rel_bits as egtr_pack_relations_u64 writes them) instead of the pointer
+ * table: the same passes, order, arithmetic and workspace; on the dense form of the same targets both entries return
+ * the same bits.  The target passes load one word per (subject, object) pair.  num_rel > 64: EGTR_E_UNSUPPORTED. */
+int egtr_relation_loss_bits_f32(egtr_stream_t stream, const float* pred_rel, const float* pred_conn,
+                                const uint64_t* rel_bits, const int64_t* pred_idx, const int64_t* tgt_idx,
+                                const float* match_cost, const int* out_offsets, int batch, int num_query, int num_rel,
+                                float nonmatching_cost, int sample_negatives, int sample_nonmatching, float* loss_out,
+                                float* grad_rel, float* grad_conn, void* workspace);
+
 /* IoU matrix of the reference's native evaluator routine, lib/fpn/box_intersections_cpu/bbox.pyx: mode 0 =
  * bbox_overlaps (:21-61), mode 1 = bbox_intersections (:64-108).  boxes [num_boxes, 4], query_boxes [num_query, 4]
  * (x0, y0, x1, y1), float64 like the reference (DTYPE = np.float), "+1 pixel" convention; out [num_boxes, num_query],
