@@ -172,7 +172,106 @@ __global__ __launch_bounds__(kThreads) void sgg_fold(const double* __restrict__ 
   if (j < W) egtr_fold_column(slab, B, W, acc, j);
 }
 
+// Zero-shot recall: the recall over the GT triplets whose (subject class, object class, predicate) never
+// occurs in training -- bit ((cs * C1 + co) * R + p) of seen_bits is clear.  Filtering the GT list changes no triplet's
+// match (the argument at the top of this file), so the first ranks sgg_match left behind are all it needs.  One WAVE per
+// image: lanes take the image's triplets 64 at a time and the ballots' population counts are the integer tallies.  Row of
+// nk + 2 doubles: recall at ks[j] = double(hits) / double(count) (0 without a zero-shot triplet), 1 = the image has one,
+// the number of them.  A triplet with an index, class or predicate out of range is not zero-shot.
+struct ZeroShotArgs {
+  const int* first_rank;            // [T]
+  const int64_t* gt_rels;           // [T, 3]
+  const int64_t* rel_off;           // [B + 1]
+  const int64_t* gt_classes;        // [G]
+  const int64_t* box_off;           // [B + 1]
+  const unsigned long long* seen;   // [ceil(C1 * C1 * R / 64)]
+  double* slab;                     // [B, nk + 2]
+  long long T, G;
+  int K, C1, R, nk;
+  int ks[kMaxK];
+};
+
+__global__ __launch_bounds__(64) void sgg_zero_shot(const ZeroShotArgs a) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const long long r0 = clamp_off(a.rel_off[b], a.T);
+  long long r1 = clamp_off(a.rel_off[b + 1], a.T);
+  if (r1 < r0) r1 = r0;
+  const long long g0 = clamp_off(a.box_off[b], a.G);
+  long long g1 = clamp_off(a.box_off[b + 1], a.G);
+  if (g1 < g0) g1 = g0;
+  const long long n_boxes = g1 - g0;
+  int hits[kMaxK];
+  for (int j = 0; j < kMaxK; ++j) hits[j] = 0;
+  int count = 0;
+  for (long long base = r0; base < r1; base += 64) {   // wave-uniform trip count: every lane reaches every ballot
+    const long long t = base + lane;
+    bool zs = false;
+    int fr = a.K;
+    if (t < r1) {
+      const long long s = a.gt_rels[t * 3], o = a.gt_rels[t * 3 + 1], p = a.gt_rels[t * 3 + 2];
+      if (s >= 0 && s < n_boxes && o >= 0 && o < n_boxes && p >= 0 && p < a.R) {
+        const long long cs = a.gt_classes[g0 + s], co = a.gt_classes[g0 + o];
+        if (cs >= 0 && cs < a.C1 && co >= 0 && co < a.C1) {
+          const long long bit = (cs * a.C1 + co) * a.R + p;
+          zs = !((a.seen[bit >> 6] >> (bit & 63)) & 1ull);
+          fr = a.first_rank[t];
+        }
+      }
+    }
+    count += __popcll(__ballot(zs));
+    for (int j = 0; j < kMaxK; ++j)
+      if (j < a.nk) hits[j] += __popcll(__ballot(zs && fr < a.ks[j] && fr < a.K));
+  }
+  double v = 0.0;   // lane j writes column j
+  for (int j = 0; j < kMaxK; ++j)
+    if (j == lane && j < a.nk) v = count ? (double)hits[j] / (double)count : 0.0;
+  if (lane == a.nk) v = count ? 1.0 : 0.0;
+  if (lane == a.nk + 1) v = (double)count;
+  if (lane < a.nk + 2) a.slab[(long long)b * (a.nk + 2) + lane] = v;
+}
+
 }  // namespace
+
+extern "C" int egtr_sgg_zero_shot_f64(egtr_stream_t stream, const int* first_rank, const int64_t* gt_rels,
+                                      const int64_t* rel_offsets, long long num_gt_rels, const int64_t* gt_classes,
+                                      const int64_t* box_offsets, long long num_gt_boxes, int batch, int num_cand,
+                                      int num_classes, int num_rel, const int64_t* seen_bits, const int* ks, int num_k,
+                                      double* slab, double* acc) {
+  if (batch < 0 || num_cand < 0 || num_cand > kMaxCand || num_classes < 1 || num_rel < 1 || num_rel > kMaxRel ||
+      num_k < 1 || num_k > kMaxK || num_gt_rels < 0 || num_gt_boxes < 0 || !ks)
+    return EGTR_E_ARG;
+  if ((long long)num_classes * num_classes * num_rel >= (1ll << 31)) return EGTR_E_UNSUPPORTED;
+  for (int j = 0; j < num_k; ++j)
+    if (ks[j] < 1 || (j > 0 && ks[j] <= ks[j - 1])) return EGTR_E_ARG;
+  if (batch == 0) return EGTR_OK;
+  if (!rel_offsets || !box_offsets || !seen_bits || !slab) return EGTR_E_ARG;
+  if (num_gt_rels > 0 && (!gt_rels || !first_rank)) return EGTR_E_ARG;
+  if (num_gt_boxes > 0 && !gt_classes) return EGTR_E_ARG;
+
+  ZeroShotArgs a;
+  a.first_rank = first_rank;
+  a.gt_rels = gt_rels;
+  a.rel_off = rel_offsets;
+  a.gt_classes = gt_classes;
+  a.box_off = box_offsets;
+  a.seen = reinterpret_cast<const unsigned long long*>(seen_bits);
+  a.slab = slab;
+  a.T = num_gt_rels;
+  a.G = num_gt_boxes;
+  a.K = num_cand;
+  a.C1 = num_classes;
+  a.R = num_rel;
+  a.nk = num_k;
+  for (int j = 0; j < kMaxK; ++j) a.ks[j] = j < num_k ? ks[j] : 0;
+
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(sgg_zero_shot, dim3((unsigned)batch), dim3(64), 0, s, a);
+  int st = egtr_check_launch();
+  if (st != EGTR_OK || !acc) return st;
+  const int W = num_k + 2;   // the rows fold like the recall slab: image order, one thread per column
+  hipLaunchKernelGGL(sgg_fold, dim3(1), dim3(kThreads), 0, s, slab, batch, W, acc);
+  return egtr_check_launch();
+}
 
 extern "C" long long egtr_sgg_eval_width(int num_rel, int num_k) {
   if (num_rel < 1 || num_rel > kMaxRel || num_k < 1 || num_k > kMaxK) return EGTR_E_ARG;

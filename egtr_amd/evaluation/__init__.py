@@ -11,7 +11,7 @@ import types
 import torch
 
 from ._common import (_MAX_CAND, _MAX_K, _MAX_REL, _bbox_iou_pyx, _tensor, first_ranks_host, gt_entry, numpy_argmax,  # noqa: F401
-                      rescale_bboxes)
+                      rescale_bboxes, seen_bits_host)
 from .coco import (_COCO_MAX_CLS, _COCO_MAX_DET, _COCO_MAX_GT, _EPS, COCO_AREA_RNGS, COCO_IOU_THRS, COCO_MAX_DETS,  # noqa: F401
                    COCO_REC_THRS, COCO_STATS, CocoDetectionMetrics, _coco_gt, _score_key, _segment_rank,
                    coco_accumulate_host, coco_gt_entry, coco_iou_host, coco_match_host, coco_summarize)
@@ -22,7 +22,7 @@ from .sgg import SceneGraphRecall, _check_candidate  # noqa: F401
 
 @torch.no_grad()
 def evaluate(model, batches, num_labels, num_rel_labels, single=True, multiple=False, max_topk=100, graphed=True,
-             forward=None, oi=False, coco=False, feature_extractor=None):
+             forward=None, oi=False, coco=False, feature_extractor=None, train_counts=None):
     """The Visual Genome path of the reference's ``evaluate`` (evaluate_egtr.py:40-127): run the model over ``batches``
     (the reference's collate_fn format: pixel_values, pixel_mask, labels), build the candidates on the device
     (``runtime.triplet_candidates``) and score them.  Returns the reference's ``metric_dict`` keys: ``R@k`` / ``mR@k``
@@ -32,14 +32,16 @@ def evaluate(model, batches, num_labels, num_rel_labels, single=True, multiple=F
     Open Images branch (``OpenImagesRelationMetrics`` on ``triplet_candidates(mode="oi")``) and add its keys --
     w_rel_mAP, w_phr_mAP, microR@50, score, rel_mAP, phr_mAP, microR@k, and the per-image mean recalls as (oi)R@k.
     ``coco``: also score the boxes (``feature_extractor.post_process`` with the targets' orig_size, default a
-    ``DeformableDetrFeatureExtractor``, into ``CocoDetectionMetrics(num_labels)``) and add the reference's "AP50"."""
+    ``DeformableDetrFeatureExtractor``, into ``CocoDetectionMetrics(num_labels)``) and add the reference's "AP50".
+    ``train_counts``: a ``RelationStatistics`` / ``fg_matrix`` of the training set (``SceneGraphRecall(train_counts=...)``);
+    adds the zero-shot recalls ``zR@k`` (multiple) and ``(single)zR@k``."""
     from ..runtime import GraphedForward, triplet_candidates
     if not (single or multiple or oi or coco):
         raise ValueError("enable at least one of single / multiple / oi / coco")
     model.eval()
     device = next(model.parameters()).device
-    ev_s = SceneGraphRecall(num_rel_labels, multiple_preds=False) if single else None
-    ev_m = SceneGraphRecall(num_rel_labels, multiple_preds=True) if multiple else None
+    ev_s = SceneGraphRecall(num_rel_labels, multiple_preds=False, train_counts=train_counts) if single else None
+    ev_m = SceneGraphRecall(num_rel_labels, multiple_preds=True, train_counts=train_counts) if multiple else None
     ev_oi = OpenImagesRelationMetrics(num_rel_labels) if oi else None
     ev_coco = CocoDetectionMetrics(num_labels) if coco else None
     if coco and feature_extractor is None:
@@ -78,9 +80,13 @@ def evaluate(model, batches, num_labels, num_rel_labels, single=True, multiple=F
     if ev_m is not None:
         metrics.update(ev_m.compute())
         metrics.update(ev_m.mean_recall())
+        if train_counts is not None:
+            metrics.update(ev_m.zero_shot())
     if ev_s is not None:
         metrics.update({f"(single){k}": v for k, v in ev_s.compute().items()})
         metrics.update({f"(single){k}": v for k, v in ev_s.mean_recall().items()})
+        if train_counts is not None:
+            metrics.update({f"(single){k}": v for k, v in ev_s.zero_shot().items()})
     if ev_oi is not None:
         metrics.update({(f"(oi){k}" if k.startswith("R@") else k): v for k, v in ev_oi.compute().items()})
     if ev_coco is not None:

@@ -76,6 +76,17 @@ def _tensor(x):
     return x if torch.is_tensor(x) else torch.as_tensor(x)
 
 
+def seen_bits_host(counts):
+    """The "occurs in training" bitset of a host count tensor (any shape, read row-major): int64 [ceil(n / 64)], bit
+    (i & 63) of word i >> 6 set iff counts.flatten()[i] > 0 -- what egtr_rel_seen_bits_i64 writes (csrc/rel_stats.hip)."""
+    seen = (counts.reshape(-1) > 0).long()
+    words = (seen.numel() + 63) // 64
+    seen = torch.cat([seen, seen.new_zeros(words * 64 - seen.numel())]).view(words, 64)
+    weight = torch.ones(64, dtype=torch.int64) << torch.arange(64).clamp(max=62)
+    weight[63] = -(1 << 63)     # bit 63 is the sign bit of the word
+    return (seen * weight).sum(1)
+
+
 # ---- argument checks ----------------------------------------------------------------------------------------------------
 def check_ks(num_rel_labels, ks):
     """The ``num_rel_labels`` / ``ks`` checks of the relation evaluators; returns ``ks`` as a tuple of ints."""

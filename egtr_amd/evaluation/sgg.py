@@ -16,11 +16,13 @@ Differences from the reference, on purpose:
 import ctypes
 import math
 
+import numpy as np
 import torch
 
 from .. import _lib
+from ..kernels.statistics import sgg_zero_shot
 from ._common import (_MAX_CAND, FlatAccumulator, StagingRing, backend_device, check_gt_predicates, check_ks,
-                      first_ranks_host, gt_entry, numpy_argmax, upload_relation_gt)
+                      first_ranks_host, gt_entry, numpy_argmax, placed, seen_bits_host, upload_relation_gt)
 
 
 def _check_candidate(c, multiple, num_rel):
@@ -44,9 +46,16 @@ class SceneGraphRecall(FlatAccumulator):
     ``multiple_preds=False``: graph-constrained (the reference's "single" evaluator: candidates [K, 2] + rel_scores
     [K, R], predicate = argmax of the row); ``True``: candidates [K, 3].  All metrics live in ONE flat float64 tensor
     ``acc`` (sums of per-image recalls, image counts, skipped count; see csrc/sgg_eval.hip for the layout), on the device
-    of the first ``update`` -- ``merge`` / ``all_reduce`` add it."""
+    of the first ``update`` -- ``merge`` / ``all_reduce`` add it.
 
-    def __init__(self, num_rel_labels, ks=(20, 50, 100), multiple_preds=False, iou_thresh=0.5, keep_per_image=False):
+    ``train_counts``: also accumulate the ZERO-SHOT recall -- the recall over the GT triplets whose
+    (subject class, object class, predicate) has count 0 in the training set.  A ``RelationStatistics``, an ``fg_matrix``
+    array [C1, C1, R], or a ``seen_bits`` tensor (then with ``train_num_labels`` = C1 - 1); read once, here.  Its state is
+    the separate flat float64 ``zs_acc`` [len(ks) + 2]: sums of per-image zero-shot recalls, the number of images with a
+    zero-shot GT triplet, the number of such triplets.  ``acc`` and ``width`` are the same with or without it."""
+
+    def __init__(self, num_rel_labels, ks=(20, 50, 100), multiple_preds=False, iou_thresh=0.5, keep_per_image=False,
+                 train_counts=None, train_num_labels=None):
         ks = check_ks(num_rel_labels, ks)
         if not math.isfinite(iou_thresh):
             raise ValueError("iou_thresh must be finite")
@@ -59,12 +68,44 @@ class SceneGraphRecall(FlatAccumulator):
         self.width = nk + 2 + R * (nk + 1)
         self._pbase, self._fbase = nk + 2, nk + 2 + R * nk
         self._ring = StagingRing()
+        self._seen_bits, self._zs_classes = None, 0
+        if train_counts is not None:
+            self._read_train_counts(train_counts, train_num_labels)
         self.reset()
+
+    def _read_train_counts(self, train_counts, train_num_labels):
+        R = self.num_rel
+        if callable(getattr(train_counts, "seen_bits", None)):       # a RelationStatistics
+            if train_counts.shape[2] != R:
+                raise ValueError(f"train_counts counts {train_counts.shape[2]} predicates, the evaluator {R}")
+            bits, C1 = train_counts.seen_bits(), train_counts.shape[0]
+        elif torch.is_tensor(train_counts) and train_counts.dim() == 1:
+            if train_num_labels is None:
+                raise ValueError("a seen_bits tensor needs train_num_labels")
+            bits, C1 = train_counts.long().contiguous(), int(train_num_labels) + 1
+        else:
+            fg = train_counts if torch.is_tensor(train_counts) else torch.from_numpy(np.ascontiguousarray(train_counts))
+            if fg.dim() != 3 or fg.shape[0] != fg.shape[1] or fg.shape[2] != R:
+                raise ValueError(f"an fg_matrix must be [C1, C1, {R}], got {tuple(fg.shape)}")
+            bits, C1 = seen_bits_host(fg.cpu()), fg.shape[0]
+        if bits.numel() < (C1 * C1 * R + 63) // 64:
+            raise ValueError(f"seen_bits holds {bits.numel()} words, {C1} x {C1} x {R} bits need more")
+        self._seen_bits, self._zs_classes = bits, C1
 
     # ---- state -----------------------------------------------------------------------------------------------------
     def reset(self, device=None):
         self._reset_acc(device)
         self._per_image = []       # slab columns [B, nk + 2] (recalls, counted, skipped) per update
+        self.zs_acc = None if device is None or self._seen_bits is None else torch.zeros(
+            len(self.ks) + 2, dtype=torch.float64, device=device)
+        self._per_image_zs = []    # zero-shot rows [B, nk + 2] per update
+
+    def _zs_on(self, device):
+        """``zs_acc`` (placed like ``acc``) with the bitset beside it."""
+        self.zs_acc = placed(self.zs_acc, device, len(self.ks) + 2, torch.float64)
+        if self._seen_bits.device != device:
+            self._seen_bits = self._seen_bits.to(device)
+        return self.zs_acc
 
     def merge(self, other):
         """Add another evaluator's accumulators (same ks / num_rel_labels) into this one."""
@@ -73,6 +114,9 @@ class SceneGraphRecall(FlatAccumulator):
         if other.acc is not None:
             self._acc_on(other.acc.device).add_(other.acc)
         self._per_image += other._per_image
+        if other.zs_acc is not None:
+            self.zs_acc = placed(self.zs_acc, other.zs_acc.device, len(self.ks) + 2, torch.float64).add_(other.zs_acc)
+        self._per_image_zs += other._per_image_zs
         return self
 
     def all_reduce(self, group=None):
@@ -84,6 +128,8 @@ class SceneGraphRecall(FlatAccumulator):
         if self.acc is None:
             self._acc_on(backend_device(group))
         dist.all_reduce(self.acc, op=dist.ReduceOp.SUM, group=group)
+        if self._seen_bits is not None:   # every rank was constructed alike
+            dist.all_reduce(self._zs_on(self.acc.device), op=dist.ReduceOp.SUM, group=group)
         return self
 
     # ---- update ----------------------------------------------------------------------------------------------------
@@ -131,9 +177,28 @@ class SceneGraphRecall(FlatAccumulator):
             row[self._fbase + q] = 1.0
         return row
 
+    def _zero_shot_row(self, fr, g, K):
+        """One zero-shot row (float64 [nk + 2]) from the first ranks of an image, as sgg_zero_shot writes it."""
+        nk, R, C1 = len(self.ks), self.num_rel, self._zs_classes
+        row = torch.zeros(nk + 2, dtype=torch.float64)
+        rels = g["gt_relations"]
+        if rels.shape[0] == 0:
+            return row
+        cs, co = g["gt_classes"][rels[:, 0]], g["gt_classes"][rels[:, 1]]
+        ok = (cs >= 0) & (cs < C1) & (co >= 0) & (co < C1)
+        bit = ((cs * C1 + co) * R + rels[:, 2]).clamp(0, C1 * C1 * R - 1)
+        zs = ok & (((self._seen_bits[bit >> 6] >> (bit & 63)) & 1) == 0)
+        n = int(zs.sum())
+        if n:
+            row[:nk] = torch.tensor([float(int((zs & (fr < min(k, K))).sum())) / float(n) for k in self.ks],
+                                    dtype=torch.float64)
+            row[nk], row[nk + 1] = 1.0, float(n)
+        return row
+
     def _update_host(self, candidates, gts):
         acc = self._acc_on(torch.device("cpu"))
-        rows = []
+        zs_acc = None if self._seen_bits is None else self._zs_on(torch.device("cpu"))
+        rows, zs_rows = [], []
         for c, g in zip(candidates, gts):
             inds = c["pred_rel_inds"].long()
             if self.multiple_preds:
@@ -143,10 +208,16 @@ class SceneGraphRecall(FlatAccumulator):
             fr = first_ranks_host(rels, c["pred_boxes"].float(), c["pred_classes"].long(), g["gt_relations"],
                                   g["gt_boxes"], g["gt_classes"], self.iou_thresh)
             rows.append(self._image_row(fr, g["gt_relations"], rels.shape[0]))
+            if zs_acc is not None:
+                zs_rows.append(self._zero_shot_row(fr, g, rels.shape[0]))
         for r in rows:          # image order, like sgg_fold
             acc.add_(r)
+        for r in zs_rows:
+            zs_acc.add_(r)
         if self.keep_per_image:
             self._per_image.append(torch.stack(rows)[:, :len(self.ks) + 2])
+            if zs_rows:
+                self._per_image_zs.append(torch.stack(zs_rows))
 
     def _update_device(self, candidates, gts, device):
         acc = self._acc_on(device)
@@ -168,6 +239,13 @@ class SceneGraphRecall(FlatAccumulator):
         slab = self._launch(acc)
         if self.keep_per_image:
             self._per_image.append(slab[:, :len(self.ks) + 2].clone())
+        if self._seen_bits is not None:   # right behind the matching pass, on its stream: reads the first ranks it left
+            zs_acc = self._zs_on(device)
+            with torch.cuda.device(device):
+                zs_slab = sgg_zero_shot(self.last_first_rank, self._staged[4], B, inds.shape[1], self._zs_classes,
+                                        self.num_rel, self._seen_bits, self.ks, zs_acc)
+            if self.keep_per_image:
+                self._per_image_zs.append(zs_slab)
 
     def _launch(self, acc):
         """egtr_sgg_eval_f32 on the inputs the last device update staged (``_staged``); returns the slab."""
@@ -228,6 +306,37 @@ class SceneGraphRecall(FlatAccumulator):
                 s += v[f"R@{k}"]
             out[f"mR@{k}"] = s / self.num_rel
         return out
+
+    def _host_zs(self):
+        if self._seen_bits is None:
+            raise RuntimeError("construct the evaluator with train_counts=...")
+        return torch.zeros(len(self.ks) + 2, dtype=torch.float64) if self.zs_acc is None else self.zs_acc.cpu()
+
+    def zero_shot(self):
+        """{"zR@k": mean per-image zero-shot recall} over the images that have a zero-shot GT triplet; NaN without one."""
+        a = self._host_zs().tolist()
+        nk = len(self.ks)
+        return {f"zR@{k}": self._mean(a[j], a[nk]) for j, k in enumerate(self.ks)}
+
+    @property
+    def n_zero_shot_images(self):
+        return int(self._host_zs()[len(self.ks)])
+
+    @property
+    def n_zero_shot_triplets(self):
+        return int(self._host_zs()[len(self.ks) + 1])
+
+    def per_image_zero_shot(self):
+        """Per-image zero-shot recalls [n, len(ks)] (float64, host) of the images that have a zero-shot GT triplet, in
+        update order."""
+        if not self.keep_per_image:
+            raise RuntimeError("construct the evaluator with keep_per_image=True")
+        self._host_zs()
+        nk = len(self.ks)
+        if not self._per_image_zs:
+            return torch.zeros(0, nk, dtype=torch.float64)
+        rows = torch.cat([r.cpu() for r in self._per_image_zs])
+        return rows[rows[:, nk] == 1][:, :nk]
 
     def per_image(self):
         """Per-image recalls [n_images, len(ks)] (float64, host) of the images that were not skipped, in update order."""

@@ -517,6 +517,30 @@ int egtr_sgg_eval_f32(egtr_stream_t stream, const int64_t* cand, int cand_cols, 
                       long long num_gt_boxes, const int* ks, int num_k, double iou_thresh, int* first_rank, double* slab,
                       double* acc);
 
+/* Training-set relation statistics, the reference's fg_matrix (data/visual_genome.py:84-118, data/open_image.py:161-185):
+ * counts [num_classes, num_classes, num_rel] int64 is INCREMENTED by one at (class of s, class of o, p) for every row of
+ * rels [num_rels, 3] (s, o, p; s / o index the image's own objects), duplicates included.  The batch is packed ragged as
+ * for egtr_sgg_eval_f32: rel_offsets / box_offsets [batch + 1], classes [num_boxes].  One 64-bit integer atomic add per
+ * row (order-free: deterministic).  A row whose s / o is outside its image's objects, whose class is outside
+ * [0, num_classes) or whose predicate is outside [0, num_rel) is not counted and sets bit 0 of *status (one int32 in
+ * device memory, never cleared here).
+ * egtr_rel_seen_bits_i64: bits [ceil(num_counts / 64)] words, bit (i & 63) of word i >> 6 set iff counts[i] > 0 (row-major
+ * (class s, class o, p)); fully overwritten. */
+int egtr_rel_stats_i64(egtr_stream_t stream, const int64_t* rels, const int64_t* rel_offsets, long long num_rels,
+                       const int64_t* classes, const int64_t* box_offsets, long long num_boxes, int batch,
+                       int num_classes, int num_rel, int64_t* counts, int* status);
+int egtr_rel_seen_bits_i64(egtr_stream_t stream, const int64_t* counts, long long num_counts, int64_t* bits);
+/* Zero-shot Recall@K: per image, the recall over the GT triplets whose (subject class, object class, predicate) bit is
+ * clear in seen_bits (as egtr_rel_seen_bits_i64 writes them for counts [num_classes, num_classes, num_rel]), from the
+ * first_rank [num_gt_rels] buffer egtr_sgg_eval_f32 wrote for the same staged GT and num_cand.  slab [batch, num_k + 2]:
+ * #{zero-shot t : first_rank[t] < min(ks[j], num_cand)} / #{zero-shot t} as double / double (0 without one), 1 = the
+ * image has a zero-shot triplet, their number; acc [num_k + 2] (may be NULL) is then incremented by the rows in image
+ * order.  ks is HOST memory.  GT rows with an index, class or predicate out of range are not zero-shot. */
+int egtr_sgg_zero_shot_f64(egtr_stream_t stream, const int* first_rank, const int64_t* gt_rels,
+                           const int64_t* rel_offsets, long long num_gt_rels, const int64_t* gt_classes,
+                           const int64_t* box_offsets, long long num_gt_boxes, int batch, int num_cand, int num_classes,
+                           int num_rel, const int64_t* seen_bits, const int* ks, int num_k, double* slab, double* acc);
+
 /* Open Images relation metrics of the reference's OI evaluator (lib/evaluation/oi_eval.py eval_rel_results,
  * lib/evaluation/ap_eval_rel.py; inputs as train_egtr.py:154-174 builds them), in three steps.  Layouts in oi_eval.hip.
  *
