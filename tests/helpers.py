@@ -232,19 +232,21 @@ def rel_fro(y, ref):
     return float((y.double() - ref).norm() / ref.norm())
 
 
-def split_error_model(op, a, w, post=None, lost=SMALL_TERMS):
+def split_error_model(op, a, w, post=None, lost=SMALL_TERMS, a_split=None, w_split=None):
     """(ref, E_model, E_loss) of one case: the fp64 result of the intact fp32 operands, the relative Frobenius error of the
     six-term sum against it, and the smallest such error among the five-term sums that leave out one of ``lost`` in turn.
-    ``post``: a map applied to every restatement before the errors are taken (the stem's ReLU + max-pool)."""
+    ``post``: a map applied to every restatement before the errors are taken (the stem's ReLU + max-pool).  ``a_split`` /
+    ``w_split``: the split of each operand; the default is what the forward kernels do, activation = truncation, weight = nearest
+    even (the weight gradient splits both of its operands by truncation)."""
     post = post or (lambda t: t)
-    ap, wp, cache = split3_trunc(a), split3_rne(w), {}
+    ap, wp, cache = (a_split or split3_trunc)(a), (w_split or split3_rne)(w), {}
     ref = post(op(a.double(), w.double()))
     e_model = rel_fro(post(term_sum(op, ap, wp, SIX_TERMS, cache)), ref)
     e_loss = min(rel_fro(post(term_sum(op, ap, wp, [t for t in SIX_TERMS if t != out], cache)), ref) for out in lost)
     return ref, e_model, e_loss
 
 
-def paired_operands(family, a_shape, w_shape, gen):
+def paired_operands(family, a_shape, w_shape, gen, nonneg=False):
     """(a, w) fp32 CPU tensors of the given shapes, the LAST dimension of both being the kernels' innermost K index (the
     channel), whose leading products cancel in adjacent k pairs (2i, 2i + 1), so that the result is carried by the small pieces
     alone.  w ~ N(0, 1 / fan-in).
@@ -262,16 +264,48 @@ def paired_operands(family, a_shape, w_shape, gen):
         w[..., 1::2] = -w[..., 0::2]
         low = torch.randint(0, 1 << 16, a[..., 0::2].shape, generator=gen)
         a[..., 1::2] = _bits_f32((_f32_bits(a[..., 0::2]) & 0xffff0000) | low)
+        if nonneg:
+            a = a.abs()
         assert torch.equal(split3_trunc(a[..., 1::2].contiguous())[0], split3_trunc(a[..., 0::2].contiguous())[0])
     elif family == "wgt":
-        a[..., 1::2] = -a[..., 0::2]
+        if nonneg:
+            a = a.abs()
+        a[..., 1::2] = a[..., 0::2] if nonneg else -a[..., 0::2]
         hi = split3_rne(w[..., 0::2].contiguous())[0]
         low = torch.randint(-0x7fff, 0x8000, hi.shape, generator=gen)
         w[..., 1::2] = _bits_f32(_f32_bits(hi) + low)             # bit arithmetic: fp32 steps, also across a binade
         assert torch.equal(split3_rne(w[..., 1::2].contiguous())[0], hi)
+        if nonneg:
+            w[..., 1::2] = -w[..., 1::2]
     else:
         raise ValueError(family)
     return a, w
+
+
+def paired_operands_trunc(family, a_shape, w_shape, gen):
+    """``paired_operands`` for a product whose operands are BOTH split by truncation (the weight gradient g^T x: ``a`` = g,
+    ``w`` = x, the last dimension of both the reduction index m).  "act": as above, a shares the leading piece within a pair
+    and w changes sign.  "wgt": the same construction with the roles exchanged -- w[..., 2i+1] has the leading piece BY
+    TRUNCATION of w[..., 2i] and a[..., 2i+1] = -a[..., 2i].  RESOLVED_TERMS holds for both as it stands."""
+    if family == "act":
+        return paired_operands("act", a_shape, w_shape, gen)
+    if family != "wgt":
+        raise ValueError(family)
+    w, a = paired_operands("act", w_shape, a_shape, gen)
+    return a, w
+
+
+def add_on_load(a):
+    """(x, pos) with fl32(x + pos) == a bit for bit: x = a_hi + a_mid (16 significant bits: exact in fp32), pos = a - x, which
+    is exact and equals a_lo wherever three bf16 hold a (|a| >= 2^-110; below that pos also keeps the bits a_lo cannot), the
+    pieces by truncation.  For the entries that add position rows to an operand while loading it."""
+    hi, mid, lo = split3_trunc(a)
+    x = hi + mid
+    pos = a - x
+    full = a.abs() >= 2.0 ** -110
+    assert torch.equal(x.double(), hi.double() + mid.double()) and torch.equal(pos.double(), a.double() - x.double())
+    assert torch.equal(_f32_bits(pos[full]), _f32_bits(lo[full])) and torch.equal(_f32_bits(x + pos), _f32_bits(a + 0.0))
+    return x, pos
 
 
 def xs_decode(buf, rows, K):

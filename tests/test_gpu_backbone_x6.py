@@ -54,6 +54,7 @@ class Case:
     the kernel applies behind it; runs(a, w): [(label, kernel output in op's layout)]; K: products per output the kernel walks."""
     post = staticmethod(lambda t: t)
     post_bound = staticmethod(lambda t: t)
+    a_split = w_split = None      # helpers.split_error_model's defaults: activation = truncation, weight = nearest even
 
     def fp32(self, a, w):
         return self.post(self.op(a, w))
@@ -164,16 +165,21 @@ def _stem_case(family, size):
 
 
 # ---- item 2: paired operands, bar from the fp64 restatement ---------------------------------------------------------------------
+def _model(case, family):
+    ref, e_model, e_loss = H.split_error_model(case.op, case.a, case.w, post=case.post, lost=H.RESOLVED_TERMS[family],
+                                               a_split=case.a_split, w_split=case.w_split)
+    return ref, e_model, e_loss, (e_model * e_loss) ** 0.5
+
+
 def _check_six_terms(case, family):
-    ref, e_model, e_loss = H.split_error_model(case.op, case.a, case.w, post=case.post, lost=H.RESOLVED_TERMS[family])
-    bar = (e_model * e_loss) ** 0.5
+    ref, e_model, e_loss, bar = _model(case, family)
     e32 = H.rel_fro(case.fp32(case.a, case.w), ref)
     print(f"\n[six-terms {family}] {case.name}: E_model {e_model:.3g} E_loss {e_loss:.3g} bar {bar:.3g} fp32 route {e32:.3g}")
     assert e_loss >= 50 * e_model, "input health: a lost term must stand out of the six-term model"
     assert e32 <= bar, "input health: the plain fp32 route must itself meet the bar"
     worst = 0.0
     for label, y in case.runs(case.a, case.w):
-        assert y.shape == ref.shape
+        assert y.shape == ref.shape, (y.shape, ref.shape)
         err = H.rel_fro(y, ref)
         print(f"    {label}: err_kernel {err:.3g} = {err / e_model:.2f} x E_model")
         assert err <= bar, (case.name, label, err, bar)
@@ -217,20 +223,19 @@ def test_stem_keeps_all_six_terms(family, size):
 # ---- item 3: the metric resolves ONE term on the real matrix pipe ----------------------------------------------------------------
 def _check_teeth(case, family):
     """Operands with one piece removed, against the fp64 result of the INTACT operands: exactly a lost term.  "wgt": weights
-    w - w_lo (loses w_lo a_hi) and w - w_mid - w_lo (also w_mid a_hi, w_mid a_mid); "act": activations a - a_lo (w_hi a_lo)."""
-    ref, e_model, e_loss = H.split_error_model(case.op, case.a, case.w, post=case.post, lost=H.RESOLVED_TERMS[family])
-    bar = (e_model * e_loss) ** 0.5
+    w - w_lo (loses w_lo a_hi) and, for nearest-even weights, w - w_mid - w_lo (also w_mid a_hi, w_mid a_mid); "act": activations
+    a - a_lo (w_hi a_lo).  A case with split functions of its own (the weight gradient: a is g, w is x) is damaged by those."""
+    ref, e_model, e_loss, bar = _model(case, family)
     assert e_loss >= 50 * e_model
     intact = max(H.rel_fro(y, ref) for _, y in case.runs(case.a, case.w))
     assert intact <= bar
     if family == "wgt":
-        hi, mid, lo = H.split3_rne(case.w)
-        damaged = [("w - w_lo", case.a, hi + mid), ("w - w_mid - w_lo", case.a, hi)]
-        assert torch.equal((hi + mid).double(), hi.double() + mid.double())           # the removal is exact in fp32
+        hi, mid, lo = (case.w_split or H.split3_rne)(case.w)
+        damaged = [("w - w_lo", case.a, hi + mid)] + ([("w - w_mid - w_lo", case.a, hi)] if case.w_split is None else [])
     else:
-        hi, mid, lo = H.split3_trunc(case.a)
+        hi, mid, lo = (case.a_split or H.split3_trunc)(case.a)
         damaged = [("a - a_lo", hi + mid, case.w)]
-        assert torch.equal((hi + mid).double(), hi.double() + mid.double())
+    assert torch.equal((hi + mid).double(), hi.double() + mid.double())               # the removal is exact in fp32
     assert float(lo.abs().max()) > 0
     for what, a, w in damaged:
         for label, y in case.runs(a, w):

@@ -126,3 +126,97 @@ def test_paired_operands_separate_a_lost_term_from_accumulation_noise(family, K,
     assert e_chain <= bar and e_mm <= bar
     # the leading products cancel: the result is small against sum |a| |w|
     assert float(ref.abs().max()) < 2.0 ** -6 * float((a.double().abs() @ w.double().abs().t()).max())
+
+
+# ---- the extensions tests/test_gpu_token_x6.py needs ------------------------------------------------------------------------------
+def _health(op, a, w, family, post=None, **splits):
+    ref, e_model, e_loss = H.split_error_model(op, a, w, post=post, lost=H.RESOLVED_TERMS[family], **splits)
+    (blind,) = [t for t in H.SMALL_TERMS if t not in H.RESOLVED_TERMS[family]]
+    ap = splits.get("a_split", H.split3_trunc)(a)
+    wp = splits.get("w_split", H.split3_rne)(w)
+    assert float(H.term_sum(op, ap, wp, [blind]).abs().max()) == 0.0           # the third small term: exactly zero
+    return ref, e_model, e_loss
+
+
+@pytest.mark.parametrize("family", ["act", "wgt"])
+@pytest.mark.parametrize("K", [32, 256, 1024])
+def test_non_negative_paired_operands_resolve_the_same_terms(family, K, capsys):
+    """The non-negative variant (activations behind a ReLU): a >= 0 everywhere, relu(a) == a, and the same separation
+    E_loss >= 50 E_model with the same third small term exactly zero as the signed families; the fp32 product under the bar."""
+    op = lambda x, y: x @ y.t()
+    gen = torch.Generator().manual_seed(7 * K + len(family))
+    a, w = H.paired_operands(family, (200, K), (64, K), gen, nonneg=True)
+    assert bool((a >= 0).all()) and torch.equal(torch.relu(a), a)
+    if family == "wgt":
+        assert torch.equal(a[:, 1::2], a[:, 0::2])
+        assert torch.equal(H.split3_rne(w[:, 1::2].contiguous())[0], -H.split3_rne(w[:, 0::2].contiguous())[0])
+    ref, e_model, e_loss = _health(op, a, w, family)
+    bar = (e_model * e_loss) ** 0.5
+    with capsys.disabled():
+        print(f"\n[paired nonneg {family} K={K}] E_model {e_model:.3g} E_loss {e_loss:.3g} bar {bar:.3g}")
+    assert e_loss >= 50 * e_model
+    assert H.rel_fro(a @ w.t(), ref) <= bar
+    assert float(ref.abs().max()) < 2.0 ** -6 * float((a.double() @ w.double().abs().t()).max())
+
+
+@pytest.mark.parametrize("family", ["act", "wgt"])
+@pytest.mark.parametrize("M", [34, 778, 4100])
+def test_truncation_truncation_family_of_the_weight_gradient(family, M, capsys):
+    """g^T x with both operands split by truncation, pairs along the reduction index m (adjacent rows): the split function per
+    operand of ``split_error_model``, E_loss >= 50 E_model, the third small term exactly zero, both families."""
+    gen = torch.Generator().manual_seed(M + len(family))
+    gt, xt = H.paired_operands_trunc(family, (128, M), (128, M), gen)           # [N, M], [K, M]
+    g, x = gt.t().contiguous(), xt.t().contiguous()
+    op = lambda gg, xx: gg.t() @ xx
+    both = dict(a_split=H.split3_trunc, w_split=H.split3_trunc)
+    ref, e_model, e_loss = _health(op, g, x, family, **both)
+    shared = x if family == "wgt" else g
+    assert torch.equal(H.split3_trunc(shared[1::2].contiguous())[0], H.split3_trunc(shared[0::2].contiguous())[0])
+    bar = (e_model * e_loss) ** 0.5
+    with capsys.disabled():
+        print(f"\n[paired trunc {family} M={M}] E_model {e_model:.3g} E_loss {e_loss:.3g} bar {bar:.3g}")
+    assert e_loss >= 50 * e_model
+    assert H.rel_fro(g.t() @ x, ref) <= bar
+    # the default splits are still activation = truncation, weight = nearest even
+    d = H.split_error_model(op, g, x, lost=H.RESOLVED_TERMS[family])
+    e = H.split_error_model(op, g, x, lost=H.RESOLVED_TERMS[family], a_split=H.split3_trunc, w_split=H.split3_rne)
+    assert d[1:] == e[1:]
+
+
+def test_add_on_load_decomposition_is_exact():
+    """x = a_hi + a_mid, pos = a_lo: the fp32 sum x + pos is a bit for bit, for every value three bf16 can hold; below 2^-110
+    (a paired partner of an activation that is exactly zero is an fp32 denormal) pos = a - x keeps the sum exact as well."""
+    a = _wide_values()
+    x, pos = H.add_on_load(a)
+    assert torch.equal(H._f32_bits(x + pos), H._f32_bits(a + 0.0))
+    full = a.abs() >= 2.0 ** -110
+    assert float(pos[full].abs().max()) > 0 and _is_bf16(pos[full]) and torch.equal(pos[full], H.split3_trunc(a)[2][full])
+    g = torch.Generator().manual_seed(4)
+    a, _ = H.paired_operands("act", (37, 64), (8, 64), g)
+    x, pos = H.add_on_load(a)
+    assert torch.equal(H._f32_bits(x + pos), H._f32_bits(a))
+
+
+def test_selector_and_identity_weights_return_the_activation_exactly():
+    """A 0 / 1 weight is (1, 0, 0) in pieces, so its six-term product is a_hi + a_mid + a_lo (and zeros) added in fp32 in SOME
+    order.  Every partial sum of the pieces of one fp32 number is representable -- hi + mid is the leading 16 bits, hi + lo and
+    mid + lo fit in 24 bits between the first bit of the larger and the last bit of a -- so every order returns a exactly."""
+    import itertools
+    a = _wide_values()
+    a = a[(a.abs() >= 2.0 ** -110) & (a.abs() < 2.0 ** 120)]
+    one = torch.ones(1)
+    assert [float(p) for p in H.split3_rne(one)] == [1.0, 0.0, 0.0]
+    pieces = H.split3_trunc(a)
+    for order in itertools.permutations(range(3)):
+        acc = torch.zeros_like(a)
+        for i in order:
+            acc = acc + pieces[i] * one                                          # the product with 1 is exact
+            acc = acc + 0.0 * pieces[i]                                          # the terms with the weight's zero pieces
+        assert torch.equal(H._f32_bits(acc), H._f32_bits(a + 0.0)), order
+    # as a matrix: a selector of a window of the hidden layer after the ReLU
+    g = torch.Generator().manual_seed(9)
+    h, _ = H.paired_operands("wgt", (37, 64), (8, 64), g, nonneg=True)
+    sel = torch.zeros(16, 64)
+    sel[torch.arange(16), 32 + torch.arange(16)] = 1.0
+    six = H.term_sum(lambda x, y: x @ y.t(), H.split3_trunc(h), H.split3_rne(sel), H.SIX_TERMS)
+    assert torch.equal(six, h[:, 32:48].double())
