@@ -71,6 +71,10 @@ SIGNATURES = {
                           _P, _I, ctypes.c_double, _P, _P, _P],
     "egtr_sgg_zero_shot_f64": [_P, _P, _P, _P, ctypes.c_longlong, _P, _P, ctypes.c_longlong, _I, _I, _I, _I, _P, _P, _I, _P,
                                _P],
+    "egtr_sgg_eval_phrdet_f32": [_P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P, ctypes.c_longlong, _P, _P, _P,
+                                 ctypes.c_longlong, _P, _I, ctypes.c_double, _P, _P, _P],
+    "egtr_sgg_eval_preddet_f32": [_P, _P, _P, _I, _I, _I, _P, _P, ctypes.c_longlong, _P, ctypes.c_longlong, _P, _I, _P, _P,
+                                  _P, _P, _P],
     "egtr_rel_stats_i64": [_P, _P, _P, ctypes.c_longlong, _P, _P, ctypes.c_longlong, _I, _I, _I, _P, _P],
     "egtr_rel_seen_bits_i64": [_P, _P, ctypes.c_longlong, _P],
     "egtr_oi_eval_width": [_I, _I],

@@ -3,6 +3,8 @@ host implementation of the same semantics (the module docstrings state them):
   * ``sgg``   scene-graph Recall@K / mean Recall@K (``SceneGraphRecall``; csrc/sgg_eval.hip);
   * ``oi``    Open Images relation mAP / recall / score (``OpenImagesRelationMetrics``; csrc/oi_eval.hip);
   * ``coco``  COCO box-detection AP / AR (``CocoDetectionMetrics``; csrc/coco_eval.hip);
+  * ``vrd``   phrase- and predicate-detection recall (``PhraseDetectionRecall``, ``PredicateDetectionRecall``;
+    csrc/vrd_eval.hip);
   * ``_common``  what they share: the GT entry, the first-rank matching, staging, accumulator, checks, record exchange.
 ``evaluate`` below drives a model over batches and scores whichever of them are enabled.
 """
@@ -18,11 +20,14 @@ from .coco import (_COCO_MAX_CLS, _COCO_MAX_DET, _COCO_MAX_GT, _EPS, COCO_AREA_R
 from .oi import (_OI_MAX_GT, _OI_MAX_PAIRS, _OI_MAX_PRDK, _OI_MAX_TOPK, OpenImagesRelationMetrics, _union,  # noqa: F401
                  bbox_iou_f32, oi_ap_host, oi_select_host, oi_tp_host)
 from .sgg import SceneGraphRecall, _check_candidate  # noqa: F401
+from .vrd import (PhraseDetectionRecall, PredicateDetectionRecall, phrase_first_ranks_host, preddet_ranks_host,  # noqa: F401
+                  score_keys_host)
 
 
 @torch.no_grad()
 def evaluate(model, batches, num_labels, num_rel_labels, single=True, multiple=False, max_topk=100, graphed=True,
-             forward=None, oi=False, coco=False, feature_extractor=None, train_counts=None):
+             forward=None, oi=False, coco=False, feature_extractor=None, train_counts=None, phrdet=False, preddet=False,
+             matcher=None):
     """The Visual Genome path of the reference's ``evaluate`` (evaluate_egtr.py:40-127): run the model over ``batches``
     (the reference's collate_fn format: pixel_values, pixel_mask, labels), build the candidates on the device
     (``runtime.triplet_candidates``) and score them.  Returns the reference's ``metric_dict`` keys: ``R@k`` / ``mR@k``
@@ -34,16 +39,24 @@ def evaluate(model, batches, num_labels, num_rel_labels, single=True, multiple=F
     ``coco``: also score the boxes (``feature_extractor.post_process`` with the targets' orig_size, default a
     ``DeformableDetrFeatureExtractor``, into ``CocoDetectionMetrics(num_labels)``) and add the reference's "AP50".
     ``train_counts``: a ``RelationStatistics`` / ``fg_matrix`` of the training set (``SceneGraphRecall(train_counts=...)``);
-    adds the zero-shot recalls ``zR@k`` (multiple) and ``(single)zR@k``."""
-    from ..runtime import GraphedForward, triplet_candidates
-    if not (single or multiple or oi or coco):
-        raise ValueError("enable at least one of single / multiple / oi / coco")
+    adds the zero-shot recalls ``zR@k`` (multiple) and ``(single)zR@k``.
+    ``phrdet``: also score phrase detection (``PhraseDetectionRecall`` on the "multiple" candidates) and add
+    ``phrdet_R@k`` / ``phrdet_mR@k`` (and ``phrdet_zR@k`` with ``train_counts``).  ``preddet``: also score predicate
+    detection (``PredicateDetectionRecall`` on ``runtime.matched_pair_candidates``: the GT objects matched to queries by
+    ``matcher``, default the model's own Hungarian matcher) and add ``preddet_R@k`` / ``preddet_mR@k``."""
+    from ..runtime import GraphedForward, matched_pair_candidates, triplet_candidates
+    if not (single or multiple or oi or coco or phrdet or preddet):
+        raise ValueError("enable at least one of single / multiple / oi / coco / phrdet / preddet")
     model.eval()
     device = next(model.parameters()).device
     ev_s = SceneGraphRecall(num_rel_labels, multiple_preds=False, train_counts=train_counts) if single else None
     ev_m = SceneGraphRecall(num_rel_labels, multiple_preds=True, train_counts=train_counts) if multiple else None
     ev_oi = OpenImagesRelationMetrics(num_rel_labels) if oi else None
     ev_coco = CocoDetectionMetrics(num_labels) if coco else None
+    ev_phr = PhraseDetectionRecall(num_rel_labels, train_counts=train_counts) if phrdet else None
+    ev_prd = PredicateDetectionRecall(num_rel_labels) if preddet else None
+    if preddet and matcher is None:
+        matcher = model._matcher()
     if coco and feature_extractor is None:
         from ..feature_extraction import DeformableDetrFeatureExtractor
         feature_extractor = DeformableDetrFeatureExtractor()
@@ -64,8 +77,14 @@ def evaluate(model, batches, num_labels, num_rel_labels, single=True, multiple=F
             sizes = torch.stack([torch.as_tensor(t["orig_size"]).cpu() for t in targets])
             if device.type == "cuda":   # a pageable host -> device copy would wait for the stream
                 sizes = sizes.pin_memory().to(device, non_blocking=True)
-            if ev_m is not None:
-                ev_m.update(triplet_candidates(outputs, num_labels, sizes, max_topk, mode="multiple"), targets)
+            if ev_m is not None or ev_phr is not None:
+                cands_m = triplet_candidates(outputs, num_labels, sizes, max_topk, mode="multiple")
+                if ev_m is not None:
+                    ev_m.update(cands_m, targets)
+                if ev_phr is not None:
+                    ev_phr.update(cands_m, targets)
+            if ev_prd is not None:
+                ev_prd.update(matched_pair_candidates(outputs, targets, matcher, num_labels), targets)
             if ev_s is not None:
                 ev_s.update(triplet_candidates(outputs, num_labels, sizes, max_topk, mode="single"), targets)
             if ev_oi is not None:
@@ -91,4 +110,8 @@ def evaluate(model, batches, num_labels, num_rel_labels, single=True, multiple=F
         metrics.update({(f"(oi){k}" if k.startswith("R@") else k): v for k, v in ev_oi.compute().items()})
     if ev_coco is not None:
         metrics["AP50"] = ev_coco.compute()["AP50"]
+    if ev_phr is not None:
+        metrics.update({f"phrdet_{k}": v for k, v in ev_phr.compute().items()})
+    if ev_prd is not None:
+        metrics.update({f"preddet_{k}": v for k, v in ev_prd.compute().items()})
     return metrics

@@ -195,6 +195,8 @@ class SceneGraphRecall(FlatAccumulator):
             row[nk], row[nk + 1] = 1.0, float(n)
         return row
 
+    _first_ranks = staticmethod(first_ranks_host)     # the host matching; a subclass with another box test replaces it
+
     def _update_host(self, candidates, gts):
         acc = self._acc_on(torch.device("cpu"))
         zs_acc = None if self._seen_bits is None else self._zs_on(torch.device("cpu"))
@@ -205,8 +207,8 @@ class SceneGraphRecall(FlatAccumulator):
                 rels = inds[:, :3]
             else:
                 rels = torch.cat([inds[:, :2], numpy_argmax(c["rel_scores"].float())[:, None]], 1)
-            fr = first_ranks_host(rels, c["pred_boxes"].float(), c["pred_classes"].long(), g["gt_relations"],
-                                  g["gt_boxes"], g["gt_classes"], self.iou_thresh)
+            fr = self._first_ranks(rels, c["pred_boxes"].float(), c["pred_classes"].long(), g["gt_relations"],
+                                   g["gt_boxes"], g["gt_classes"], self.iou_thresh)
             rows.append(self._image_row(fr, g["gt_relations"], rels.shape[0]))
             if zs_acc is not None:
                 zs_rows.append(self._zero_shot_row(fr, g, rels.shape[0]))

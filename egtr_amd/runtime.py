@@ -594,3 +594,29 @@ def triplet_candidates(outputs, num_labels, orig_sizes, max_topk=100, mode="mult
     rel_scores = rel.reshape(B, -1).gather(1, flat)
     return [dict(c, pred_rel_inds=torch.stack([s_idx[b], o_idx[b], p_idx[b]], -1), rel_scores=rel_scores[b],
                  triplet_scores=top[b]) for b, c in enumerate(common)]
+
+
+@torch.no_grad()
+def matched_pair_candidates(outputs, targets, matcher, num_labels):
+    """The predicate-detection inputs (``evaluation.PredicateDetectionRecall``) of a model's outputs: "how good are the
+    predicates once the objects are found".  Per image, ``matcher`` (a ``DeformableDetrHungarianMatcher``, run on the first
+    ``num_labels`` logits like every evaluator input) maps GT objects to queries; ``pred_rel_inds`` [k, 2] is every ordered
+    pair (s, o), s != o, of matched GT OBJECT indices in row-major order and ``rel_scores`` [k, R] the rows
+    ``clamp(pred_rel) * clamp(pred_connectivity)`` at (query of s, query of o).  With at least as many queries as GT objects
+    every GT object is matched and k = G (G - 1).  Returns a list of dicts of tensors on the outputs' device; nothing waits
+    for the device (the matched counts are shapes)."""
+    rel = torch.clamp(outputs["pred_rel"], 0.0, 1.0)
+    if "pred_connectivity" in outputs and outputs["pred_connectivity"] is not None:
+        rel = rel * torch.clamp(outputs["pred_connectivity"], 0.0, 1.0)
+    device = rel.device
+    matched = matcher({"logits": outputs["logits"][..., :num_labels], "pred_boxes": outputs["pred_boxes"]}, targets)[0]
+    out = []
+    for b, (pred_idx, tgt_idx) in enumerate(matched):
+        n = pred_idx.shape[0]
+        k = torch.arange(n * max(n - 1, 0), device=device)          # static shape: nothing waits for the device
+        s, o = k // max(n - 1, 1), k % max(n - 1, 1)
+        o = o + (o >= s)                                            # row-major over (s, o), the diagonal left out
+        order = torch.argsort(tgt_idx.to(device))                   # matched entries in GT-object order
+        gt_of, q_of = tgt_idx.to(device)[order], pred_idx.to(device)[order]
+        out.append({"pred_rel_inds": torch.stack([gt_of[s], gt_of[o]], -1), "rel_scores": rel[b, q_of[s], q_of[o]]})
+    return out

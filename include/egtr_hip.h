@@ -541,6 +541,37 @@ int egtr_sgg_zero_shot_f64(egtr_stream_t stream, const int* first_rank, const in
                            const int64_t* box_offsets, long long num_gt_boxes, int batch, int num_cand, int num_classes,
                            int num_rel, const int64_t* seen_bits, const int* ks, int num_k, double* slab, double* acc);
 
+/* The two VRD protocols of the reference's evaluator (lib/evaluation/sg_eval.py vrd_modes; vrd_eval.hip).  Slab rows,
+ * width (egtr_sgg_eval_width), fold into acc and the packed ragged ground truth are those of egtr_sgg_eval_f32.
+ *
+ * egtr_sgg_eval_phrdet_f32 (phrase detection): the arguments of egtr_sgg_eval_f32, with cand_cols == 3 (rel_scores is not
+ * read).  A GT triplet matches a candidate when both classes and the predicate agree and the bbox.pyx IoU (float64) of the
+ * two UNION boxes -- (min x1, min y1, max x2, max y2) of subject and object, for the GT and for the candidate -- is
+ * >= iou_thresh.  first_rank as for egtr_sgg_eval_f32, so egtr_sgg_zero_shot_f64 reads it unchanged.
+ *
+ * egtr_sgg_eval_preddet_f32 (predicate detection, sg_eval.py:111-132): cand [batch, num_cand, 2] are (s, o) pairs of GT
+ * OBJECT indices, rel_scores [batch, num_cand, num_rel] their predicate scores; no boxes, no classes (box_offsets only
+ * bounds the indices).  For GT row j the chosen candidate row is the first one whose pair equals the GT pair, row 0 if
+ * none does.  The image's list holds the n_gt x num_rel entries (pair of the chosen row of j, p, rel_scores[chosen row
+ * of j][p]) in the order: descending score, NaN last, -0 = +0, ties by ascending flat index j * num_rel + p.  A GT
+ * triplet is recalled at k when one of the first k entries equals its (s, o, p).  The per-predicate recalls of the slab
+ * rank inside the GT rows of that predicate (the reference's per-predicate evaluators get a filtered GT list).  An image
+ * with GT relations and num_cand == 0 counts, with recall 0.  Outputs, each [num_gt_rels] and each may be NULL:
+ * chosen_row; first_rank = the lowest list position of an entry equal to the triplet, INT32_MAX if none;
+ * first_rank_pred = the same inside the rows of the triplet's predicate.  Pairs or GT rows with out-of-range indices
+ * never match.  At most 1024 GT relations per image: an image with more gets NaN recalls (callers check beforehand). */
+int egtr_sgg_eval_phrdet_f32(egtr_stream_t stream, const int64_t* cand, int cand_cols, const float* rel_scores,
+                             const float* pred_boxes, const int64_t* pred_classes, int batch, int num_cand, int num_obj,
+                             int num_rel, const int64_t* gt_rels, const int64_t* rel_offsets, long long num_gt_rels,
+                             const float* gt_boxes, const int64_t* gt_classes, const int64_t* box_offsets,
+                             long long num_gt_boxes, const int* ks, int num_k, double iou_thresh, int* first_rank,
+                             double* slab, double* acc);
+int egtr_sgg_eval_preddet_f32(egtr_stream_t stream, const int64_t* cand, const float* rel_scores, int batch,
+                              int num_cand, int num_rel, const int64_t* gt_rels, const int64_t* rel_offsets,
+                              long long num_gt_rels, const int64_t* box_offsets, long long num_gt_boxes, const int* ks,
+                              int num_k, int* chosen_row, int* first_rank, int* first_rank_pred, double* slab,
+                              double* acc);
+
 /* Open Images relation metrics of the reference's OI evaluator (lib/evaluation/oi_eval.py eval_rel_results,
  * lib/evaluation/ap_eval_rel.py; inputs as train_egtr.py:154-174 builds them), in three steps.  Layouts in oi_eval.hip.
  *
