@@ -75,6 +75,8 @@ SIGNATURES = {
                                  ctypes.c_longlong, _P, _I, ctypes.c_double, _P, _P, _P],
     "egtr_sgg_eval_preddet_f32": [_P, _P, _P, _I, _I, _I, _P, _P, ctypes.c_longlong, _P, ctypes.c_longlong, _P, _I, _P, _P,
                                   _P, _P, _P],
+    "egtr_matched_topk_workspace_bytes": [_I, _I, _I],
+    "egtr_matched_topk_f32": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
     "egtr_rel_stats_i64": [_P, _P, _P, ctypes.c_longlong, _P, _P, ctypes.c_longlong, _I, _I, _I, _P, _P],
     "egtr_rel_seen_bits_i64": [_P, _P, ctypes.c_longlong, _P],
     "egtr_oi_eval_width": [_I, _I],
@@ -166,7 +168,7 @@ _RESTYPES = {"egtr_status_string": ctypes.c_char_p, "egtr_last_hip_error": ctype
              "egtr_linear_split_bf16_wgrad_workspace_floats": ctypes.c_longlong,
              "egtr_dropout_add_layernorm_backward_workspace_floats": ctypes.c_longlong,
              "egtr_xs_bytes": ctypes.c_longlong, "egtr_sgg_eval_width": ctypes.c_longlong,
-             "egtr_oi_eval_width": ctypes.c_longlong, "egtr_oi_select_workspace_bytes": ctypes.c_longlong}
+             "egtr_oi_eval_width": ctypes.c_longlong, "egtr_matched_topk_workspace_bytes": ctypes.c_longlong, "egtr_oi_select_workspace_bytes": ctypes.c_longlong}
 
 _lib = None
 

@@ -29,6 +29,7 @@
 #include <stdint.h>
 
 #include "common.h"
+#include "order_key.h"
 #include "sgg_match.h"
 
 namespace {
@@ -182,14 +183,6 @@ struct PredArgs {
   int K, R, nk, W;
   int ks[kMaxK];
 };
-
-// The order key of a score: a larger key ranks earlier.  NaN is the smallest key (numpy sorts NaN last), -0 = +0.
-__device__ __forceinline__ unsigned score_key(float x) {
-  if (x != x) return 0u;
-  if (x == 0.f) x = 0.f;
-  const unsigned u = __float_as_uint(x);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 
 __global__ __launch_bounds__(kThreads) void preddet_match(const PredArgs a) {
   __shared__ unsigned s_key[kMaxEnt];

@@ -3,6 +3,7 @@ host implementation of the same semantics (the module docstrings state them):
   * ``sgg``   scene-graph Recall@K / mean Recall@K (``SceneGraphRecall``; csrc/sgg_eval.hip);
   * ``oi``    Open Images relation mAP / recall / score (``OpenImagesRelationMetrics``; csrc/oi_eval.hip);
   * ``coco``  COCO box-detection AP / AR (``CocoDetectionMetrics``; csrc/coco_eval.hip);
+  * PredCls / SGCls: ``SceneGraphRecall`` itself, on ``runtime.matched_triplet_candidates`` (csrc/matched_topk.hip);
   * ``vrd``   phrase- and predicate-detection recall (``PhraseDetectionRecall``, ``PredicateDetectionRecall``;
     csrc/vrd_eval.hip);
   * ``_common``  what they share: the GT entry, the first-rank matching, staging, accumulator, checks, record exchange.
@@ -27,7 +28,7 @@ from .vrd import (PhraseDetectionRecall, PredicateDetectionRecall, phrase_first_
 @torch.no_grad()
 def evaluate(model, batches, num_labels, num_rel_labels, single=True, multiple=False, max_topk=100, graphed=True,
              forward=None, oi=False, coco=False, feature_extractor=None, train_counts=None, phrdet=False, preddet=False,
-             matcher=None):
+             matcher=None, predcls=False, sgcls=False):
     """The Visual Genome path of the reference's ``evaluate`` (evaluate_egtr.py:40-127): run the model over ``batches``
     (the reference's collate_fn format: pixel_values, pixel_mask, labels), build the candidates on the device
     (``runtime.triplet_candidates``) and score them.  Returns the reference's ``metric_dict`` keys: ``R@k`` / ``mR@k``
@@ -43,10 +44,18 @@ def evaluate(model, batches, num_labels, num_rel_labels, single=True, multiple=F
     ``phrdet``: also score phrase detection (``PhraseDetectionRecall`` on the "multiple" candidates) and add
     ``phrdet_R@k`` / ``phrdet_mR@k`` (and ``phrdet_zR@k`` with ``train_counts``).  ``preddet``: also score predicate
     detection (``PredicateDetectionRecall`` on ``runtime.matched_pair_candidates``: the GT objects matched to queries by
-    ``matcher``, default the model's own Hungarian matcher) and add ``preddet_R@k`` / ``preddet_mR@k``."""
-    from ..runtime import GraphedForward, matched_pair_candidates, triplet_candidates
+    ``matcher``, default the model's own Hungarian matcher) and add ``preddet_R@k`` / ``preddet_mR@k``.
+    ``predcls`` / ``sgcls``: also score the PredCls / SGCls protocol (``SceneGraphRecall`` on
+    ``runtime.matched_triplet_candidates``: GT boxes, the GT objects matched to queries by ``matcher``).  ``multiple`` and
+    ``single`` select the evaluators as they do for sgdet -- at least one must be on -- and the keys are ``predcls_R@k`` /
+    ``predcls_mR@k`` (``predcls_zR@k`` with ``train_counts``), ``(single)predcls_...`` for the single-predicate
+    evaluator, and the same with ``sgcls_``."""
+    from ..runtime import GraphedForward, matched_pair_candidates, matched_triplet_candidates, triplet_candidates
     if not (single or multiple or oi or coco or phrdet or preddet):
         raise ValueError("enable at least one of single / multiple / oi / coco / phrdet / preddet")
+    protocols = [name for name, on in (("predcls", predcls), ("sgcls", sgcls)) if on]
+    if protocols and not (single or multiple):
+        raise ValueError("predcls / sgcls need at least one of single / multiple")
     model.eval()
     device = next(model.parameters()).device
     ev_s = SceneGraphRecall(num_rel_labels, multiple_preds=False, train_counts=train_counts) if single else None
@@ -55,7 +64,12 @@ def evaluate(model, batches, num_labels, num_rel_labels, single=True, multiple=F
     ev_coco = CocoDetectionMetrics(num_labels) if coco else None
     ev_phr = PhraseDetectionRecall(num_rel_labels, train_counts=train_counts) if phrdet else None
     ev_prd = PredicateDetectionRecall(num_rel_labels) if preddet else None
-    if preddet and matcher is None:
+    # (protocol, candidate mode, key prefix) -> evaluator
+    ev_proto = {(name, mode, prefix): SceneGraphRecall(num_rel_labels, multiple_preds=(mode == "multiple"),
+                                                       train_counts=train_counts)
+                for name in protocols for mode, prefix, on in (("multiple", "", multiple), ("single", "(single)", single))
+                if on}
+    if (preddet or protocols) and matcher is None:
         matcher = model._matcher()
     if coco and feature_extractor is None:
         from ..feature_extraction import DeformableDetrFeatureExtractor
@@ -85,6 +99,9 @@ def evaluate(model, batches, num_labels, num_rel_labels, single=True, multiple=F
                     ev_phr.update(cands_m, targets)
             if ev_prd is not None:
                 ev_prd.update(matched_pair_candidates(outputs, targets, matcher, num_labels), targets)
+            for (name, mode, _), ev in ev_proto.items():
+                ev.update(matched_triplet_candidates(outputs, targets, matcher, num_labels, max_topk, mode=mode,
+                                                     protocol=name), targets)
             if ev_s is not None:
                 ev_s.update(triplet_candidates(outputs, num_labels, sizes, max_topk, mode="single"), targets)
             if ev_oi is not None:
@@ -114,4 +131,9 @@ def evaluate(model, batches, num_labels, num_rel_labels, single=True, multiple=F
         metrics.update({f"phrdet_{k}": v for k, v in ev_phr.compute().items()})
     if ev_prd is not None:
         metrics.update({f"preddet_{k}": v for k, v in ev_prd.compute().items()})
+    for (name, _, prefix), ev in ev_proto.items():
+        res = dict(ev.compute(), **ev.mean_recall())
+        if train_counts is not None:
+            res.update(ev.zero_shot())
+        metrics.update({f"{prefix}{name}_{k}": v for k, v in res.items()})
     return metrics

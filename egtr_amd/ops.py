@@ -26,6 +26,7 @@ from .kernels.elementwise import _DIM_T  # noqa: F401
 from .kernels.heads import *  # noqa: F401,F403
 from .kernels.linear import *  # noqa: F401,F403
 from .kernels.linear import _c16, _host_array, _skinny_bwd, _skinny_fwd, _split3_bf16, _wgrad_ex  # noqa: F401
+from .kernels.protocols import *  # noqa: F401,F403
 from .kernels.statistics import *  # noqa: F401,F403
 from .kernels.vrd import *  # noqa: F401,F403
 from .load_custom import load_hip_kernels

@@ -596,6 +596,23 @@ def triplet_candidates(outputs, num_labels, orig_sizes, max_topk=100, mode="mult
                  triplet_scores=top[b]) for b, c in enumerate(common)]
 
 
+def _matched_queries(outputs, targets, matcher, num_labels):
+    """GT object -> query: ``matcher`` (a ``DeformableDetrHungarianMatcher``) on the first ``num_labels`` logits, like every
+    evaluator input.  One (pred_idx, tgt_idx) pair of index tensors per image."""
+    return matcher({"logits": outputs["logits"][..., :num_labels], "pred_boxes": outputs["pred_boxes"]}, targets)[0]
+
+
+def _matched_query_of(outputs, targets, matcher, num_labels, Gp):
+    """``_matched_queries`` as int32 [B, Gp] on the outputs' device: the query of GT object g, -1 where the object is
+    unmatched or padding.  Index writes only: nothing waits for the device."""
+    device = outputs["logits"].device
+    matched = _matched_queries(outputs, targets, matcher, num_labels)
+    query_of = torch.full((len(matched), Gp), -1, dtype=torch.int32, device=device)
+    for b, (pred_idx, tgt_idx) in enumerate(matched):
+        query_of[b, tgt_idx.to(device).long()] = pred_idx.to(device).int()
+    return query_of
+
+
 @torch.no_grad()
 def matched_pair_candidates(outputs, targets, matcher, num_labels):
     """The predicate-detection inputs (``evaluation.PredicateDetectionRecall``) of a model's outputs: "how good are the
@@ -609,7 +626,7 @@ def matched_pair_candidates(outputs, targets, matcher, num_labels):
     if "pred_connectivity" in outputs and outputs["pred_connectivity"] is not None:
         rel = rel * torch.clamp(outputs["pred_connectivity"], 0.0, 1.0)
     device = rel.device
-    matched = matcher({"logits": outputs["logits"][..., :num_labels], "pred_boxes": outputs["pred_boxes"]}, targets)[0]
+    matched = _matched_queries(outputs, targets, matcher, num_labels)
     out = []
     for b, (pred_idx, tgt_idx) in enumerate(matched):
         n = pred_idx.shape[0]
@@ -620,3 +637,115 @@ def matched_pair_candidates(outputs, targets, matcher, num_labels):
         gt_of, q_of = tgt_idx.to(device)[order], pred_idx.to(device)[order]
         out.append({"pred_rel_inds": torch.stack([gt_of[s], gt_of[o]], -1), "rel_scores": rel[b, q_of[s], q_of[o]]})
     return out
+
+
+def matched_topk_host(pred_rel, pred_conn, query_of, obj_score, K, mode):
+    """The torch twin of ``ops.matched_topk`` (csrc/matched_topk.hip), same arguments, same definition, same outputs, on
+    whatever device the tensors live (it reads ``query_of`` on the host).  Per image the domain is every (s, o, p) --
+    (s, o) with ``mode`` 1 -- of GT-object indices with s != o and both objects matched (``0 <= query_of < N``);
+    ``r = clamp(pred_rel[qs, qo, p]) [* clamp(pred_conn[qs, qo])]``, ``so = obj_score[s] * obj_score[o]``,
+    ``score = r * so`` (mode 0) or ``max_p(r) * so`` (mode 1), each product rounded once in float32.  Order: descending
+    score key (``evaluation.score_keys_host``: NaN last, -0 = +0), ties by ascending (s, o, p) -- a stable sort of the
+    domain in row-major order.  Rows from ``count`` to ``K`` hold index Gp - 1 and score 0."""
+    from .evaluation.vrd import score_keys_host
+    B, N, _, R = pred_rel.shape
+    Gp, K, dev = query_of.shape[1], int(K), pred_rel.device
+    cols = 3 if mode == 0 else 2
+    inds = torch.full((B, K, cols), Gp - 1, dtype=torch.int64, device=dev)
+    rel_scores = torch.zeros((B, K) if mode == 0 else (B, K, R), dtype=torch.float32, device=dev)
+    triplet_scores = torch.zeros(B, K, dtype=torch.float32, device=dev)
+    count = torch.zeros(B, dtype=torch.int32, device=dev)
+    q_host = query_of.cpu().long()
+    for b in range(B):
+        g = torch.nonzero((q_host[b] >= 0) & (q_host[b] < N)).flatten()          # matched GT objects, ascending
+        M = g.numel()
+        if M < 2:
+            continue
+        q, g = q_host[b][g].to(dev), g.to(dev)
+        r = torch.clamp(pred_rel[b][q][:, q].float(), 0.0, 1.0)                    # [M, M, R]
+        if pred_conn is not None:
+            r = r * torch.clamp(pred_conn[b].reshape(N, N)[q][:, q].float(), 0.0, 1.0)[..., None]
+        sc = obj_score[b][g].float()
+        so = sc[:, None] * sc[None, :]
+        off = ~torch.eye(M, dtype=torch.bool, device=dev)
+        if mode == 0:
+            score = (r * so[..., None])[off]                                       # [M (M - 1), R], row-major
+            s_i, o_i = (x[off] for x in torch.meshgrid(g, g, indexing="ij"))
+            flat_s, flat_o = s_i[:, None].expand(-1, R).reshape(-1), o_i[:, None].expand(-1, R).reshape(-1)
+            flat_p = torch.arange(R, device=dev).expand(s_i.shape[0], R).reshape(-1)
+            score, rvals = score.reshape(-1), r[off].reshape(-1)
+        else:
+            score = (r.max(-1)[0] * so)[off]                                       # [M (M - 1)]
+            flat_s, flat_o = (x[off] for x in torch.meshgrid(g, g, indexing="ij"))
+            rvals = r[off]                                                          # [M (M - 1), R]
+        order = torch.sort(score_keys_host(score), descending=True, stable=True)[1][:K]
+        n = order.numel()
+        count[b] = n
+        inds[b, :n, 0], inds[b, :n, 1] = flat_s[order], flat_o[order]
+        if mode == 0:
+            inds[b, :n, 2] = flat_p[order]
+        rel_scores[b, :n] = rvals[order]
+        triplet_scores[b, :n] = score[order]
+    return inds, rel_scores, triplet_scores, count
+
+
+def _pinned_to(t, device):
+    """A host tensor on ``device`` without waiting for the stream (a pageable host -> device copy would)."""
+    return t.pin_memory().to(device, non_blocking=True) if device.type == "cuda" else t
+
+
+@torch.no_grad()
+def matched_triplet_candidates(outputs, targets, matcher, num_labels, max_topk=100, mode="multiple", protocol="predcls"):
+    """The candidate lists of the PredCls and SGCls protocols (lib/evaluation/sg_eval.py:99-106) for a one-stage model: the
+    "given boxes" are the GT boxes, and the GT objects are the queries ``matcher`` assigns to them (as in
+    ``matched_pair_candidates``).  Per image the ``max_topk`` best entries over the matched queries, scored as
+    ``triplet_candidates`` scores them (train_egtr.py:57-69, 86, 122) with
+      * "predcls": object scores 1 and the GT classes;
+      * "sgcls": score and class of the matched query (softmax over the first ``num_labels`` logits);
+    ``mode`` "multiple": (s, o, p) triplets, ``rel_scores`` [K]; "single": (s, o) pairs, ``rel_scores`` [K, R].  The order
+    among equal scores is defined (ascending (s, o, p)); self pairs and unmatched objects are not in the list.
+
+    Returns one dict per image with the keys ``SceneGraphRecall.update`` takes, indices in GT-OBJECT numbering, all of one
+    shape: Gp = (largest G of the batch) + 1 objects -- ``pred_boxes[:G]`` are the GT boxes of ``evaluation.gt_entry``
+    bit for bit, padding objects have a zero box and class -1, an unmatched GT object (G > N) has class -1 -- and
+    ``max_topk`` candidate rows, the rows after the image's last entry pointing at object Gp - 1 at both ends: its class
+    -1 equals no GT class, so such a row never matches and the recalls are those of the unpadded list.  Device tensors go
+    to ``ops.matched_topk`` (csrc/matched_topk.hip), host tensors to ``matched_topk_host``; nothing waits for the
+    device."""
+    from .evaluation._common import gt_entry
+    if mode not in ("multiple", "single"):
+        raise ValueError(f"mode must be 'multiple' or 'single', got {mode!r}")
+    if protocol not in ("predcls", "sgcls"):
+        raise ValueError(f"protocol must be 'predcls' or 'sgcls', got {protocol!r}")
+    rel = outputs["pred_rel"]
+    conn = outputs["pred_connectivity"] if "pred_connectivity" in outputs else None
+    device = rel.device
+    B, N = rel.shape[0], rel.shape[1]
+    gts = [gt_entry(t) for t in targets]
+    Gp = max([g["gt_classes"].shape[0] for g in gts] + [0]) + 1
+    boxes = torch.zeros(B, Gp, 4, dtype=torch.float32)
+    gt_classes = torch.full((B, Gp), -1, dtype=torch.int64)
+    for b, g in enumerate(gts):
+        n = g["gt_classes"].shape[0]
+        boxes[b, :n], gt_classes[b, :n] = g["gt_boxes"], g["gt_classes"]
+    boxes, gt_classes = _pinned_to(boxes, device), _pinned_to(gt_classes, device)
+    query_of = _matched_query_of(outputs, targets, matcher, num_labels, Gp)
+    is_matched = query_of >= 0
+    if protocol == "predcls":
+        obj_scores = (gt_classes >= 0).float()
+        classes = torch.where(is_matched, gt_classes, -1)
+    else:
+        q_scores, q_classes = torch.max(outputs["logits"].softmax(-1)[..., :num_labels], -1)          # [B, N]
+        at = query_of.clamp(min=0).long()
+        obj_scores = torch.where(is_matched, q_scores.float().gather(1, at), 0.0)
+        classes = torch.where(is_matched, q_classes.gather(1, at), -1)
+    args = (rel.float().contiguous(), None if conn is None else conn.float().contiguous(), query_of,
+            obj_scores.contiguous(), max_topk, 0 if mode == "multiple" else 1)
+    if device.type == "cpu":
+        inds, rel_scores, triplet_scores, _ = matched_topk_host(*args)
+    else:
+        from . import ops
+        with torch.cuda.device(device):
+            inds, rel_scores, triplet_scores, _ = ops.matched_topk(*args)
+    return [{"pred_boxes": boxes[b], "pred_classes": classes[b], "obj_scores": obj_scores[b], "pred_rel_inds": inds[b],
+             "rel_scores": rel_scores[b], "triplet_scores": triplet_scores[b]} for b in range(B)]

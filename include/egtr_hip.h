@@ -572,6 +572,26 @@ int egtr_sgg_eval_preddet_f32(egtr_stream_t stream, const int64_t* cand, const f
                               int num_k, int* chosen_row, int* first_rank, int* first_rank_pred, double* slab,
                               double* acc);
 
+/* The candidate builder of the PredCls / SGCls protocols (matched_topk.hip): per image the num_cand best relation entries
+ * over the queries matched to GT objects, in a defined order.  pred_rel [batch, num_query, num_query, num_rel]; pred_conn
+ * [batch, num_query, num_query] or NULL; query_of int32 [batch, num_gt_padded]: the query of GT object g, -1 = unmatched or
+ * padding (a value >= num_query counts as unmatched); obj_score [batch, num_gt_padded].  Domain of an image: every
+ * (s, o, p) -- (s, o) with mode 1 -- of GT-object indices with s != o and both objects matched; self pairs and unmatched
+ * objects are not in the list.  With qs = query_of[s], qo = query_of[o], in float32, one rounding per product:
+ *   r = clamp(pred_rel[qs, qo, p], 0, 1) [* clamp(pred_conn[qs, qo], 0, 1)],  so = obj_score[s] * obj_score[o],
+ *   score = r * so (mode 0: multiple predicates per pair),  max_p(r) * so (mode 1: one entry per pair).
+ * Order: descending score with NaN last and -0 = +0 (the score_key of the predicate-detection entry), ties by ascending
+ * (s, o, p); it does not depend on num_gt_padded.  Outputs for the first count = min(num_cand, #entries) ranks: inds int64
+ * [batch, num_cand, 3] (mode 1: [.., 2]); rel_scores [batch, num_cand] = r (mode 1: [batch, num_cand, num_rel], the pair's
+ * whole r row); triplet_scores [batch, num_cand] = score; count int32 [batch].  Ranks from count to num_cand get index
+ * num_gt_padded - 1 in every column and score 0.  1 <= num_cand <= 1024, num_rel <= 256; num_gt_padded^2 * num_rel must be
+ * below 2^31 (EGTR_E_UNSUPPORTED otherwise).  workspace: egtr_matched_topk_workspace_bytes(batch, num_gt_padded, num_cand)
+ * bytes of device memory, 8-byte aligned (-1 for arguments outside the limits); contents need not be kept. */
+long long egtr_matched_topk_workspace_bytes(int batch, int num_gt_padded, int num_cand);
+int egtr_matched_topk_f32(egtr_stream_t stream, const float* pred_rel, const float* pred_conn, const int* query_of,
+                          const float* obj_score, int batch, int num_query, int num_rel, int num_gt_padded, int num_cand,
+                          int mode, void* workspace, int64_t* inds, float* rel_scores, float* triplet_scores, int* count);
+
 /* Open Images relation metrics of the reference's OI evaluator (lib/evaluation/oi_eval.py eval_rel_results,
  * lib/evaluation/ap_eval_rel.py; inputs as train_egtr.py:154-174 builds them), in three steps.  Layouts in oi_eval.hip.
  *
