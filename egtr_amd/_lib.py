@@ -140,6 +140,7 @@ SIGNATURES = {
     "egtr_conv1x1_strided_x6_f32": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I],
     "egtr_conv3x3_phase_channels": [_I, _I, _I, _I],
     "egtr_conv3x3_x6_f32": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I],
+    "egtr_conv3x3_x6_shift_f32": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I],
     "egtr_conv1x1_tail_pack_weights_bf16": [_P, _P, _I, _I, _I, _P],
     "egtr_conv1x1_tail_bf16": [_P, _P, _I, _P, _I, _P, _P, _P, _I, _I, _P, _I, _I, _I, _I],
     "egtr_ffn_x6_f32": [_P, _P, _I, _P, _P, _P, _P, _P, _P, ctypes.c_float, _P, _I, _P, _P, _I, _I, _I],

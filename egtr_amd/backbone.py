@@ -32,6 +32,17 @@ CONV3_FUSED_BF16 = True   # the bf16 twin (csrc/conv_tail_bf16.hip)
 CONV1_X6 = True           # fp32 first 1x1 convolution of a block through the tail kernel ...
 CONV1_X6_SHAPES = ((64, 64),)   # ... for these (input channels, planes): 7 us against the vendor GEMM's 16 at 64 -> 64 (layer 1,
                           # block 0); at 256 -> 64 and wider the two are level inside the forward (tools/conv2_ab.sh, SWITCH=CONV1_X6)
+# fp32: conv1 as a BIAS-FREE product (torch.mm: free to take the GEMM TunableOp picks, where the bias + ReLU epilogue pins
+# hipBLASLt's Bias_HA kernels), its folded-BN shift + ReLU applied by the own 3x3 kernel while it loads its input tile
+# (ops.conv3x3 in_shift, csrc/conv3x3_x6.hip) -- for the blocks whose conv2 runs on that kernel ...
+CONV1_SHIFT_ON_LOAD = True
+# ... and whose (input channels, planes) measured faster inside the forward, conv1 + conv3x3 launch together, means of four
+# traces each way (profiles/conv1_plain_vs_epilogue.txt): 256 -> 64: 36.6 us against 41.2, 256 -> 128: 50.1 / 55.5,
+# 512 -> 128: 36.2 / 39.7, 1024 -> 256: 38.3 / 42.5.  Left on the epilogue route: 512 -> 256 (62.3 / 63.5: inside the spread
+# of the epilogue GEMM's pick), 1024 -> 512 (65.1 / 63.3) and 2048 -> 512 (47.2 / 47.2) -- the stride-2 3x3 kernels pay 1-2 us
+# for the shift and the plain product gains nothing at these shapes.
+CONV1_PLAIN_SHAPES = ((256, 64), (256, 128), (512, 128), (1024, 256))
+CONV1_SPLIT_SHAPES = ()   # ... of these, through ops.linear_split_bf16 instead of torch.mm: none (23-27 us against 15-22)
 SHORTCUT_X6 = True        # fp32 stride-2 shortcut projections as the one-tap form of csrc/conv3x3_x6.hip
 FROZEN_PREFIX_NHWC = True  # training: the frozen stem + layer 1 through the channels-last inference kernels
 STEM_FUSED_BF16 = True    # the bf16 twin (csrc/stem_bf16.hip)
@@ -209,13 +220,18 @@ class Bottleneck(nn.Module):
         return out
 
     def forward_folded_nhwc(self, x, q):
-        """Inference, x a channels-last [B, C, H, W] tensor: conv1 = GEMM + bias + ReLU in its epilogue (no pass of its own),
-        conv2 = MIOpen NHWC; then fp32: the tail kernel (conv2's shift + ReLU, conv3, shift + shortcut + ReLU in one launch);
-        bf16: one epilogue pass, conv3 = GEMM, shift + shortcut + ReLU in one pass."""
+        """Inference, x a channels-last [B, C, H, W] tensor: conv1 = GEMM + bias + ReLU in its epilogue (no pass of its own; fp32
+        with CONV1_SHIFT_ON_LOAD: the bare product, shift + ReLU inside conv2's own kernel), conv2 = MIOpen NHWC; then fp32: the
+        tail kernel (conv2's shift + ReLU, conv3, shift + shortcut + ReLU in one launch); bf16: one epilogue pass, conv3 = GEMM,
+        shift + shortcut + ReLU in one pass."""
         from . import ops
         B, C, H, W_ = x.shape
         x2 = x.permute(0, 2, 3, 1).reshape(-1, C)                      # a view: channels-last IS [B*H*W, C]
         N1 = q["w1"].shape[0]
+        st2 = tuple(self.conv2.stride)
+        # conv2 goes to the own 3x3 kernel (given a dense channels-last fp32 input, checked on the tensor below)
+        conv2_x6 = (CONV2_X6 and ops.GEMM_SPLIT_BF16 and st2 in ((1, 1), (2, 2)) and q["w2"].shape[0] <= CONV2_X6_MAX_WIDTH)
+        shift1 = None      # conv1's shift + ReLU still to be applied (by conv2's kernel)
         if (CONV1_X6 and ops.GEMM_SPLIT_BF16 and (C, N1) in CONV1_X6_SHAPES and ops.conv1x1_tail_supported(x2, N1)):
             # fp32, block inputs of up to 512 channels: the panel-resident split-bf16 kernel of the tail, here without input
             # shift and shortcut (csrc/conv_tail_x6.hip), instead of the vendor GEMM with its bias + ReLU epilogue
@@ -223,17 +239,29 @@ class Bottleneck(nn.Module):
                 q["w1xs"] = ops.xs_split(q["w1"], weights=True)
                 q["b1f"] = q["b1"].float().contiguous()
             y = ops.conv1x1_tail(x2, None, q["w1xs"], q["b1f"], None, N1, relu_in=False, relu_out=True)
+        elif (CONV1_SHIFT_ON_LOAD and conv2_x6 and (C, N1) in CONV1_PLAIN_SHAPES and x.is_cuda and x.dtype == torch.float32
+              and q["b1"].dtype == torch.float32 and N1 == q["w2"].shape[1]):
+            # fp32, conv2 on the own kernel: the bare product here, shift + ReLU on that kernel's halo load
+            if (C, N1) in CONV1_SPLIT_SHAPES and ops.gemm_split_supported(x2, N1, C):
+                if "w1gs" not in q:
+                    q["w1gs"] = ops.gemm_split_weights(q["w1"])
+                y = ops.linear_split_bf16(x2, q["w1gs"], None, N1)
+            else:
+                y = torch.mm(x2, q["w1"].t())
+            shift1 = q["b1"]
         else:
             y = torch._addmm_activation(q["b1"], x2, q["w1"].t(), use_gelu=False)
         y = y.view(B, H, W_, -1).permute(0, 3, 1, 2)                   # channels-last view of the GEMM's output
-        st2 = tuple(self.conv2.stride)
-        if (CONV2_X6 and ops.GEMM_SPLIT_BF16 and st2 in ((1, 1), (2, 2)) and q["w2"].shape[0] <= CONV2_X6_MAX_WIDTH
-                and ops.conv3x3_supported(y, q["w2"].shape[0], st2[0])):
+        conv2_x6 = conv2_x6 and ops.conv3x3_supported(y, q["w2"].shape[0], st2[0])
+        if shift1 is not None and not conv2_x6:
+            ops.bias_act_rows_(y.permute(0, 2, 3, 1).reshape(-1, N1), shift1)   # (not reached: the product's output is dense)
+            shift1 = None
+        if conv2_x6:
             # fp32: the 3x3 convolution as a split-bf16 implicit GEMM of our own (csrc/conv3x3_x6.hip) -- 22 us where MIOpen's
             # fp32-MFMA kernels take 41 at 600 x 1000
             if "w2xs" not in q:
                 q["w2xs"] = ops.conv3x3_weights(q["w2"], st2[0])
-            y = ops.conv3x3(y, q["w2xs"], q["w2"].shape[0], st2[0])
+            y = ops.conv3x3(y, q["w2xs"], q["w2"].shape[0], st2[0], in_shift=shift1)
         else:
             y = F.conv2d(y, q["w2"], None, stride=self.conv2.stride, padding=1)
         if not y.is_contiguous(memory_format=torch.channels_last):

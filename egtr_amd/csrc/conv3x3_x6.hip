@@ -2,6 +2,8 @@
 // the middle convolution of a ResNet bottleneck in inference (reference: model/deformable_detr.py:735-760, the timm ResNet-50
 // backbone; frozen batch norm folded into the weights, its shift + ReLU applied by the consumer, conv_tail_x6.hip).
 //     y[b, h, w, n] = sum_{dy, dx, c} x[b, h + dy - 1, w + dx - 1, c] * W[n, c, dy, dx]
+// egtr_conv3x3_x6_shift_f32 (template flag SHIFT): the same of relu(x + in_shift[c]) -- the PRODUCER's folded shift + ReLU (the
+// block's conv1 run as a bias-free product) applied to the fp32 registers of the halo load, before the split.
 // MIOpen serves these with fp32-MFMA implicit-GEMM kernels at 65-75 TFLOP/s (37-42 us per convolution at 600 x 1000, bs 1).
 // Here: the six-term split-bf16 product of the x6 kernels (x6_common.h) as an implicit GEMM whose activation operand never leaves
 // the CU once loaded:
@@ -25,12 +27,18 @@ namespace {
 using namespace x6;
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 
+// relu(v + sh) per element (egtr_relu: a NaN stays a NaN, as with torch.relu)
+__device__ __forceinline__ f32x4v shift_relu(f32x4v v, f32x4v sh) {
+  return f32x4v{egtr_relu(v.x + sh.x), egtr_relu(v.y + sh.y), egtr_relu(v.z + sh.z), egtr_relu(v.w + sh.w)};
+}
+
 struct ConvArgs {
   const float* x;   // [B, H, W, C] channels-last
   const char* w;    // XS(Wm [N, 9 C]), Wm[n][(dy * 3 + dx) * C + c]
   float* y;         // [B, H, W, N]
   int B, H, W, N;
   int tiles_x, tiles_y;
+  const float* in_shift;   // [C] or null: the SHIFT kernels multiply relu(x + in_shift[c]) (the producer's folded-BN shift + ReLU)
 };
 
 #ifdef EGTR_CONV_TIMING
@@ -45,7 +53,7 @@ __device__ unsigned long long g_conv_rec[kRecWg][8];
 
 // TH x TW output pixels per workgroup; an MFMA row tile is 4 rows x 8 pixels (TW == 8), MT = TH / 4 of them, split over WM
 // wave rows; WN = 4 / WM waves side by side over the 32-column tiles.
-template <int C, int TH, int WM, int NTW, int NWV = 4>
+template <int C, int TH, int WM, int NTW, int NWV = 4, bool SHIFT = false>
 __global__ __launch_bounds__(64 * NWV) void conv3x3_x6_kernel(ConvArgs A) {
   constexpr int TW = 8;
   constexpr int HW_ = TW + 2, HH = TH + 2, HP = HH * HW_;   // halo tile
@@ -95,6 +103,14 @@ __global__ __launch_bounds__(64 * NWV) void conv3x3_x6_kernel(ConvArgs A) {
 
   // the halo tile: chunk idx = halo pixel * C4 + c4; pixels outside the image are zeros
   {
+    // SHIFT: NT is a multiple of C4, so a thread's channel quad is the same for all its chunks -- one float4 of shift, requested
+    // before the halo loads.  The padding is applied AFTER the activation and must stay exactly zero: pixels outside the image
+    // enter as -inf, relu(-inf + shift) = +0 for every finite shift (no second predicate at the split: recomputing `in` there
+    // made the compiler serialise the halo loads and double the registers)
+    constexpr float kPad = SHIFT ? -__builtin_inff() : 0.f;
+    static_assert(!SHIFT || NT % C4 == 0, "one channel quad per thread");
+    f32x4v sh = f32x4v{0.f, 0.f, 0.f, 0.f};
+    if constexpr (SHIFT) sh = *reinterpret_cast<const f32x4v*>(A.in_shift + 4 * (tid % C4));
     constexpr int CHUNKS = HP * C4;
     constexpr int NQ = (CHUNKS + NT - 1) / NT;
     constexpr int CH = 6;
@@ -108,7 +124,7 @@ __global__ __launch_bounds__(64 * NWV) void conv3x3_x6_kernel(ConvArgs A) {
         const int hp = idx / C4, c4 = idx % C4;
         const int gy = y0 - 1 + hp / HW_, gx = x0 - 1 + hp % HW_;
         const bool in = (q0 + q < NQ) && idx < CHUNKS && gy >= 0 && gy < A.H && gx >= 0 && gx < A.W;
-        v[q] = f32x4v{0.f, 0.f, 0.f, 0.f};
+        v[q] = f32x4v{kPad, kPad, kPad, kPad};
         if (in) v[q] = *reinterpret_cast<const f32x4v*>(xb + ((size_t)gy * A.W + gx) * C + 4 * c4);
       }
       if (q0 == 0) {
@@ -123,8 +139,10 @@ __global__ __launch_bounds__(64 * NWV) void conv3x3_x6_kernel(ConvArgs A) {
         const int idx = tid + NT * (q0 + q);
         if (q0 + q < NQ && idx < CHUNKS) {
           const int hp = idx / C4, c4 = idx % C4;
-          const xs::Split3 s0 = xs::split3_fast(v[q].x), s1 = xs::split3_fast(v[q].y), s2 = xs::split3_fast(v[q].z),
-                           s3 = xs::split3_fast(v[q].w);
+          f32x4v u = v[q];
+          if constexpr (SHIFT) u = shift_relu(u, sh);   // (padding: relu(-inf + shift) = 0)
+          const xs::Split3 s0 = xs::split3_fast(u.x), s1 = xs::split3_fast(u.y), s2 = xs::split3_fast(u.z),
+                           s3 = xs::split3_fast(u.w);
           __bf16* p = sA + hp * kPitch + 4 * c4;
           *reinterpret_cast<uint2*>(p) = make_uint2(xs::pack_hi16(s0.hi, s1.hi), xs::pack_hi16(s2.hi, s3.hi));
           *reinterpret_cast<uint2*>(p + HP * kPitch) = make_uint2(xs::pack_hi16(s0.mid, s1.mid), xs::pack_hi16(s2.mid, s3.mid));
@@ -214,7 +232,7 @@ __global__ __launch_bounds__(64 * NWV) void conv3x3_x6_kernel(ConvArgs A) {
 // (egtr_amd/ops.py::conv3x3_weights with `phase`).  One phase of k-steps is unrolled; the phases are a loop.
 // TAPS == 1: the same machinery as a 1x1 convolution with stride (a bottleneck's shortcut projection: no padding, the tile is
 // the 4 x 8 input pixels the outputs read, gathered with the stride; weights XS(W [N, C]) as they are).
-template <int C, int CP, int STRIDE, int TAPS = 9>
+template <int C, int CP, int STRIDE, int TAPS = 9, bool SHIFT = false>
 __global__ __launch_bounds__(256) void conv3x3_x6_phased_kernel(ConvArgs A) {
   constexpr int TH = 4, TW = 8;
   static_assert(TAPS == 9 || TAPS == 1, "3x3 or 1x1");
@@ -227,6 +245,7 @@ __global__ __launch_bounds__(256) void conv3x3_x6_phased_kernel(ConvArgs A) {
   constexpr int PF = EGTR_CONV_PF;
   constexpr int C4 = CP / 4;
   static_assert(KSP % (PF + 1) == 0, "the fragment ring must line up at the phase boundary");
+  static_assert(!SHIFT || (TAPS == 9 && 256 % C4 == 0), "one channel quad per thread");
   extern __shared__ __attribute__((aligned(16))) char s_raw[];
   __bf16* const sA = reinterpret_cast<__bf16*>(s_raw);   // [3][HP][kPitch]
 
@@ -269,6 +288,9 @@ __global__ __launch_bounds__(256) void conv3x3_x6_phased_kernel(ConvArgs A) {
       constexpr int CHUNKS = HP * C4;
       constexpr int NQ = (CHUNKS + 255) / 256;
       constexpr int CH = NQ < 8 ? NQ : 8;
+      constexpr float kPad = SHIFT ? -__builtin_inff() : 0.f;   // SHIFT: relu(-inf + shift) = +0, the padding stays zero
+      f32x4v sh = f32x4v{0.f, 0.f, 0.f, 0.f};                   // ... and this thread's channel quad of the phase
+      if constexpr (SHIFT) sh = *reinterpret_cast<const f32x4v*>(A.in_shift + ph * CP + 4 * (tid % C4));
 #pragma unroll
       for (int q0 = 0; q0 < NQ; q0 += CH) {
         f32x4v v[CH];
@@ -278,7 +300,7 @@ __global__ __launch_bounds__(256) void conv3x3_x6_phased_kernel(ConvArgs A) {
           const int hp = idx / C4, c4 = idx % C4;
           const int gy = TAPS == 9 ? iy0 + hp / HW_ : STRIDE * (y0 + hp / HW_), gx = TAPS == 9 ? ix0 + hp % HW_ : STRIDE * (x0 + hp % HW_);
           const bool in = (q0 + q < NQ) && idx < CHUNKS && gy >= 0 && gy < A.H && gx >= 0 && gx < A.W;
-          v[q] = f32x4v{0.f, 0.f, 0.f, 0.f};
+          v[q] = f32x4v{kPad, kPad, kPad, kPad};
           if (in) v[q] = *reinterpret_cast<const f32x4v*>(xb + ((size_t)gy * A.W + gx) * C + ph * CP + 4 * c4);
         }
 #pragma unroll
@@ -286,8 +308,10 @@ __global__ __launch_bounds__(256) void conv3x3_x6_phased_kernel(ConvArgs A) {
           const int idx = tid + 256 * (q0 + q);
           if (q0 + q < NQ && idx < CHUNKS) {
             const int hp = idx / C4, c4 = idx % C4;
-            const xs::Split3 s0 = xs::split3_fast(v[q].x), s1 = xs::split3_fast(v[q].y), s2 = xs::split3_fast(v[q].z),
-                             s3 = xs::split3_fast(v[q].w);
+            f32x4v u = v[q];
+            if constexpr (SHIFT) u = shift_relu(u, sh);   // (padding: relu(-inf + shift) = 0)
+            const xs::Split3 s0 = xs::split3_fast(u.x), s1 = xs::split3_fast(u.y), s2 = xs::split3_fast(u.z),
+                             s3 = xs::split3_fast(u.w);
             __bf16* p = sA + hp * kPitch + 4 * c4;
             *reinterpret_cast<uint2*>(p) = make_uint2(xs::pack_hi16(s0.hi, s1.hi), xs::pack_hi16(s2.hi, s3.hi));
             *reinterpret_cast<uint2*>(p + HP * kPitch) = make_uint2(xs::pack_hi16(s0.mid, s1.mid), xs::pack_hi16(s2.mid, s3.mid));
@@ -333,7 +357,7 @@ __global__ __launch_bounds__(256) void conv3x3_x6_phased_kernel(ConvArgs A) {
 // owns 4 x 8 output pixels x ONE 32-channel tile; within every phase wave q multiplies the q-th quarter of the phase's channels
 // (all 9 taps), so a wave walks K / 4; the four partial tiles meet in LDS at the end (fixed order: wave 0 + 1 + 2 + 3), each wave
 // finishing and storing a quarter of the rows.
-template <int C, int CP, int STRIDE>
+template <int C, int CP, int STRIDE, bool SHIFT = false>
 __global__ __launch_bounds__(256) void conv3x3_x6_ksplit_kernel(ConvArgs A) {
   constexpr int TH = 4, TW = 8;
   constexpr int HH = STRIDE * (TH - 1) + 3, HW_ = STRIDE * (TW - 1) + 3, HP = HH * HW_;
@@ -346,6 +370,7 @@ __global__ __launch_bounds__(256) void conv3x3_x6_ksplit_kernel(ConvArgs A) {
   constexpr int PF = (JS % 6 == 0) ? 5 : 2;
   constexpr int C4 = CP / 4;
   static_assert(KCP % 4 == 0 && JS % (PF + 1) == 0, "phase shape");
+  static_assert(!SHIFT || 256 % C4 == 0, "one channel quad per thread");
   extern __shared__ __attribute__((aligned(16))) char s_raw[];
   __bf16* const sA = reinterpret_cast<__bf16*>(s_raw);   // [3][HP][kPitch]; afterwards the partial tiles [4][16][64] floats
 
@@ -392,6 +417,9 @@ __global__ __launch_bounds__(256) void conv3x3_x6_ksplit_kernel(ConvArgs A) {
       constexpr int CHUNKS = HP * C4;
       constexpr int NQ = (CHUNKS + 255) / 256;
       constexpr int CH = NQ < 8 ? NQ : 8;
+      constexpr float kPad = SHIFT ? -__builtin_inff() : 0.f;   // SHIFT: relu(-inf + shift) = +0, the padding stays zero
+      f32x4v sh = f32x4v{0.f, 0.f, 0.f, 0.f};                   // ... and this thread's channel quad of the phase
+      if constexpr (SHIFT) sh = *reinterpret_cast<const f32x4v*>(A.in_shift + ph * CP + 4 * (tid % C4));
 #pragma unroll
       for (int q0 = 0; q0 < NQ; q0 += CH) {
         f32x4v v[CH];
@@ -401,7 +429,7 @@ __global__ __launch_bounds__(256) void conv3x3_x6_ksplit_kernel(ConvArgs A) {
           const int hp = idx / C4, c4 = idx % C4;
           const int gy = iy0 + hp / HW_, gx = ix0 + hp % HW_;
           const bool in = (q0 + q < NQ) && idx < CHUNKS && gy >= 0 && gy < A.H && gx >= 0 && gx < A.W;
-          v[q] = f32x4v{0.f, 0.f, 0.f, 0.f};
+          v[q] = f32x4v{kPad, kPad, kPad, kPad};
           if (in) v[q] = *reinterpret_cast<const f32x4v*>(xb + ((size_t)gy * A.W + gx) * C + ph * CP + 4 * c4);
         }
 #pragma unroll
@@ -409,8 +437,10 @@ __global__ __launch_bounds__(256) void conv3x3_x6_ksplit_kernel(ConvArgs A) {
           const int idx = tid + 256 * (q0 + q);
           if (q0 + q < NQ && idx < CHUNKS) {
             const int hp = idx / C4, c4 = idx % C4;
-            const xs::Split3 s0 = xs::split3_fast(v[q].x), s1 = xs::split3_fast(v[q].y), s2 = xs::split3_fast(v[q].z),
-                             s3 = xs::split3_fast(v[q].w);
+            f32x4v u = v[q];
+            if constexpr (SHIFT) u = shift_relu(u, sh);   // (padding: relu(-inf + shift) = 0)
+            const xs::Split3 s0 = xs::split3_fast(u.x), s1 = xs::split3_fast(u.y), s2 = xs::split3_fast(u.z),
+                             s3 = xs::split3_fast(u.w);
             __bf16* p = sA + hp * kPitch + 4 * c4;
             *reinterpret_cast<uint2*>(p) = make_uint2(xs::pack_hi16(s0.hi, s1.hi), xs::pack_hi16(s2.hi, s3.hi));
             *reinterpret_cast<uint2*>(p + HP * kPitch) = make_uint2(xs::pack_hi16(s0.mid, s1.mid), xs::pack_hi16(s2.mid, s3.mid));
@@ -464,13 +494,13 @@ __global__ __launch_bounds__(256) void conv3x3_x6_ksplit_kernel(ConvArgs A) {
   }
 }
 
-template <int C, int CP, int STRIDE>
+template <int C, int CP, int STRIDE, bool SHIFT = false>
 int launch_ksplit(hipStream_t st, ConvArgs A) {
   static unsigned long long raised = 0;
   constexpr int HP = (STRIDE * 3 + 3) * (STRIDE * 7 + 3);
   constexpr int lds = 3 * HP * (CP + 8) * 2;
   static_assert(lds >= 4 * 16 * 64 * 4, "the partial tiles reuse the halo tile's LDS");
-  auto kern = conv3x3_x6_ksplit_kernel<C, CP, STRIDE>;
+  auto kern = conv3x3_x6_ksplit_kernel<C, CP, STRIDE, SHIFT>;
   if (lds > 64 * 1024) {
     const int rc = egtr_raise_dynamic_lds(reinterpret_cast<const void*>(kern), lds, &raised);
     if (rc != EGTR_OK) return rc;
@@ -484,12 +514,12 @@ int launch_ksplit(hipStream_t st, ConvArgs A) {
   return egtr_check_launch();
 }
 
-template <int C, int CP, int STRIDE, int TAPS = 9>
+template <int C, int CP, int STRIDE, int TAPS = 9, bool SHIFT = false>
 int launch_phased(hipStream_t st, ConvArgs A) {
   static unsigned long long raised = 0;
   constexpr int HP = TAPS == 9 ? (STRIDE * 3 + 3) * (STRIDE * 7 + 3) : 32;
   constexpr int lds = 3 * HP * (CP + 8) * 2;
-  auto kern = conv3x3_x6_phased_kernel<C, CP, STRIDE, TAPS>;
+  auto kern = conv3x3_x6_phased_kernel<C, CP, STRIDE, TAPS, SHIFT>;
   if (lds > 64 * 1024) {
     const int rc = egtr_raise_dynamic_lds(reinterpret_cast<const void*>(kern), lds, &raised);
     if (rc != EGTR_OK) return rc;
@@ -503,14 +533,14 @@ int launch_phased(hipStream_t st, ConvArgs A) {
   return egtr_check_launch();
 }
 
-template <int C, int TH, int WM, int NTW, int NWV = 4>
+template <int C, int TH, int WM, int NTW, int NWV = 4, bool SHIFT = false>
 int launch(hipStream_t st, ConvArgs A) {
   static unsigned long long raised = 0;
   // (fewer resident workgroups -- LDS padded to 53 / 80 / 160 KB so that later workgroups' halo loads overlap earlier ones'
   // products -- measured slower: 23.1 -> 27.7 / 31.1 / 36.6 us at C = 64)
   constexpr int lds = 3 * (TH + 2) * 10 * (C + 8) * 2;
   constexpr int BN = 32 * NTW * (NWV / WM);
-  auto kern = conv3x3_x6_kernel<C, TH, WM, NTW, NWV>;
+  auto kern = conv3x3_x6_kernel<C, TH, WM, NTW, NWV, SHIFT>;
   if (lds > 64 * 1024) {
     const int rc = egtr_raise_dynamic_lds(reinterpret_cast<const void*>(kern), lds, &raised);
     if (rc != EGTR_OK) return rc;
@@ -552,46 +582,69 @@ extern "C" int egtr_conv3x3_phase_channels(int C, int N, int stride, int variant
   return 0;
 }
 
-extern "C" int egtr_conv3x3_x6_f32(egtr_stream_t stream, const float* x, const void* w_xs, float* y, int B, int H, int W, int C,
-                                   int N, int stride, int variant) {
-  if (!x || !w_xs || !y || B <= 0 || H <= 0 || W <= 0 || C <= 0 || N <= 0) return EGTR_E_ARG;
-  if ((reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(y) & 15) || (reinterpret_cast<uintptr_t>(w_xs) & 15))
-    return EGTR_E_UNSUPPORTED;
-  if (egtr_conv3x3_phase_channels(C, N, stride, variant) == 0) return EGTR_E_UNSUPPORTED;
-  ConvArgs A{x, static_cast<const char*>(w_xs), y, B, H, W, N, 0, 0};
-  hipStream_t st = static_cast<hipStream_t>(stream);
+namespace {
+// one dispatch table for both entries: SHIFT = relu(x + in_shift[c]) on the halo load
+template <bool SHIFT>
+int conv3x3_dispatch(hipStream_t st, ConvArgs A, int C, int stride, int variant) {
   if (stride == 2) {
     // (inside the forward: C = 128 phased 27.1 us, K split 33.8; C = 256 phased 37.4, K split 39.6; C = 512 phased 49, K split 37)
-    if (C == 128) return variant == 1 ? launch_ksplit<128, 64, 2>(st, A) : launch_phased<128, 64, 2>(st, A);
-    if (C == 256) return variant == 1 ? launch_ksplit<256, 64, 2>(st, A) : launch_phased<256, 64, 2>(st, A);
-    if (variant == 1) return launch_phased<512, 64, 2>(st, A);
-    return launch_ksplit<512, 64, 2>(st, A);
+    if (C == 128) return variant == 1 ? launch_ksplit<128, 64, 2, SHIFT>(st, A) : launch_phased<128, 64, 2, 9, SHIFT>(st, A);
+    if (C == 256) return variant == 1 ? launch_ksplit<256, 64, 2, SHIFT>(st, A) : launch_phased<256, 64, 2, 9, SHIFT>(st, A);
+    if (variant == 1) return launch_phased<512, 64, 2, 9, SHIFT>(st, A);
+    return launch_ksplit<512, 64, 2, SHIFT>(st, A);
   }
   // variant 0 = the library's choice, by the kernels' times INSIDE the forward (tools/conv2_ab.sh; stand-alone the variants are
   // within 10 % of each other): the kernels are bound by the matrix pipes during their product phase and by the halo-tile
   // latency before it (tools/conv3x3_timing.sh) -- many small workgroups balance the CUs best, and from C = 128 on splitting K
   // over the waves of a workgroup shortens the longest wave.  The other variants pin a kernel for the tests and the sweeps.
   if (C == 64) {
-    if (variant == 1) return launch<64, 8, 2, 1>(st, A);     // 8 x 8 pixels x 64 channels: 2 (pixel halves) x 2 (channel tiles)
-    if (variant == 2) return launch<64, 16, 2, 1>(st, A);    // 16 x 8 pixels
-    if (variant == 3) return launch<64, 16, 4, 1>(st, A);    // 16 x 8 pixels x 32 channels: the four waves share a weight stream
-    if (variant == 4) return launch_ksplit<64, 64, 1>(st, A);   // K split over the waves: 24.7 us inside the forward
-    return launch<64, 4, 1, 1, 2>(st, A);                       // 4 x 8 pixels x 64 channels, two waves: 20.4 us
+    if (variant == 1) return launch<64, 8, 2, 1, 4, SHIFT>(st, A);     // 8 x 8 pixels x 64 channels: 2 pixel halves x 2 channel tiles
+    if (variant == 2) return launch<64, 16, 2, 1, 4, SHIFT>(st, A);    // 16 x 8 pixels
+    if (variant == 3) return launch<64, 16, 4, 1, 4, SHIFT>(st, A);    // 16 x 8 pixels x 32 channels: one weight stream for 4 waves
+    if (variant == 4) return launch_ksplit<64, 64, 1, SHIFT>(st, A);   // K split over the waves: 24.7 us inside the forward
+    return launch<64, 4, 1, 1, 2, SHIFT>(st, A);                       // 4 x 8 pixels x 64 channels, two waves: 20.4 us
   }
   if (C == 128) {
-    if (variant == 1) return launch<128, 8, 2, 1>(st, A);    // 8 x 8 pixels x 64 channels
-    if (variant == 3) return launch<128, 16, 4, 1>(st, A);   // 16 x 8 pixels x 32 channels
-    if (variant == 4) return launch<128, 4, 1, 1, 2>(st, A); // 4 x 8 pixels x 64 channels, two waves
-    if (variant == 2) return launch<128, 4, 1, 1>(st, A);    // 4 x 8 pixels x 128 channels (4 waves x 32)
-    return launch_ksplit<128, 128, 1>(st, A);
+    if (variant == 1) return launch<128, 8, 2, 1, 4, SHIFT>(st, A);    // 8 x 8 pixels x 64 channels
+    if (variant == 3) return launch<128, 16, 4, 1, 4, SHIFT>(st, A);   // 16 x 8 pixels x 32 channels
+    if (variant == 4) return launch<128, 4, 1, 1, 2, SHIFT>(st, A);    // 4 x 8 pixels x 64 channels, two waves
+    if (variant == 2) return launch<128, 4, 1, 1, 4, SHIFT>(st, A);    // 4 x 8 pixels x 128 channels (4 waves x 32)
+    return launch_ksplit<128, 128, 1, SHIFT>(st, A);
   }
   if (C == 256) {
-    if (variant == 1) return launch_phased<256, 128, 1>(st, A);   // two phases of 128 channels, three workgroups per CU: 31.4 us
-    if (variant == 3) return launch<256, 4, 1, 1>(st, A);
-    return launch_ksplit<256, 128, 1>(st, A);   // K split over the waves                           // inside the forward, the whole halo tile resident (95 KiB): 29.6
+    if (variant == 1) return launch_phased<256, 128, 1, 9, SHIFT>(st, A);   // two phases of 128 channels, 3 workgroups per CU: 31.4 us
+    if (variant == 3) return launch<256, 4, 1, 1, 4, SHIFT>(st, A);
+    return launch_ksplit<256, 128, 1, SHIFT>(st, A);   // K split over the waves                           // inside the forward, the whole halo tile resident (95 KiB): 29.6
   }
-  if (variant == 1) return launch_phased<512, 128, 1>(st, A);
-  return launch_ksplit<512, 128, 1>(st, A);
+  if (variant == 1) return launch_phased<512, 128, 1, 9, SHIFT>(st, A);
+  return launch_ksplit<512, 128, 1, SHIFT>(st, A);
+}
+
+int conv3x3_check(const float* x, const void* w_xs, const float* y, int B, int H, int W, int C, int N, int stride, int variant) {
+  if (!x || !w_xs || !y || B <= 0 || H <= 0 || W <= 0 || C <= 0 || N <= 0) return EGTR_E_ARG;
+  if ((reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(y) & 15) || (reinterpret_cast<uintptr_t>(w_xs) & 15))
+    return EGTR_E_UNSUPPORTED;
+  if (egtr_conv3x3_phase_channels(C, N, stride, variant) == 0) return EGTR_E_UNSUPPORTED;
+  return EGTR_OK;
+}
+}  // namespace
+
+extern "C" int egtr_conv3x3_x6_f32(egtr_stream_t stream, const float* x, const void* w_xs, float* y, int B, int H, int W, int C,
+                                   int N, int stride, int variant) {
+  const int rc = conv3x3_check(x, w_xs, y, B, H, W, C, N, stride, variant);
+  if (rc != EGTR_OK) return rc;
+  ConvArgs A{x, static_cast<const char*>(w_xs), y, B, H, W, N, 0, 0, nullptr};
+  return conv3x3_dispatch<false>(static_cast<hipStream_t>(stream), A, C, stride, variant);
+}
+
+extern "C" int egtr_conv3x3_x6_shift_f32(egtr_stream_t stream, const float* x, const float* in_shift, const void* w_xs, float* y,
+                                         int B, int H, int W, int C, int N, int stride, int variant) {
+  if (!in_shift) return EGTR_E_ARG;
+  const int rc = conv3x3_check(x, w_xs, y, B, H, W, C, N, stride, variant);
+  if (rc != EGTR_OK) return rc;
+  if (reinterpret_cast<uintptr_t>(in_shift) & 15) return EGTR_E_UNSUPPORTED;
+  ConvArgs A{x, static_cast<const char*>(w_xs), y, B, H, W, N, 0, 0, in_shift};
+  return conv3x3_dispatch<true>(static_cast<hipStream_t>(stream), A, C, stride, variant);
 }
 
 extern "C" int egtr_conv1x1_strided_x6_f32(egtr_stream_t stream, const float* x, const void* w_xs, float* y, int B, int H, int W,
@@ -600,7 +653,7 @@ extern "C" int egtr_conv1x1_strided_x6_f32(egtr_stream_t stream, const float* x,
   if ((reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(y) & 15) || (reinterpret_cast<uintptr_t>(w_xs) & 15) ||
       N % 128 || (stride != 1 && stride != 2))
     return EGTR_E_UNSUPPORTED;
-  ConvArgs A{x, static_cast<const char*>(w_xs), y, B, H, W, N, 0, 0};
+  ConvArgs A{x, static_cast<const char*>(w_xs), y, B, H, W, N, 0, 0, nullptr};
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (stride == 2) {
     if (C == 256) return launch_phased<256, 256, 2, 1>(st, A);

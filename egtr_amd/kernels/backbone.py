@@ -116,15 +116,24 @@ def conv3x3_weights(w, stride=1, variant=0):
     return xs_split(wm, weights=True)
 
 
-def conv3x3(x, w_xs, N, stride=1, variant=0):
+def conv3x3(x, w_xs, N, stride=1, variant=0, in_shift=None):
     """3x3 convolution, stride 1 or 2, padding 1, no bias, on a channels-last fp32 tensor in ONE HIP launch with fp32-level
     accuracy on the bf16 matrix cores (egtr_conv3x3_x6_f32; reference: the timm ResNet-50 bottleneck's conv2,
     model/deformable_detr.py:735-760).  ``w_xs`` from ``conv3x3_weights`` with the same stride / variant.  Returns a channels-last
-    [B, N, Ho, Wo] tensor.  Inference only."""
+    [B, N, Ho, Wo] tensor.  Inference only.
+    ``in_shift`` ([C] fp32): the convolution of relu(x + in_shift[c]) instead -- the preceding bias-free conv1's folded-BN shift +
+    ReLU applied while the input tile is loaded, the padding staying zero (egtr_conv3x3_x6_shift_f32)."""
     B, C, H, W = x.shape
     Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
     y = torch.empty((B, N, Ho, Wo), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
-    _lib.launch("egtr_conv3x3_x6_f32", x.data_ptr(), w_xs.data_ptr(), y.data_ptr(), B, H, W, C, N, int(stride), int(variant))
+    if in_shift is None:
+        _lib.launch("egtr_conv3x3_x6_f32", x.data_ptr(), w_xs.data_ptr(), y.data_ptr(), B, H, W, C, N, int(stride), int(variant))
+        return y
+    if (not in_shift.is_cuda or in_shift.dtype != torch.float32 or in_shift.dim() != 1 or in_shift.shape[0] != C
+            or not in_shift.is_contiguous()):
+        raise RuntimeError(f"conv3x3: in_shift must be a contiguous float32 [{C}] device tensor")
+    _lib.launch("egtr_conv3x3_x6_shift_f32", x.data_ptr(), in_shift.data_ptr(), w_xs.data_ptr(), y.data_ptr(), B, H, W, C, N,
+                int(stride), int(variant))
     return y
 
 

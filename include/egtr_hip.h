@@ -896,6 +896,13 @@ int egtr_stem_conv7x7_pool_bf16(egtr_stream_t stream, const uint16_t* x, const u
 int egtr_conv3x3_phase_channels(int C, int N, int stride, int variant);
 int egtr_conv3x3_x6_f32(egtr_stream_t stream, const float* x, const void* w_xs, float* y, int B, int H, int W, int C, int N,
                         int stride, int variant);
+/* The same convolution of relu(x + in_shift[c]): the producer's folded batch-norm shift + ReLU (a bottleneck's conv1 run as a
+ * bias-free product) applied while the input tile is loaded, before the split.  The padding is applied AFTER the activation:
+ * pixels outside the image stay exactly zero.  in_shift [C] fp32, 16-byte aligned (EGTR_E_UNSUPPORTED otherwise; EGTR_E_ARG when
+ * null).  Shapes, variants, weight streams and dispatch as egtr_conv3x3_x6_f32; bit-identical to that entry on an input that
+ * holds relu(x + in_shift) already. */
+int egtr_conv3x3_x6_shift_f32(egtr_stream_t stream, const float* x, const float* in_shift, const void* w_xs, float* y, int B, int H,
+                              int W, int C, int N, int stride, int variant);
 
 /* 1x1 convolution with stride 1 or 2 (no padding, no bias) on channels-last fp32 data: x [B, H, W, C] -> y [B, Ho, Wo, N],
  * Ho = (H - 1) / stride + 1 -- the shortcut projection of a bottleneck that changes resolution (model/deformable_detr.py:735-760:
