@@ -199,7 +199,28 @@ class DecoderSelfAttentionFunction(Function):
         return gq, gk, gv, None, None
 
 
+SELF_ATTN_HEAD_DIM, SELF_ATTN_MAX_QUERIES = 32, 640   # what csrc/self_attn.hip serves (40 key tiles of 16 in registers)
+
+
+def _self_attention_composed(q, k, v, num_heads, want_maps):
+    """softmax(q k^T) v per head as batched GEMMs in the input dtype (the operation order of
+    ``DeformableDetrMultiheadAttention._attention_with_map``), differentiable by ordinary autograd; the maps are views."""
+    b, n, md = q.shape
+    d = md // num_heads
+    qh, kh, vh = (t.reshape(b, n, num_heads, d).transpose(1, 2) for t in (q, k, v))
+    probs = torch.softmax(torch.matmul(qh, kh.transpose(2, 3)), dim=-1)
+    out = torch.matmul(probs, vh).transpose(1, 2).reshape(b, n, md)
+    return (out, qh, kh) if want_maps else (out, None, None)
+
+
 def decoder_self_attention(q, k, v, num_heads, want_maps=True):
+    # CPU tensors and other dtypes are not what the kernel exists for: they go on below exactly as before (and are refused there)
+    if q.is_cuda and q.dtype in (torch.float32, torch.bfloat16):
+        n, md = q.shape[1], q.shape[2]
+        if not _gate("self_attention", True, md == SELF_ATTN_HEAD_DIM * num_heads and n <= SELF_ATTN_MAX_QUERIES,
+                     lambda: f"{n} queries of head_dim {md / num_heads:g}: the kernel serves head_dim {SELF_ATTN_HEAD_DIM} and up to "
+                             f"{SELF_ATTN_MAX_QUERIES} queries (batched GEMMs + softmax instead)"):
+            return _self_attention_composed(q, k, v, num_heads, want_maps)
     if (q.dtype == torch.bfloat16 and q.is_cuda and k.dtype == v.dtype == torch.bfloat16 and q.shape[-1] == 32 * num_heads
             and q.shape[1] <= 640 and not (torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad))):
         # bf16 model at inference: the kernel reads and writes bf16 itself (fp32 arithmetic) -- no cast launches around it

@@ -321,3 +321,88 @@ def xs_decode(buf, rows, K):
         byte = ((rb * (K // 16) + ks) * 3 + p) * 1024 + (kk // 8) * 512 + r * 16 + (kk % 8) * 2
         pieces.append(_bits_f32(half[byte // 2] << 16))
     return tuple(pieces)
+
+
+# ---- decoder self-attention inputs whose scores are EXACT fp32 numbers (csrc/self_attn.hip; tests/test_gpu_self_attention.py) --------
+# q and k are multiples of 1/8 in [-1, 1]: every product is a multiple of 1/64 of magnitude <= 1 and every partial sum of a
+# 32-term score (plus a shift of up to 128) stays below 2^8 in steps of 2^-6, i.e. inside 24 bits: the score is the same fp32
+# number whatever the summation order, so is s - max, and every value is exact in bf16 as well.  Component 0 of every head is
+# q = 1, k = 0: writing c into k's component 0 shifts every score of that key by exactly c.
+ATTN_HEAD_DIM = 32
+ATTN_TILE = 16          # keys per register tile of the forward kernel
+ATTN_DOMINANT = 128.0   # a dominant key's score exceeds every other by >= 128 - 2 * 11 > 104: exp(-104) is 0 in fp32
+
+
+def attn_grid_inputs(seed, B, N, M):
+    """(q, k, v, grad_out) fp32 CPU tensors [B, N, M * 32]: q, k on the 1/8 grid in [-1, 1] with component 0 of every head
+    q = 1, k = 0; v and the upstream gradient standard normal."""
+    g = torch.Generator().manual_seed(seed)
+    q = torch.randint(-8, 9, (B, N, M * ATTN_HEAD_DIM), generator=g).float() / 8
+    k = torch.randint(-8, 9, (B, N, M * ATTN_HEAD_DIM), generator=g).float() / 8
+    q[..., 0::ATTN_HEAD_DIM] = 1.0
+    k[..., 0::ATTN_HEAD_DIM] = 0.0
+    v = torch.randn(B, N, M * ATTN_HEAD_DIM, generator=g)
+    go = torch.randn(B, N, M * ATTN_HEAD_DIM, generator=g)
+    return q, k, v, go
+
+
+def attn_shift(k, M, c):
+    """A copy of ``k`` with component 0 of every head set to ``c``: every score moves by exactly c (q's component 0 is 1)."""
+    assert k.shape[-1] == M * ATTN_HEAD_DIM
+    k = k.clone()
+    k[..., 0::ATTN_HEAD_DIM] = c
+    return k
+
+
+def attn_dominant_keys(k, B, N, M, rot=0):
+    """(k', keys): a copy of ``k`` in which, for each (b, h), ONE key has component 0 = 128, and the [B, M] table of those keys.
+    The key of (b, h) lies in tile t = (b * M + h + rot) mod ntile, at min(16 t + (5 t mod 16), N - 1): with B * M >= ntile every
+    tile is dominant for some (b, h); smaller batches reach the other tiles through ``rot``."""
+    assert k.shape == (B, N, M * ATTN_HEAD_DIM)
+    ntile = (N + ATTN_TILE - 1) // ATTN_TILE
+    k = k.clone()
+    keys = torch.empty(B, M, dtype=torch.long)
+    for b in range(B):
+        for h in range(M):
+            t = (b * M + h + rot) % ntile
+            keys[b, h] = min(ATTN_TILE * t + (5 * t) % ATTN_TILE, N - 1)
+            k[b, keys[b, h], h * ATTN_HEAD_DIM] = ATTN_DOMINANT
+    return k, keys
+
+
+def attn_heads(t, M):
+    B, N, MD = t.shape
+    return t.view(B, N, M, MD // M).transpose(1, 2)
+
+
+def attn_scores(q, k, M):
+    """[B, M, N, N] scores q k^T per head in the operands' dtype."""
+    return attn_heads(q, M) @ attn_heads(k, M).transpose(-1, -2)
+
+
+def attn_compose(q, k, v, M, drop_tile=None, skip_max=False):
+    """softmax(q k^T) v per head as a plain torch composition in the operands' dtype and on their device: the yardstick of the
+    kernel tests (fp32) and their reference (fp64).  Two deliberately WRONG variants show that an assertion has teeth:
+    ``drop_tile=t`` leaves keys 16 t .. 16 t + 15 out (a register-tile slot that never receives its keys), ``skip_max`` takes
+    exp(s) without subtracting the row maximum."""
+    B, N, MD = q.shape
+    s = attn_scores(q, k, M)
+    if drop_tile is not None:
+        s = s.clone()
+        s[..., drop_tile * ATTN_TILE:(drop_tile + 1) * ATTN_TILE] = float("-inf")
+    if skip_max:
+        e = torch.exp(s)
+        w = e / e.sum(-1, keepdim=True)
+    else:
+        w = torch.softmax(s, -1)
+    return (w @ attn_heads(v, M)).transpose(1, 2).reshape(B, N, MD)
+
+
+def attn_dominant_mismatches(out, v, keys, M):
+    """The (b, h, tile) triples at which ``out[b, :, h]`` is not bit for bit ``v[b, keys[b, h], h]`` in every query row."""
+    B = out.shape[0]
+    bits = torch.int32 if out.dtype == torch.float32 else torch.int16
+    kd = keys.to(v.device)
+    want = torch.stack([attn_heads(v, M)[b, torch.arange(M, device=v.device), kd[b]] for b in range(B)])   # [B, M, D]
+    same = (attn_heads(out, M).contiguous().view(bits) == want[:, :, None, :].contiguous().view(bits)).all(-1).all(-1).cpu()
+    return [(b, h, int(keys[b, h]) // ATTN_TILE) for b in range(B) for h in range(M) if not bool(same[b, h])]
