@@ -41,8 +41,9 @@ constexpr int kMaxGt = 1024;
 constexpr int kMaxCls = 1024;
 constexpr int kThreads = 256;
 
-// descending-score order key: larger key = higher score; -0 and +0 are one value (numpy compares them equal)
-__device__ __forceinline__ unsigned score_key(float s) {
+// descending-score order key: larger key = higher score; -0 and +0 are one value (numpy compares them equal).  Not
+// order_key.h's score_key: this one has no NaN rule.
+__device__ __forceinline__ unsigned coco_score_key(float s) {
   unsigned u = __float_as_uint(s);
   if (u == 0x80000000u) u = 0u;
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
@@ -132,7 +133,7 @@ __global__ __launch_bounds__(kThreads) void coco_match(const MatchArgs a) {
   for (int i = tid; i < D; i += kThreads) {
     const long long l = a.det_labels[(long long)b * D + i];
     s_dlab[i] = (l >= 0 && l < K) ? (short)l : (short)-1;
-    s_dkey[i] = score_key(a.det_scores[(long long)b * D + i]);
+    s_dkey[i] = coco_score_key(a.det_scores[(long long)b * D + i]);
     s_mb[i] = 0;
     s_ib[i] = 0;
   }

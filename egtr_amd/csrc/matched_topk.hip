@@ -14,11 +14,9 @@
 // Two launches, select-then-sort in both:
 //   mtk_slice  grid (W, B).  The Gp x Gp pairs of an image are cut into W <= 256 contiguous slices.  A WAVE owns a pair:
 //              lanes walk the pair's R predicates (one coalesced row of pred_rel), so nothing is divided per entry.  The
-//              workgroup finds the K-th largest order word of its slice with a radix select (digits of 11, 11, 10 bits
-//              over the key half, then the same over the index half; LDS histogram, one pass over the slice per digit,
-//              recomputing the scores from global memory, which L2 serves after the first pass).  It stops at the first
-//              digit whose bucket is taken whole -- after the three key digits unless scores tie across the K-th rank --
-//              and then writes the <= K words >= the threshold to the workspace, unsorted.
+//              workgroup finds the K-th largest order word of its slice with the radix select of topk_select.h (one pass
+//              over the slice per digit, recomputing the scores from global memory, which L2 serves after the first
+//              pass) and then writes the <= K words >= the threshold to the workspace, unsorted.
 //   mtk_merge  grid (B).  The same select over the <= W * K surviving words of the image, a bitonic sort of the <= K
 //              winners in LDS, and the outputs: a wave per rank decodes flat, reads the entry's row again and writes
 //              indices, r (mode 1: the pair's whole r row) and score; ranks from count to K get index Gp - 1 and score 0.
@@ -30,13 +28,12 @@
 
 #include "common.h"
 #include "order_key.h"
+#include "topk_select.h"
 
 namespace {
 
 constexpr int kThreads = 512;
 constexpr int kWaves = kThreads / 64;
-constexpr int kBins = 2048;        // 11-bit digits
-constexpr int kBinsPerThread = kBins / kThreads;
 constexpr int kMaxK = 1024;        // _MAX_CAND
 constexpr int kMaxRel = 256;
 constexpr int kMaxSlices = 256;
@@ -55,12 +52,6 @@ struct Args {
   int* ws_count;                  // [B, W]
   int N, R, Gp, K, mode, W;
   long long slice_pairs;
-};
-
-struct Sel {
-  unsigned long long prefix;
-  int krem;
-  int done;   // 1: the bucket of the last digit is taken whole; 2: fewer than K entries, all are taken
 };
 
 __device__ __forceinline__ float clamp01(float x) { return x < 0.f ? 0.f : (x > 1.f ? 1.f : x); }   // keeps NaN
@@ -135,64 +126,8 @@ struct WorkspaceSource {
   }
 };
 
-// Radix select, all threads of the workgroup: the threshold word t such that exactly min(K, #entries) entries of `src` are
-// >= t.  Digit `pass` of a word: passes 0..2 are bits 63..53, 52..42, 41..32, passes 3..5 the same split of the low half.
-template <class Src>
-__device__ unsigned long long select_threshold(const Src& src, int K, unsigned* s_hist, unsigned* s_part, Sel* st) {
-  const int tid = threadIdx.x;
-  if (tid == 0) {
-    st->prefix = 0ull;
-    st->krem = K;
-    st->done = 0;
-  }
-  __syncthreads();
-  for (int pass = 0; pass < 6; ++pass) {
-    const int sub = pass % 3;
-    const int shift = (pass < 3 ? 32 : 0) + (sub == 0 ? 21 : (sub == 1 ? 10 : 0));
-    const int width = sub == 2 ? 10 : 11;
-    const unsigned mask = (1u << width) - 1u;
-    const int hi = shift + width;                      // the bits above the digit; 64 on pass 0
-    for (int i = tid; i < kBins; i += kThreads) s_hist[i] = 0u;
-    __syncthreads();
-    const unsigned long long prefix = st->prefix;
-    const unsigned krem = (unsigned)st->krem;
-    src([&](unsigned long long c) {
-      if (hi == 64 || (c >> hi) == (prefix >> hi)) atomicAdd(&s_hist[(unsigned)(c >> shift) & mask], 1u);
-    });
-    __syncthreads();
-    unsigned part = 0;                                 // thread t owns bins [t * kBinsPerThread, (t + 1) * kBinsPerThread)
-    for (int j = 0; j < kBinsPerThread; ++j) part += s_hist[tid * kBinsPerThread + j];
-    s_part[tid] = part;
-    __syncthreads();
-    unsigned above = 0;                                // entries in the bins of higher threads
-    for (int u = tid + 1; u < kThreads; ++u) above += s_part[u];
-    if (tid == 0 && above + part < krem) st->done = 2;
-    if (above < krem && krem <= above + part) {        // one thread: the bin of the krem-th largest is among its bins
-      unsigned acc = above;
-      for (int j = kBinsPerThread - 1; j >= 0; --j) {
-        const unsigned h = s_hist[tid * kBinsPerThread + j];
-        if (krem <= acc + h) {
-          st->prefix = prefix | ((unsigned long long)(tid * kBinsPerThread + j) << shift);
-          st->krem = (int)(krem - acc);
-          if (acc + h == krem) st->done = 1;
-          break;
-        }
-        acc += h;
-      }
-    }
-    __syncthreads();
-    if (st->done) break;                               // uniform: read after the barrier
-  }
-  const unsigned long long thr = st->done == 2 ? 0ull : st->prefix;
-  __syncthreads();                                     // st may be reused
-  return thr;
-}
-
 __global__ __launch_bounds__(kThreads) void mtk_slice(const Args a) {
-  __shared__ unsigned s_hist[kBins];
-  __shared__ unsigned s_part[kThreads];
-  __shared__ Sel s_sel;
-  __shared__ int s_cnt;
+  __shared__ TopkScratch<kThreads> s_sel;
   const int w = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
   const long long pairs = (long long)a.Gp * a.Gp;
   long long p0 = (long long)w * a.slice_pairs, p1 = p0 + a.slice_pairs;
@@ -200,27 +135,15 @@ __global__ __launch_bounds__(kThreads) void mtk_slice(const Args a) {
   if (p1 > pairs) p1 = pairs;
   const SliceSource src{a, b, p0, p1};
   const int K = a.K;
-  const unsigned long long thr = select_threshold(src, K, s_hist, s_part, &s_sel);
-  if (tid == 0) s_cnt = 0;
-  __syncthreads();
-  unsigned long long* out = a.ws_items + ((long long)b * a.W + w) * K;
-  src([&](unsigned long long c) {
-    if (c >= thr) {
-      const int pos = atomicAdd(&s_cnt, 1);
-      if (pos < K) out[pos] = c;
-    }
-  });
-  __syncthreads();
-  if (tid == 0) a.ws_count[(long long)b * a.W + w] = s_cnt < K ? s_cnt : K;
+  const unsigned long long thr = egtr_select_threshold(src, K, s_sel);
+  const int n = egtr_compact_ge(src, thr, K, a.ws_items + ((long long)b * a.W + w) * K, &s_sel.cnt);
+  if (tid == 0) a.ws_count[(long long)b * a.W + w] = n;
 }
 
 __global__ __launch_bounds__(kThreads) void mtk_merge(const Args a) {
-  __shared__ unsigned s_hist[kBins];
-  __shared__ unsigned s_part[kThreads];
+  __shared__ TopkScratch<kThreads> s_sel;
   __shared__ unsigned long long s_top[kMaxK];
   __shared__ int s_wcnt[kMaxSlices];
-  __shared__ Sel s_sel;
-  __shared__ int s_cnt;
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int K = a.K, R = a.R, Gp = a.Gp, N = a.N, W = a.W;
   for (int i = tid; i < W; i += kThreads) {
@@ -229,36 +152,9 @@ __global__ __launch_bounds__(kThreads) void mtk_merge(const Args a) {
   }
   __syncthreads();
   const WorkspaceSource src{a.ws_items + (long long)b * W * K, s_wcnt, W, K};
-  const unsigned long long thr = select_threshold(src, K, s_hist, s_part, &s_sel);
-  if (tid == 0) s_cnt = 0;
-  __syncthreads();
-  src([&](unsigned long long c) {
-    if (c >= thr) {
-      const int pos = atomicAdd(&s_cnt, 1);
-      if (pos < K) s_top[pos] = c;
-    }
-  });
-  __syncthreads();
-  const int n = s_cnt < K ? s_cnt : K;
-  int P = 1;
-  while (P < n) P <<= 1;                               // P <= 1024 = kMaxK
-  for (int i = n + tid; i < P; i += kThreads) s_top[i] = 0ull;   // below every real word (flat < 2^31)
-  __syncthreads();
-  for (int k = 2; k <= P; k <<= 1) {                   // bitonic sort, descending
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = tid; i < P; i += kThreads) {
-        const int x = i ^ j;
-        if (x > i) {
-          const unsigned long long u = s_top[i], v = s_top[x];
-          if ((i & k) == 0 ? u < v : u > v) {
-            s_top[i] = v;
-            s_top[x] = u;
-          }
-        }
-      }
-      __syncthreads();
-    }
-  }
+  const unsigned long long thr = egtr_select_threshold(src, K, s_sel);
+  const int n = egtr_compact_ge(src, thr, K, s_top, &s_sel.cnt);
+  egtr_bitonic_sort_desc<kThreads>(s_top, n);         // pads with 0: below every real word (flat < 2^31)
 
   const int cols = a.mode == 0 ? 3 : 2;
   const int* qof = a.query_of + (long long)b * Gp;

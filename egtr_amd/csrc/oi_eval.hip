@@ -10,13 +10,15 @@
 // ascending, and are unique.  Pass 1 has many workgroups per image: each takes 512 pairs, finds every pair's kk best
 // predicates by kk argmax passes over the row (NaN last, ties to the lower predicate index: numpy argsort(-row) with a
 // defined tie rule),
-// writes the keys to LDS and keeps its `topk` largest (a radix select of the threshold key, then a compaction).  Pass 2 is
-// one workgroup per image: the same radix select over the partial lists, a compaction to LDS and a bitonic sort; it
-// writes the detections (s, o, p, score) in rank order and their count.
+// writes the keys to LDS and keeps its `topk` largest (radix_threshold below: a radix select of the threshold key over the
+// nonzero keys; then the compaction of topk_select.h).  Pass 2 is one workgroup per image: the same select over the
+// partial lists, the compaction to LDS and the bitonic sort of topk_select.h; it writes the detections (s, o, p, score)
+// in rank order and their count.  radix_threshold (8-bit digits) stays beside the 11-bit select of topk_select.h because
+// the shared one made oi_select_partial slower than its spread (profiles/eval_kernels_shared_ab.txt).
 //
-// oi_match + oi_fold (egtr_oi_match_f32): one workgroup per image (4 waves).
-//   * recall: the first-rank matching of sgg_match (sgg_match.h) on the detections -- labels (s, p, o) and the fp64
-//     bbox.pyx IoU >= 0.5 -- gives hits@k = #{GT triplets with first rank < k};
+// oi_match + the fold of sgg_match.h (egtr_oi_match_f32): one workgroup per image (4 waves).
+//   * recall: the first-rank matching of sgg_match.h with the sgdet box test on the detections -- labels (s, p, o) and
+//     the fp64 bbox.pyx IoU >= 0.5 -- gives hits@k = #{GT triplets with first rank < k};
 //   * npos: GT triplets per predicate class (integer LDS tallies);
 //   * TP flags for the AP: a wave per predicate class walks that class's detections in rank order (the in-image order of
 //     prepare_mAP_dets); its lanes hold the image's GT triplets of the class, compute the float32 bbox_iou of
@@ -25,8 +27,7 @@
 //     detection is a TP when ovmax > 0.5 and GT jmax is not yet visited (visited bits live in the lanes' registers, one
 //     bit per 64 GT triplets); rel mode uses min(iou_s, iou_o), phr mode the IoU of the union boxes, each with its own
 //     visited state.  The visited state is per image, so the flags need no other image.
-//   Per-image rows go to a slab; oi_fold adds them into the fp64 accumulators in image order (the same store-and-sum
-//   scheme as sgg_fold).
+//   Per-image rows go to a slab; egtr_fold_rows adds them into the fp64 accumulators in image order.
 //
 // oi_ap (egtr_oi_ap_f64): once per evaluation, one workgroup per (class, rel | phr) over the class's records, already
 // sorted by confidence: tp cumsum (exact integers in fp64), rec = cum / (npos + 1e-12), prec = cum / (i + 1), the
@@ -45,22 +46,23 @@
 
 #include "common.h"
 #include "sgg_match.h"
+#include "topk_select.h"
+
+using namespace egtr_eval;
 
 namespace {
 
 typedef unsigned long long u64;
 
-constexpr int kMaxRel = 256;
-constexpr int kMaxTopk = 1024;
+constexpr int kMaxRel = kEvalMaxRel, kMaxTopk = kEvalMaxCand, kMaxK = kEvalMaxK;
 constexpr int kMaxPrdK = 8;
-constexpr int kMaxK = 8;
 constexpr long long kMaxPairs = 300ll * 300;
 constexpr int kMaxGtPerImage = 64 * 64;   // AP visited bits: one 64-bit register per lane
 constexpr int kFlatBits = 20;             // flat = m * kk + j < 2^20 (90000 * 8 < 2^20)
 constexpr int kPairsPerBlock = 512;
 constexpr int kSelThreads = 256;
 constexpr int kMergeThreads = 1024;
-constexpr int kMatchThreads = 256;
+constexpr int kMatchThreads = kEvalThreads;
 constexpr int kApThreads = 256;
 
 __device__ __forceinline__ u64 oi_key(float score, unsigned flat, int p) {
@@ -139,6 +141,21 @@ __device__ u64 radix_threshold(Get get, int n, int want, int* s_hist, u64* s_b) 
   return prefix ? prefix : 1;
 }
 
+// The nonzero keys of an array, as a source of topk_select.h's compaction.
+template <int NT>
+struct NonzeroKeys {
+  const u64* keys;
+  int n;
+
+  template <class F>
+  __device__ __forceinline__ void operator()(F&& f) const {
+    for (int i = threadIdx.x; i < n; i += NT) {
+      const u64 k = keys[i];
+      if (k) f(k);
+    }
+  }
+};
+
 struct SelArgs {
   const float* scores;    // [B, M, R] with img_stride / row_stride (elements)
   const float* obj;       // [B, N]
@@ -208,18 +225,9 @@ __global__ __launch_bounds__(kSelThreads) void oi_select_partial(const SelArgs a
   __syncthreads();
   const int n = kPairsPerBlock * kk;
   const u64 thr = radix_threshold<kSelThreads>([&](int i) { return s_key[i]; }, n, a.topk, s_hist, s_b);
-  if (tid == 0) s_cnt = 0;
-  __syncthreads();
   u64* out = a.partial + ((long long)b * a.nblk + blk) * a.topk;
-  for (int i = tid; i < n; i += kSelThreads) {
-    const u64 k = s_key[i];
-    if (k >= thr) {
-      const int pos = atomicAdd(&s_cnt, 1);
-      if (pos < a.topk) out[pos] = k;
-    }
-  }
-  __syncthreads();
-  for (int i = s_cnt + tid; i < a.topk; i += kSelThreads) out[i] = 0;
+  const int cnt = egtr_compact_ge(NonzeroKeys<kSelThreads>{s_key, n}, thr, a.topk, out, &s_cnt);
+  for (int i = cnt + tid; i < a.topk; i += kSelThreads) out[i] = 0;
 }
 
 __global__ __launch_bounds__(kMergeThreads) void oi_select_merge(const SelArgs a) {
@@ -231,32 +239,8 @@ __global__ __launch_bounds__(kMergeThreads) void oi_select_merge(const SelArgs a
   const int n = a.nblk * a.topk;
   const u64* keys = a.partial + (long long)b * n;
   const u64 thr = radix_threshold<kMergeThreads>([&](int i) { return keys[i]; }, n, a.topk, s_hist, s_b);
-  if (tid == 0) s_cnt = 0;
-  s_sort[tid] = 0;
-  __syncthreads();
-  for (int i = tid; i < n; i += kMergeThreads) {
-    const u64 k = keys[i];
-    if (k >= thr) {
-      const int pos = atomicAdd(&s_cnt, 1);
-      if (pos < a.topk) s_sort[pos] = k;
-    }
-  }
-  __syncthreads();
-  // bitonic sort of the 1024 slots, descending (zero keys sink to the end)
-  for (int k = 2; k <= kMaxTopk; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      const int ixj = tid ^ j;
-      if (ixj > tid) {
-        const u64 x = s_sort[tid], y = s_sort[ixj];
-        if (((tid & k) == 0) ? (x < y) : (x > y)) {
-          s_sort[tid] = y;
-          s_sort[ixj] = x;
-        }
-      }
-      __syncthreads();
-    }
-  }
-  const int cnt = s_cnt < a.topk ? s_cnt : a.topk;
+  const int cnt = egtr_compact_ge(NonzeroKeys<kMergeThreads>{keys, n}, thr, a.topk, s_sort, &s_cnt);
+  egtr_bitonic_sort_desc<kMergeThreads>(s_sort, cnt);
   if (tid < a.topk) {
     int* sop = a.det_sop + ((long long)b * a.topk + tid) * 3;
     if (tid < cnt) {
@@ -278,24 +262,14 @@ __global__ __launch_bounds__(kMergeThreads) void oi_select_merge(const SelArgs a
   if (tid == 0) a.det_count[b] = cnt;
 }
 
-struct MatchArgs {
+struct MatchArgs : EvalCommon {   // K = topk, R = C predicate classes
   const int* det_sop;           // [B, topk, 3]
   const int* det_count;         // [B]
   const float* pred_boxes;      // [B, N, 4] xyxy
   const int64_t* pred_classes;  // [B, N]
-  const int64_t* gt_rels;       // [T, 3]
-  const int64_t* rel_off;       // [B + 1]
-  const float* gt_boxes;        // [G, 4]
-  const int64_t* gt_classes;    // [G]
-  const int64_t* box_off;       // [B + 1]
   unsigned char* tp;            // [2, B, topk]: rel flags, then phr flags
   double* slab;                 // [B, W]
-  long long T, G;
-  int topk, N, C, nk, W;
-  int ks[kMaxK];
 };
-
-__device__ __forceinline__ long long clamp_off(long long v, long long hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 
 // NaN-propagating min / max (torch.min / torch.max / np.minimum / np.maximum on two values)
 __device__ __forceinline__ float nan_min(float a, float b) { return (a != a || a < b) ? a : b; }
@@ -314,7 +288,8 @@ __device__ __forceinline__ float bbox_iou_f32(float4 p, float4 q) {
   return inter / ((a1 + a2) - inter);
 }
 
-__device__ __forceinline__ float4 union_box(float4 s, float4 o) {
+// boxes_union of ap_eval_rel.py: a NaN coordinate stays NaN.  Not vrd_eval.hip's phrase_union_box (fminf / fmaxf).
+__device__ __forceinline__ float4 oi_union_box(float4 s, float4 o) {
   return make_float4(nan_min(s.x, o.x), nan_min(s.y, o.y), nan_max(s.z, o.z), nan_max(s.w, o.w));
 }
 
@@ -337,15 +312,17 @@ __device__ __forceinline__ void wave_argmax(float* v, int* i) {
   }
 }
 
+// The recall part is recall_match's (sgg_match.h) with these differences, each the reference's OI behaviour: gok does not
+// look at the GT predicate, the IoU threshold is the literal 0.5, K is det_count[b] clamped to [0, topk], and the row
+// layout (npos, no per-predicate recall) is its own.
 __global__ __launch_bounds__(kMatchThreads) void oi_match(const MatchArgs a) {
   __shared__ int4 s_lab[kMaxTopk];   // class_s, class_o, predicate, valid
-  __shared__ float4 s_sbox[kMaxTopk];
-  __shared__ float4 s_obox[kMaxTopk];
+  __shared__ SubjectObjectBoxes s_box;
   __shared__ int s_npos[kMaxRel];
   __shared__ int s_ndet[kMaxRel];
   __shared__ int s_hits[kMaxK];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int N = a.N, C = a.C, nk = a.nk, topk = a.topk;
+  const int C = a.R, nk = a.nk, topk = a.K;
   int K = a.det_count[b];
   K = K < 0 ? 0 : (K > topk ? topk : K);
 
@@ -358,33 +335,16 @@ __global__ __launch_bounds__(kMatchThreads) void oi_match(const MatchArgs a) {
 
   for (int d = tid; d < K; d += kMatchThreads) {
     const int* sop = a.det_sop + ((long long)b * topk + d) * 3;
-    const int s = sop[0], o = sop[1], p = sop[2];
-    int4 lab = make_int4(0, 0, 0, 0);
-    float4 sb = make_float4(0.f, 0.f, 0.f, 0.f), ob = sb;
-    if (s >= 0 && s < N && o >= 0 && o < N && p >= 0 && p < C) {
-      const long long cs = a.pred_classes[(long long)b * N + s], co = a.pred_classes[(long long)b * N + o];
-      if (cs == (int)cs && co == (int)co) {
-        lab = make_int4((int)cs, (int)co, p, 1);
-        const float* bs = a.pred_boxes + ((long long)b * N + s) * 4;
-        const float* bo = a.pred_boxes + ((long long)b * N + o) * 4;
-        sb = make_float4(bs[0], bs[1], bs[2], bs[3]);
-        ob = make_float4(bo[0], bo[1], bo[2], bo[3]);
-        atomicAdd(&s_ndet[p], 1);
-      }
-    }
+    const float *bs, *bo;
+    const int4 lab = egtr_candidate_label(a.pred_boxes, a.pred_classes, b, a.N, C, sop[0], sop[1], sop[2], &bs, &bo);
+    if (lab.w) atomicAdd(&s_ndet[lab.z], 1);
     s_lab[d] = lab;
-    s_sbox[d] = sb;
-    s_obox[d] = ob;
+    s_box.stage(d, bs, bo);
   }
   __syncthreads();
 
-  const long long r0 = clamp_off(a.rel_off[b], a.T);
-  long long r1 = clamp_off(a.rel_off[b + 1], a.T);
-  if (r1 < r0) r1 = r0;
-  const long long g0 = clamp_off(a.box_off[b], a.G);
-  long long g1 = clamp_off(a.box_off[b + 1], a.G);
-  if (g1 < g0) g1 = g0;
-  const long long n_gt_boxes = g1 - g0, n_rel = r1 - r0;
+  const ImageRange im(a.rel_off, a.box_off, a.T, a.G, b);
+  const long long r0 = im.r0, r1 = im.r1, g0 = im.g0, n_gt_boxes = im.n_box(), n_rel = im.n_rel();
   const bool skip = n_rel == 0;
   unsigned char* tp_rel = a.tp + (long long)b * topk;
   unsigned char* tp_phr = a.tp + ((long long)gridDim.x + b) * topk;
@@ -395,10 +355,9 @@ __global__ __launch_bounds__(kMatchThreads) void oi_match(const MatchArgs a) {
     const bool gok = gs >= 0 && gs < n_gt_boxes && go >= 0 && go < n_gt_boxes;
     int fr = K;
     if (gok) {
-      const float* gsb = a.gt_boxes + (g0 + gs) * 4;
-      const float* gob = a.gt_boxes + (g0 + go) * 4;
-      fr = egtr_first_rank_wave(s_lab, s_sbox, s_obox, K, a.gt_classes[g0 + gs], a.gt_classes[g0 + go], gp, gsb[0],
-                                gsb[1], gsb[2], gsb[3], gob[0], gob[1], gob[2], gob[3], 0.5, lane);
+      const SubjectObjectBoxes::Gt g = SubjectObjectBoxes::gt(a.gt_boxes + (g0 + gs) * 4, a.gt_boxes + (g0 + go) * 4);
+      fr = egtr_first_rank_wave(s_lab, K, a.gt_classes[g0 + gs], a.gt_classes[g0 + go], gp, lane,
+                                [&](int c) { return s_box.test(c, g, 0.5); });
     }
     if (lane == 0) {
       if (gp >= 0 && gp < C) atomicAdd(&s_npos[gp], 1);
@@ -420,7 +379,7 @@ __global__ __launch_bounds__(kMatchThreads) void oi_match(const MatchArgs a) {
         const int d = base + __ffsll(mine) - 1;
         mine &= mine - 1;
         const int4 lab = s_lab[d];
-        const float4 ds = s_sbox[d], dob = s_obox[d], dr = union_box(ds, dob);
+        const float4 ds = s_box.sbox[d], dob = s_box.obox[d], dr = oi_union_box(ds, dob);
         float best_r = 0.f, best_p = 0.f;
         int ir = -1, ip = -1;
         bool have = false, valid_any = false;
@@ -438,7 +397,7 @@ __global__ __launch_bounds__(kMatchThreads) void oi_match(const MatchArgs a) {
               const float4 gov = make_float4(gob[0], gob[1], gob[2], gob[3]);
               const float m = valid ? 1.0f : 0.0f;
               const float ovr = nan_min(bbox_iou_f32(ds, gsv), bbox_iou_f32(dob, gov)) * m;
-              const float ovp = bbox_iou_f32(dr, union_box(gsv, gov)) * m;
+              const float ovp = bbox_iou_f32(dr, oi_union_box(gsv, gov)) * m;
               const int j = 64 * q + lane;
               if (argmax_better(ovr, j, best_r, ir)) {
                 best_r = ovr;
@@ -507,11 +466,6 @@ __global__ __launch_bounds__(kMatchThreads) void oi_match(const MatchArgs a) {
   }
 }
 
-__global__ __launch_bounds__(256) void oi_fold(const double* __restrict__ slab, int B, int W, double* __restrict__ acc) {
-  const int j = blockIdx.x * 256 + threadIdx.x;
-  if (j < W) egtr_fold_column(slab, B, W, acc, j);
-}
-
 // inclusive scan of v over the workgroup (kApThreads threads); s_w: one int per wave
 __device__ __forceinline__ int block_inclusive_sum(int v, int* s_w) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -547,8 +501,8 @@ __global__ __launch_bounds__(kApThreads) void oi_ap(const unsigned char* __restr
   __shared__ int s_wi[kApThreads / 64];
   __shared__ double s_wd[kApThreads / 64];
   const int c = blockIdx.x, mode = blockIdx.y, tid = threadIdx.x;
-  const long long a0 = clamp_off(seg_off[c], n_total);
-  long long a1 = clamp_off(seg_off[c + 1], n_total);
+  const long long a0 = egtr_clamp_off(seg_off[c], n_total);
+  long long a1 = egtr_clamp_off(seg_off[c + 1], n_total);
   if (a1 < a0) a1 = a0;
   const long long n = a1 - a0;
   const unsigned char* f = tp + mode * n_total + a0;
@@ -663,44 +617,29 @@ extern "C" int egtr_oi_match_f32(egtr_stream_t stream, const int* det_sop, const
                                  const float* gt_boxes, const int64_t* gt_classes, const int64_t* box_offsets,
                                  long long num_gt_boxes, const int* ks, int num_k, unsigned char* tp, double* slab,
                                  double* acc) {
-  if (batch < 0 || topk < 1 || topk > kMaxTopk || num_obj < 1 || num_rel < 1 || num_rel > kMaxRel || num_k < 1 ||
-      num_k > kMaxK || num_gt_rels < 0 || num_gt_boxes < 0)
+  if (batch < 0 || topk < 1 || topk > kMaxTopk || num_obj < 1 || num_rel < 1 || num_rel > kMaxRel ||
+      num_gt_rels < 0 || num_gt_boxes < 0 || egtr_bad_ks(ks, num_k))
     return EGTR_E_ARG;
-  if (!ks) return EGTR_E_ARG;
-  for (int j = 0; j < num_k; ++j)
-    if (ks[j] < 1 || (j > 0 && ks[j] <= ks[j - 1])) return EGTR_E_ARG;
   if ((num_gt_rels > 0 && !gt_rels) || (num_gt_boxes > 0 && (!gt_boxes || !gt_classes))) return EGTR_E_ARG;
   if (batch == 0) return EGTR_OK;
   if (!det_sop || !det_count || !pred_boxes || !pred_classes || !rel_offsets || !box_offsets || !tp || !slab)
     return EGTR_E_ARG;
 
   MatchArgs a;
+  egtr_fill_common(&a, gt_rels, rel_offsets, num_gt_rels, gt_boxes, gt_classes, box_offsets, num_gt_boxes, topk, num_obj,
+                   num_rel, (int)egtr_oi_eval_width(num_rel, num_k), ks, num_k);
   a.det_sop = det_sop;
   a.det_count = det_count;
   a.pred_boxes = pred_boxes;
   a.pred_classes = pred_classes;
-  a.gt_rels = gt_rels;
-  a.rel_off = rel_offsets;
-  a.gt_boxes = gt_boxes;
-  a.gt_classes = gt_classes;
-  a.box_off = box_offsets;
   a.tp = tp;
   a.slab = slab;
-  a.T = num_gt_rels;
-  a.G = num_gt_boxes;
-  a.topk = topk;
-  a.N = num_obj;
-  a.C = num_rel;
-  a.nk = num_k;
-  a.W = (int)egtr_oi_eval_width(num_rel, num_k);
-  for (int j = 0; j < kMaxK; ++j) a.ks[j] = j < num_k ? ks[j] : 0;
 
   const hipStream_t s = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(oi_match, dim3((unsigned)batch), dim3(kMatchThreads), 0, s, a);
-  int st = egtr_check_launch();
+  const int st = egtr_check_launch();
   if (st != EGTR_OK || !acc) return st;
-  hipLaunchKernelGGL(oi_fold, dim3((unsigned)((a.W + 255) / 256)), dim3(256), 0, s, slab, batch, a.W, acc);
-  return egtr_check_launch();
+  return egtr_fold_rows(s, slab, batch, a.W, acc);
 }
 
 extern "C" int egtr_oi_ap_f64(egtr_stream_t stream, const unsigned char* tp_sorted, const int64_t* seg_offsets,

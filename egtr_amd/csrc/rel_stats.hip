@@ -7,21 +7,22 @@
 #include <stdint.h>
 
 #include "common.h"
+#include "sgg_match.h"
+
+using namespace egtr_eval;
 
 namespace {
 
 constexpr int kThreads = 256;
 
-__device__ __forceinline__ long long clamp_off(long long v, long long hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
-
 // One thread per relation row: its image from the row offsets (binary search over B + 1 entries), the two classes through
 // the image's object range, one 64-bit integer atomic add.  Integer addition is order-free, so the counts are the same on
 // every run.  Duplicate rows count each time (both reference loops do).  A row with a subject / object index outside its
 // image's objects, a class outside [0, C1) or a predicate outside [0, R) is NOT counted and raises bit 0 of *status (sticky).
-__global__ __launch_bounds__(kThreads) void rel_stats_count(const long long* __restrict__ rels,
-                                                            const long long* __restrict__ rel_off, long long T,
-                                                            const long long* __restrict__ classes,
-                                                            const long long* __restrict__ box_off, long long G, int B,
+__global__ __launch_bounds__(kThreads) void rel_stats_count(const int64_t* __restrict__ rels,
+                                                            const int64_t* __restrict__ rel_off, long long T,
+                                                            const int64_t* __restrict__ classes,
+                                                            const int64_t* __restrict__ box_off, long long G, int B,
                                                             int C1, int R, unsigned long long* __restrict__ counts,
                                                             unsigned* __restrict__ status) {
   const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
@@ -31,11 +32,9 @@ __global__ __launch_bounds__(kThreads) void rel_stats_count(const long long* __r
     const int mid = (lo + hi) >> 1;
     if (rel_off[mid] <= i) lo = mid; else hi = mid;
   }
-  bool ok = rel_off[lo] <= i && i < rel_off[lo + 1];   // offsets that do not cover the row: not counted
-  const long long g0 = clamp_off(box_off[lo], G);
-  long long g1 = clamp_off(box_off[lo + 1], G);
-  if (g1 < g0) g1 = g0;
-  const long long n = g1 - g0;
+  const ImageRange im(rel_off, box_off, T, G, lo);
+  bool ok = im.r0 <= i && i < im.r1;   // offsets that do not cover the row: not counted (0 <= i < T, so clamping keeps this)
+  const long long g0 = im.g0, n = im.n_box();
   const long long s = rels[3 * i], o = rels[3 * i + 1], p = rels[3 * i + 2];
   ok = ok && s >= 0 && s < n && o >= 0 && o < n && p >= 0 && p < R;
   if (ok) {
@@ -68,10 +67,8 @@ extern "C" int egtr_rel_stats_i64(egtr_stream_t stream, const int64_t* rels, con
   if (!rels || !rel_offsets || !box_offsets || !counts || !status || (num_boxes > 0 && !classes)) return EGTR_E_ARG;
   if ((num_rels + kThreads - 1) / kThreads >= (1ll << 31)) return EGTR_E_UNSUPPORTED;
   hipLaunchKernelGGL(rel_stats_count, dim3((unsigned)((num_rels + kThreads - 1) / kThreads)), dim3(kThreads), 0,
-                     static_cast<hipStream_t>(stream), reinterpret_cast<const long long*>(rels),
-                     reinterpret_cast<const long long*>(rel_offsets), num_rels,
-                     reinterpret_cast<const long long*>(classes), reinterpret_cast<const long long*>(box_offsets),
-                     num_boxes, batch, num_classes, num_rel, reinterpret_cast<unsigned long long*>(counts),
+                     static_cast<hipStream_t>(stream), rels, rel_offsets, num_rels, classes, box_offsets, num_boxes,
+                     batch, num_classes, num_rel, reinterpret_cast<unsigned long long*>(counts),
                      reinterpret_cast<unsigned*>(status));
   return egtr_check_launch();
 }

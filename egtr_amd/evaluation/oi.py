@@ -277,7 +277,7 @@ class OpenImagesRelationMetrics(FlatAccumulator):
                 tp_out[:, b, :K] = oi_tp_host(sop, boxes, classes, g["gt_relations"], g["gt_boxes"],
                                               g["gt_classes"]).to(torch.uint8)
                 valid[b, :K] = True
-        for r in rows:          # image order, like oi_fold
+        for r in rows:          # image order, like eval_fold
             acc.add_(r)
         self._batches.append((p_out, s_out, tp_out, valid))
         self.last_detections = dets

@@ -212,7 +212,7 @@ class SceneGraphRecall(FlatAccumulator):
             rows.append(self._image_row(fr, g["gt_relations"], rels.shape[0]))
             if zs_acc is not None:
                 zs_rows.append(self._zero_shot_row(fr, g, rels.shape[0]))
-        for r in rows:          # image order, like sgg_fold
+        for r in rows:          # image order, like eval_fold
             acc.add_(r)
         for r in zs_rows:
             zs_acc.add_(r)

@@ -1,5 +1,6 @@
 """GPU: the Open Images relation metrics on the device (csrc/oi_eval.hip) -- the reference fixture bit for bit, the
-selection against the torch composition at the configs[3] shape, no synchronisation inside update, evaluate(oi=True)."""
+selection against the torch composition at the configs[3] shape and where the top-`topk` boundary falls inside a tie,
+between adjacent floats or beyond the survivors, no synchronisation inside update, evaluate(oi=True)."""
 import json
 import os
 import sys
@@ -107,6 +108,87 @@ def test_select_equals_torch_at_config3_shape(B):
     assert set(got) == set(want)
     for k, v in want.items():
         assert abs(got[k] - v) <= 1e-12, (k, got[k], v)
+
+
+_BN, _BR, _BKK = 24, 6, 2      # 576 pairs: two partial blocks of 512, so the merge pass sees two lists
+
+
+def _boundary_scores(case):
+    """pred_scores [576, 6] whose per-pair top-2 values (the pair-major [M, 2] array the selection ranks) are placed by
+    ``case``; object scores are 1, so spo is the value itself."""
+    M, below = _BN * _BN, np.float32(np.nextafter(np.float32(0.5), np.float32(0)))
+    if case == "full_tie":                         # the whole list ties: the index half of the key decides
+        return torch.full((M, _BR), 0.5)
+    rng = np.random.Generator(np.random.PCG64({"adjacent": 1, "few": 2, "exact": 3}[case]))
+    if case == "adjacent":                         # 100 at 0.5, 100 at the float below, the rest far below
+        vals, fill = np.full(M * _BKK, 0.25, np.float32), 0.125
+        pos = rng.permutation(M * _BKK)[:200]
+        vals[pos[:100]], vals[pos[100:]] = 0.5, below
+    else:                                          # 7 or exactly 100 survivors of the > 1e-5 cut, equal values among them
+        n = 7 if case == "few" else 100
+        vals, fill = np.full(M * _BKK, 1e-6, np.float32), 0.0
+        vals[rng.permutation(M * _BKK)[:n]] = (0.2 + 0.7 * rng.integers(0, max(n // 2, 4), n) / n).astype(np.float32)
+    vals = -np.sort(-vals.reshape(M, _BKK), axis=1)                    # a pair's best predicate comes first
+    rows = np.full((M, _BR), fill, np.float32)
+    for m in range(M):                                                 # equal values: the lower predicate index is first
+        a, b = np.sort(rng.choice(_BR, 2, replace=False))
+        if vals[m, 0] != vals[m, 1] and rng.random() < 0.5:
+            a, b = b, a
+        rows[m, a], rows[m, b] = vals[m, 0], vals[m, 1]
+    return torch.from_numpy(rows)
+
+
+@pytest.fixture(scope="module")
+def boundary():
+    """{case: (pred_scores, {topk: (sop, score) of oi_select_host})}: the host's stable sort defines the tie order."""
+    obj = torch.ones(_BN)
+    pairs = torch.cartesian_prod(torch.arange(_BN), torch.arange(_BN))
+    out = {}
+    for case in ("full_tie", "adjacent", "few", "exact"):
+        ps = _boundary_scores(case)
+        out[case] = (ps, {k: oi_select_host(ps, obj, pairs, k, _BKK) for k in (100, 101)})
+    return out
+
+
+def _select_on_device(score_list, topk):
+    rel = torch.zeros(2, 2, _BR)
+    rel[0, 1, 0] = 1
+    target = {"class_labels": torch.zeros(2, dtype=torch.long), "boxes": torch.full((2, 4), 0.25), "rel": rel,
+              "orig_size": torch.tensor([64, 64])}
+    cands = [{"pred_boxes": torch.zeros(_BN, 4, device=DEV), "pred_classes": torch.zeros(_BN, dtype=torch.long, device=DEV),
+              "obj_scores": torch.ones(_BN, device=DEV), "pred_scores": ps.to(DEV)} for ps in score_list]
+    ev = OpenImagesRelationMetrics(_BR, topk=topk, prd_k=_BKK)
+    ev.update(cands, [target] * len(cands))
+    return [x.cpu() for x in ev.last_detections]
+
+
+@pytest.mark.parametrize("case,topk", [("full_tie", 100), ("adjacent", 100), ("adjacent", 101), ("few", 100),
+                                       ("exact", 100)])
+def test_select_boundaries_equal_host(boundary, case, topk):
+    names = list(boundary)
+    other = names[(names.index(case) + 1) % len(names)]
+    want = {c: boundary[c][1][topk] for c in (case, other)}
+    ps = {c: boundary[c][0] for c in (case, other)}
+    # the properties the cases were built for, on the host result that defines them
+    w_sop, w_score = want[case]
+    if case == "full_tie":
+        flat = torch.arange(100)
+        assert torch.equal(w_sop, torch.stack([flat // 2 // _BN, flat // 2 % _BN, flat % 2], 1)) and (w_score == 0.5).all()
+    elif case == "adjacent":
+        assert (w_score[:100] == 0.5).all() and w_score.shape[0] == topk
+        assert topk == 100 or w_score[100] == np.nextafter(np.float32(0.5), np.float32(0))
+    else:
+        assert w_score.shape[0] == (7 if case == "few" else 100) and (w_score[1:] <= w_score[:-1]).all()
+        assert len(torch.unique(w_score)) < w_score.shape[0]          # ties among the survivors
+    # alone, and next to another image on either side: an image's selection does not depend on its neighbour
+    for order in ((case,), (case, other), (other, case)):
+        sop, score, count = _select_on_device([ps[c] for c in order], topk)
+        for b, c in enumerate(order):
+            n = want[c][0].shape[0]
+            assert int(count[b]) == n, (order, b)
+            assert torch.equal(sop[b, :n].long(), want[c][0]), (order, b)
+            assert torch.equal(score[b, :n], want[c][1]), (order, b)
+            assert (sop[b, n:] == -1).all() and (score[b, n:] == 0).all(), (order, b)
 
 
 def test_shared_pairs_absent_and_stacked_inputs():

@@ -2,7 +2,8 @@
 egtr_amd.evaluation.vrd -- per-image recalls bit-equal to the reference's recorded VRD evaluators
 (tests/golden/vrd_eval.npz), first ranks index-exact and accumulators bit-equal to the host path, the hand-made images
 of vrd_eval_inputs.py, merge / batch-size independence, the zero-shot pass on the phrdet first ranks,
-runtime.matched_pair_candidates."""
+runtime.matched_pair_candidates, and the kernel's own answer to more GT relations than it keeps in LDS."""
+import ctypes
 import os
 import sys
 
@@ -14,10 +15,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "golden"))
 import vrd_eval_inputs as VI  # noqa: E402
 
+from egtr_amd import _lib  # noqa: E402
 from egtr_amd.deformable_detr import DeformableDetrHungarianMatcher  # noqa: E402
 from egtr_amd.evaluation import (PhraseDetectionRecall, PredicateDetectionRecall, SceneGraphRecall, gt_entry,  # noqa: E402
                                  phrase_first_ranks_host)
-from egtr_amd.kernels.vrd import NO_RANK  # noqa: E402
+from egtr_amd.kernels.vrd import NO_RANK, PREDDET_MAX_GT  # noqa: E402
 from egtr_amd.runtime import matched_pair_candidates  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -182,6 +184,48 @@ def test_preddet_ties_and_streaming_path_equal_host(K, R, G, T):
         assert torch.equal(got, want)
     assert (host.ranks[0] < NO_RANK).sum() > 10 and (host.ranks[0] != host.ranks[2]).any()
     assert torch.equal(ev.acc.cpu(), host.acc)
+
+
+def test_preddet_kernel_with_too_many_gt_relations():
+    """evaluation/vrd.py rejects an image with more than PREDDET_MAX_GT relations, so only a direct call reaches the
+    kernel's own answer: NaN recalls, correct counted / skipped / presence columns, NO_RANK and row 0 per triplet --
+    and the neighbouring image's row untouched."""
+    K, R, ks, n0 = 4, 3, (1, 2), PREDDET_MAX_GT + 1
+    nk = len(ks)
+    gen = torch.Generator().manual_seed(11)
+    pairs = torch.tensor([[[0, 1], [1, 2], [2, 0], [0, 1]], [[0, 1], [1, 2], [0, 1], [2, 0]]])
+    scores = torch.rand(2, K, R, generator=gen)
+    cyc = torch.tensor([[0, 1, 0], [1, 2, 2], [2, 0, 0]])        # three objects, predicates 0 and 2; predicate 1 is absent
+    rels0 = cyc[torch.arange(n0) % 3]
+    rels1 = torch.tensor([[0, 1, 1], [1, 2, 0]])
+
+    def launch(rels, sizes, lo, hi):
+        # the C entry itself, as ops.sgg_eval_preddet calls it, but into PREFILLED outputs: a row the kernel does not
+        # write keeps the 7 (ops allocates with torch.empty, where an unwritten chosen_row could happen to read 0)
+        off = torch.tensor([0] + sizes).cumsum(0).to(DEV)
+        box_off = (3 * torch.arange(len(sizes) + 1)).to(DEV)
+        T, d_rels = int(off[-1]), rels.to(DEV)
+        d_pairs, d_scores = pairs[lo:hi].to(DEV), scores[lo:hi].to(DEV)
+        slab = torch.full((hi - lo, nk + 2 + R * (nk + 1)), 7.0, dtype=torch.float64, device=DEV)
+        out = torch.full((3, T), 7, dtype=torch.int32, device=DEV)
+        _lib.launch("egtr_sgg_eval_preddet_f32", d_pairs.data_ptr(), d_scores.data_ptr(), hi - lo, K, R,
+                    d_rels.data_ptr(), off.data_ptr(), T, box_off.data_ptr(), 3 * len(sizes), (ctypes.c_int * nk)(*ks),
+                    nk, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), slab.data_ptr(), None)
+        return [slab.cpu()] + [x.cpu() for x in out]      # slab, chosen_row, first_rank, first_rank_pred
+
+    slab, rows, fr, fr_pred = launch(torch.cat([rels0, rels1]), [n0, 2], 0, 2)
+    alone = launch(rels1, [2], 1, 2)
+    bad, pbase, fbase = slab[0], nk + 2, nk + 2 + R * nk
+    assert bad[:nk].isnan().all()
+    assert bad[nk] == 1 and bad[nk + 1] == 0                    # counted, not skipped
+    for p, present in enumerate((True, False, True)):
+        cols = bad[pbase + p * nk:pbase + (p + 1) * nk]
+        assert cols.isnan().all() if present else (cols == 0).all()
+        assert bad[fbase + p] == (1.0 if present else 0.0)
+    assert (fr[:n0] == NO_RANK).all() and (fr_pred[:n0] == NO_RANK).all() and (rows[:n0] == 0).all()
+    assert torch.equal(slab[1], alone[0][0]) and not slab[1].isnan().any() and slab[1][nk] == 1
+    for got, want in zip((rows, fr, fr_pred), alone[1:]):
+        assert torch.equal(got[n0:], want)
 
 
 def test_phrdet_zero_shot_equals_host(inputs):
