@@ -155,7 +155,10 @@ def _rows(t, n_rows_per_image):
     if t.dim() == 3 and t.shape[0] > 1 and t.stride(0) == 0:
         t = t[0]
     t2 = t.reshape(-1, t.shape[-1])
-    t2 = t2 if (t2.is_contiguous() and t2.data_ptr() % 16 == 0) else t2.contiguous()
+    if not t2.is_contiguous():
+        t2 = t2.contiguous()
+    if t2.data_ptr() % 16:   # dense but cut at an odd offset (``contiguous()`` hands such a tensor back as it is): a fresh copy
+        t2 = t2.clone()
     return t2, t2.shape[0]
 
 
@@ -178,18 +181,23 @@ def run(decoder, hidden_states, position_embeddings, reference_input, values, va
     scale = float(lay0.scaling)
     # layer 0's projections: inputs are rows of the query table when both operands are batch expansions -> constants
     consts = [_layer_constants(l) for l in decoder.layers]
+    # rows of layer 0's projections: one image's when states AND positions are batch expansions, else every image's (the
+    # kernel takes q, k and v with ONE row count; expanded states under per-image positions used to be added to
+    # ``pos.repeat(0, 1)``, an empty tensor -- tests/test_gpu_decoder_layer.py, "rows-mixed")
+    rows0 = max(x_rows, pos_rows)
     with_pos0 = None
     if first_with_pos is not None:
         with_pos0, _ = _rows(first_with_pos, N)
-        if with_pos0.shape[0] != x_rows:
+        if with_pos0.shape[0] != rows0:
             with_pos0 = None
 
     def qkv0():
-        xp = with_pos0 if with_pos0 is not None else (x0 + (pos if pos_rows == x_rows else pos.repeat(x_rows // pos_rows, 1)))
+        xr = x0 if x_rows == rows0 else x0.repeat(rows0 // x_rows, 1)
+        xp = with_pos0 if with_pos0 is not None else xr + (pos if pos_rows == rows0 else pos.repeat(rows0 // pos_rows, 1))
         q, k, v = ops.linear_grouped([
             dict(x=xp, w=lay0.q_proj.weight, b=lay0.q_proj.bias, alpha=lay0.scaling),
             dict(x=xp, w=lay0.k_proj.weight, b=lay0.k_proj.bias),
-            dict(x=x0, w=lay0.v_proj.weight, b=lay0.v_proj.bias)])
+            dict(x=xr, w=lay0.v_proj.weight, b=lay0.v_proj.bias)])
         return q.contiguous(), k.contiguous(), v.contiguous()
 
     def base(t):
