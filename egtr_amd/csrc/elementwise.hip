@@ -879,35 +879,88 @@ __device__ __forceinline__ void load_group8(const float* x, size_t idx, float (&
 // (1) a workgroup sums 256 tokens of one level: thread = (group t & 31, token phase t >> 5), partial (sum, sum of squares) per
 //     group in double; (2) one wave per (image, level) adds the level's partials in order and writes (mean, rstd).
 constexpr int kGnTokChunk = 256;
-template <typename T>
-__global__ __launch_bounds__(256) void gn_partial_tokens(GnTokLevels P, int L, int chunks_total, double2* __restrict__ partial) {
+// SPLIT (fp32 only): level l arrives as S_l partial products [S_l][B * hw][256] (csrc/input_proj_x6.hip).  The slabs of a
+// (token, group) chunk are added in slab order 0, 1, ... -- a fixed order: two runs are bit-identical -- the sum is written back
+// into slab 0, which gn_apply_tokens then reads, and the statistics are those of sum + conv bias.  Every chunk is read and
+// written by one thread only.  A level with S_l = 1 takes the pass below as it stands (256 tokens per workgroup).  A split
+// level reads S_l times as much, so its workgroups take fewer tokens -- 32, 16 or 8 (gn_slab_chunk_tokens: a thread adds the
+// slabs of at most 4 tokens, eight slabs in flight at a time: at most 5 dependent rounds of loads; with 256 tokens the
+// one workgroup of the bench's extra level, 36 slabs, walked 144 rounds: 237 us) -- and gn_finalize_tokens adds more partials.
+struct GnTokSlabs {
+  int S[4], ctok[4];     // slabs and tokens per workgroup of a level
+  long long stride[4];   // floats between two slabs of a level: B * hw * 256
+};
+__host__ __device__ inline int gn_slab_chunk_tokens(int S) { return S <= 1 ? 256 : S <= 8 ? 32 : S <= 16 ? 16 : 8; }
+template <typename T, bool SPLIT = false>
+__global__ __launch_bounds__(256) void gn_partial_tokens(GnTokLevels P, int L, int chunks_total, double2* __restrict__ partial,
+                                                         GnTokSlabs SL = GnTokSlabs{}) {
   __shared__ double s_red[2][32][9];
   const int b = blockIdx.y;
   int l = 0;
   while (l + 1 < L && (int)blockIdx.x >= P.cchunk0[l + 1]) ++l;
-  const int t_begin = ((int)blockIdx.x - P.cchunk0[l]) * kGnTokChunk, hw = P.hw[l];
+  const int hw = P.hw[l];
   const int g = threadIdx.x & 31, ph = threadIdx.x >> 5;
   const T* x = static_cast<const T*>(P.x[l]) + (size_t)b * hw * 256;
   const float4 ba = *reinterpret_cast<const float4*>(P.conv_bias[l] + 8 * g), bb = *reinterpret_cast<const float4*>(P.conv_bias[l] + 8 * g + 4);
   const float cb[8] = {ba.x, ba.y, ba.z, ba.w, bb.x, bb.y, bb.z, bb.w};
   float s1 = 0.f, s2 = 0.f;
+  bool summed = false;
+  if constexpr (SPLIT) {
+    const int ns = SL.S[l];
+    if (ns > 1) {   // uniform per workgroup
+      summed = true;
+      const int ct = SL.ctok[l], t0 = ((int)blockIdx.x - P.cchunk0[l]) * ct;
+      const size_t stride = (size_t)SL.stride[l];
+      for (int j = 0; j < ct / 8; ++j) {
+        const int t = t0 + ph + 8 * j;
+        if (t >= hw) break;
+        const size_t idx = (size_t)t * 32 + g;
+        float f[8];
+        load_group8(x, idx, f);
+        for (int sl0 = 1; sl0 < ns; sl0 += 8) {
+          float h[8][8];
 #pragma unroll
-  for (int u0 = 0; u0 < kGnTokChunk / 8; u0 += 8) {
-    float f[8][8];
+          for (int q = 0; q < 8; ++q)
+            if (sl0 + q < ns) load_group8(x + (size_t)(sl0 + q) * stride, idx, h[q]);
 #pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const int t = t_begin + ph + 8 * (u0 + u);
-      if (t < hw) load_group8(x, (size_t)t * 32 + g, f[u]);
-    }
+          for (int q = 0; q < 8; ++q)
+            if (sl0 + q < ns) {
 #pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const int t = t_begin + ph + 8 * (u0 + u);
-      if (t < hw) {
+              for (int k = 0; k < 8; ++k) f[k] += h[q][k];
+            }
+        }
+        float4* dst = reinterpret_cast<float4*>(const_cast<T*>(x)) + 2 * idx;
+        dst[0] = make_float4(f[0], f[1], f[2], f[3]);
+        dst[1] = make_float4(f[4], f[5], f[6], f[7]);
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
-          const float v = f[u][k] + cb[k];
+          const float v = f[k] + cb[k];
           s1 += v;
           s2 += v * v;
+        }
+      }
+    }
+  }
+  if (!summed) {
+    const int t_begin = ((int)blockIdx.x - P.cchunk0[l]) * kGnTokChunk;
+#pragma unroll
+    for (int u0 = 0; u0 < kGnTokChunk / 8; u0 += 8) {
+      float f[8][8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int t = t_begin + ph + 8 * (u0 + u);
+        if (t < hw) load_group8(x, (size_t)t * 32 + g, f[u]);
+      }
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int t = t_begin + ph + 8 * (u0 + u);
+        if (t < hw) {
+#pragma unroll
+          for (int k = 0; k < 8; ++k) {
+            const float v = f[u][k] + cb[k];
+            s1 += v;
+            s2 += v * v;
+          }
         }
       }
     }
@@ -994,9 +1047,12 @@ __global__ __launch_bounds__(256) void gn_apply_tokens(GnTokLevels P, int L, int
 }
 }  // namespace
 
-static int gn_tokens_chunks(int num_levels, const int* level_tokens) {
+static int gn_tokens_chunks(int num_levels, const int* level_tokens, const int* splits = nullptr) {
   int c = 0;
-  for (int l = 0; l < num_levels; ++l) c += (level_tokens[l] + kGnTokChunk - 1) / kGnTokChunk;
+  for (int l = 0; l < num_levels; ++l) {
+    const int ct = splits ? gn_slab_chunk_tokens(splits[l]) : kGnTokChunk;
+    c += (level_tokens[l] + ct - 1) / ct;
+  }
   return c;
 }
 
@@ -1008,7 +1064,8 @@ extern "C" long long egtr_input_proj_groupnorm_tokens_workspace_floats(int num_l
 
 static int groupnorm_tokens_launch(egtr_stream_t stream, int num_levels, const void* const* x, const float* const* conv_bias,
                                    const float* const* gamma, const float* const* beta, const int* level_tokens, int batch,
-                                   int channels, int num_groups, float eps, float* stats, void* out, bool bf16) {
+                                   int channels, int num_groups, float eps, float* stats, void* out, bool bf16,
+                                   const int* splits = nullptr) {
   if (!x || !conv_bias || !gamma || !beta || !level_tokens || !stats || !out) return EGTR_E_ARG;
   if (num_levels < 1 || num_levels > 4 || batch <= 0) return EGTR_E_ARG;
   if (channels != 256 || num_groups != 32) return EGTR_E_UNSUPPORTED;
@@ -1027,8 +1084,9 @@ static int groupnorm_tokens_launch(egtr_stream_t stream, int num_levels, const v
     P.chunk0[l] = (long long)S * 32;
     P.cchunk0[l] = cc;
     if (l < num_levels) {
+      const int ct = splits ? gn_slab_chunk_tokens(splits[l]) : kGnTokChunk;
       S += P.hw[l];
-      cc += (P.hw[l] + kGnTokChunk - 1) / kGnTokChunk;
+      cc += (P.hw[l] + ct - 1) / ct;
     }
   }
   P.chunk0[4] = (long long)S * 32;
@@ -1044,12 +1102,24 @@ static int groupnorm_tokens_launch(egtr_stream_t stream, int num_levels, const v
   const long long chunks = (long long)S * 32;
   const dim3 agrid((unsigned)((chunks + 255) / 256), batch);
   if (bf16) {
-    hipLaunchKernelGGL(gn_partial_tokens<unsigned short>, dim3(cc, batch), dim3(256), 0, st, P, num_levels, cc, partial);
+    hipLaunchKernelGGL(gn_partial_tokens<unsigned short>, dim3(cc, batch), dim3(256), 0, st, P, num_levels, cc, partial,
+                       GnTokSlabs{});
     hipLaunchKernelGGL(gn_finalize_tokens, dim3(batch, num_levels), dim3(256), 0, st, P, cc, eps, partial, st2);
     hipLaunchKernelGGL(gn_apply_tokens<unsigned short>, agrid, dim3(256), 0, st, P, num_levels, S, st2,
                        static_cast<unsigned short*>(out));
+  } else if (splits != nullptr) {
+    GnTokSlabs SL = {};
+    for (int l = 0; l < num_levels; ++l) {
+      if (splits[l] < 1) return EGTR_E_ARG;
+      SL.S[l] = splits[l];
+      SL.ctok[l] = gn_slab_chunk_tokens(splits[l]);
+      SL.stride[l] = (long long)batch * level_tokens[l] * 256;
+    }
+    hipLaunchKernelGGL((gn_partial_tokens<float, true>), dim3(cc, batch), dim3(256), 0, st, P, num_levels, cc, partial, SL);
+    hipLaunchKernelGGL(gn_finalize_tokens, dim3(batch, num_levels), dim3(256), 0, st, P, cc, eps, partial, st2);
+    hipLaunchKernelGGL(gn_apply_tokens<float>, agrid, dim3(256), 0, st, P, num_levels, S, st2, static_cast<float*>(out));
   } else {
-    hipLaunchKernelGGL(gn_partial_tokens<float>, dim3(cc, batch), dim3(256), 0, st, P, num_levels, cc, partial);
+    hipLaunchKernelGGL(gn_partial_tokens<float>, dim3(cc, batch), dim3(256), 0, st, P, num_levels, cc, partial, GnTokSlabs{});
     hipLaunchKernelGGL(gn_finalize_tokens, dim3(batch, num_levels), dim3(256), 0, st, P, cc, eps, partial, st2);
     hipLaunchKernelGGL(gn_apply_tokens<float>, agrid, dim3(256), 0, st, P, num_levels, S, st2, static_cast<float*>(out));
   }
@@ -1070,6 +1140,24 @@ extern "C" int egtr_input_proj_groupnorm_tokens_f32(egtr_stream_t stream, int nu
                                                     int channels, int num_groups, float eps, float* stats, float* out) {
   return groupnorm_tokens_launch(stream, num_levels, reinterpret_cast<const void* const*>(x), conv_bias, gamma, beta,
                                  level_tokens, batch, channels, num_groups, eps, stats, out, false);
+}
+
+extern "C" long long egtr_input_proj_groupnorm_token_slabs_workspace_floats(int num_levels, const int* level_tokens,
+                                                                            const int* splits, int batch) {
+  if (!level_tokens || !splits || num_levels < 1 || num_levels > 4 || batch <= 0) return 0;
+  for (int l = 0; l < num_levels; ++l)
+    if (splits[l] < 1 || level_tokens[l] <= 0) return 0;
+  return (long long)num_levels * batch * 64 + (long long)batch * gn_tokens_chunks(num_levels, level_tokens, splits) * 128;
+}
+
+extern "C" int egtr_input_proj_groupnorm_token_slabs_f32(egtr_stream_t stream, int num_levels, float* const* slabs,
+                                                         const int* splits, const float* const* conv_bias,
+                                                         const float* const* gamma, const float* const* beta,
+                                                         const int* level_tokens, int batch, int channels, int num_groups,
+                                                         float eps, float* stats, float* out) {
+  if (!splits) return EGTR_E_ARG;
+  return groupnorm_tokens_launch(stream, num_levels, reinterpret_cast<const void* const*>(slabs), conv_bias, gamma, beta,
+                                 level_tokens, batch, channels, num_groups, eps, stats, out, false, splits);
 }
 
 extern "C" int egtr_input_proj_groupnorm_flatten_f32(egtr_stream_t stream, int num_levels, const float* const* x,

@@ -1338,20 +1338,27 @@ class DeformableDetrModel(DeformableDetrPreTrainedModel):
                 # channels-last backbone: a feature map IS its [B*H*W, C] token matrix, the 1x1 projection a plain GEMM
                 # whose output is already `flatten(2).transpose(1, 2)`; GroupNorm + concatenation without a transpose
                 toks, spatial_shapes_list = [], []
-                for level, fm in enumerate(feature_maps):
+                # fp32 inference: every level's projection in ONE grouped K-split launch, the K ranges summed by the GroupNorm
+                # statistics pass (csrc/input_proj_x6.hip); EGTR_GEMM_SPLIT_BF16=0 keeps the vendor products below
+                grouped = (len(self.input_proj) == len(feature_maps) + n_extra
+                           and ops.input_proj_x6_supported(feature_maps, self.input_proj))
+                if grouped:
+                    source_flatten, spatial_shapes_list = ops.input_proj_x6_groupnorm(feature_maps, self.input_proj)
+                for level, fm in enumerate(feature_maps if not grouped else ()):
                     c = self.input_proj[level][0]
                     b_, c_, h_, w_ = fm.shape
                     toks.append(torch.mm(fm.permute(0, 2, 3, 1).reshape(-1, c_), c.weight.detach().view(c.weight.shape[0], c_).t())
                                 .view(b_, h_ * w_, -1))
                     spatial_shapes_list.append((h_, w_))
-                if n_extra == 1:  # dd:2228-2241: the extra level is a strided 3x3 convolution of the last feature map
+                if n_extra == 1 and not grouped:  # dd:2228-2241: the extra level is a strided 3x3 convolution of the last feature map
                     c = self.input_proj[len(feature_maps)][0]
                     wcl = ops.cached_weights(c, "weight_channels_last", [c.weight],
                                              lambda: c.weight.detach().contiguous(memory_format=torch.channels_last))
                     y = F.conv2d(feature_maps[-1], wcl, None, c.stride, c.padding)
                     toks.append(y.permute(0, 2, 3, 1).reshape(y.shape[0], y.shape[2] * y.shape[3], y.shape[1]))
                     spatial_shapes_list.append(tuple(y.shape[-2:]))
-                source_flatten = ops.input_proj_groupnorm_tokens(toks, self.input_proj)
+                if not grouped:
+                    source_flatten = ops.input_proj_groupnorm_tokens(toks, self.input_proj)
             elif (n_extra <= 1 and self.config.d_model == 256 and feature_maps[0].dtype == pixel_values.dtype
                     and self.input_proj[0][0].weight.dtype == pixel_values.dtype
                     and all(isinstance(p[1], nn.GroupNorm) and p[0].bias is not None for p in self.input_proj)):

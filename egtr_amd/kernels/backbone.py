@@ -8,7 +8,7 @@ from .._lib import _chk
 
 __all__ = ["bias_relu_maxpool", "xs_bytes", "xs_split", "conv1x1_tail", "stem_weights", "stem_weights_bf16", "stem_fused_bf16",
            "stem_fused", "conv3x3_weights", "conv3x3", "conv1x1_strided", "conv_tail_pack_bf16", "conv1x1_tail_bf16",
-           "bias_act_rows_", "bias_act_"]
+           "bias_act_rows_", "bias_act_", "input_proj_x6_plan", "input_proj_x6_weights", "input_proj_x6"]
 
 
 def bias_relu_maxpool(x, bias):
@@ -211,3 +211,77 @@ def bias_act_(x, bias, residual=None, relu=True):
     _lib.launch("egtr_bias_act_nchw_f32", x.data_ptr(), bias.data_ptr(), _lib.ptr(residual), x.data_ptr(), N, C, H * W_,
                 1 if relu else 0)
     return x
+
+
+# ---- the input projections of all levels as one grouped, K-split launch (csrc/input_proj_x6.hip) ---------------------------------
+def input_proj_x6_plan(rows, K, tap_channels):
+    """(splits S_l per level, workspace floats) for levels of ``rows[l]`` output rows and reduction length ``K[l]``;
+    ``tap_channels[l]`` = C of a 3x3 / stride 2 level (K = 9 C), 0 of a plain one (egtr_input_proj_x6_workspace_floats: a function
+    of the shapes alone, no device needed).  Raises for shapes the kernel does not serve."""
+    import ctypes
+    L = len(rows)
+    IA = ctypes.c_int * L
+    splits = IA()
+    n = int(_lib.lib().egtr_input_proj_x6_workspace_floats(L, IA(*[int(v) for v in rows]), IA(*[int(v) for v in K]),
+                                                           IA(*[int(v) for v in tap_channels]), splits))
+    if n <= 0:
+        raise RuntimeError(f"input_proj_x6_plan: rows {list(rows)}, K {list(K)}, tap channels {list(tap_channels)} are not served")
+    return [int(v) for v in splits], n
+
+
+def input_proj_x6_weights(w):
+    """Conv2d weight [256, C, kh, kw] fp32 (1x1 or 3x3) -> the operand stream of the grouped kernel: the [256, kh kw C] matrix
+    laid out [n][dy][dx][c], split round-to-nearest and tiled like ``gemm_split_tile`` ([N/128][K/32][3 pieces][128][32] bf16)."""
+    w = w.detach()
+    N = w.shape[0]
+    wm = w.permute(0, 2, 3, 1).reshape(N, -1).contiguous()
+    out = torch.empty(N // 128, wm.shape[1] // 32, 3, 128, 32, dtype=torch.bfloat16, device=w.device)
+    _lib.launch("egtr_gemm_split_tile_weights_f32", wm.data_ptr(), wm.stride(0), 0, N, wm.shape[1], out.data_ptr())
+    return out
+
+
+def input_proj_x6(maps, w_tiled, strided3x3, splits=None, slabs=None):
+    """The bias-free input projections of all levels in ONE launch (egtr_input_proj_x6_f32).  Level l multiplies ``maps[l]``
+    (channels-last fp32 [B, C_l, H_l, W_l]) by ``w_tiled[l]`` (``input_proj_x6_weights``): a 1x1 convolution, or, where
+    ``strided3x3[l]``, a 3x3 / stride 2 / padding 1 convolution (the extra level, of the last feature map).  Returns (slabs,
+    splits, shapes): ``slabs[l]`` [S_l, B, H'_l W'_l, 256] fp32 partial products over the S_l ranges of K (their sum over dim
+    0 is the projection), ``shapes[l]`` = (H'_l, W'_l) of the output.  ``splits``: the plan's own when None; ``slabs``: the caller's buffers of exactly those shapes.
+    Inference only."""
+    import ctypes
+    L = len(maps)
+    if not (L == len(w_tiled) == len(strided3x3)):
+        raise ValueError("input_proj_x6: one weight and one kind per level")
+    B = maps[0].shape[0]
+    rows, Ks, tapc, geom, shapes = [], [], [], [], []
+    for fm, conv in zip(maps, strided3x3):
+        b, c, h, w = fm.shape
+        if (not fm.is_cuda or fm.dtype != torch.float32 or b != B or not fm.is_contiguous(memory_format=torch.channels_last)
+                or fm.data_ptr() % 16):
+            raise RuntimeError("input_proj_x6: channels-last float32 device feature maps, 16-byte aligned")
+        if conv:
+            ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+            rows.append(b * ho * wo)
+            Ks.append(9 * c)
+            tapc.append(c)
+            geom += [b, h, w, c]
+            shapes.append((ho, wo))
+        else:
+            rows.append(b * h * w)
+            Ks.append(c)
+            tapc.append(0)
+            geom += [0, 0, 0, 0]
+            shapes.append((h, w))
+    for l in range(L):
+        if w_tiled[l].numel() != 3 * 256 * Ks[l] or w_tiled[l].dtype != torch.bfloat16:
+            raise ValueError(f"input_proj_x6: weight stream {l} is not that of a [256, {Ks[l]}] matrix")
+    plan, _ = input_proj_x6_plan(rows, Ks, tapc)
+    splits = plan if splits is None else [int(v) for v in splits]
+    want = [(splits[l], B, rows[l] // B, 256) for l in range(L)]
+    if slabs is None:
+        slabs = [torch.empty(w, dtype=torch.float32, device=maps[0].device) for w in want]
+    elif [tuple(t.shape) for t in slabs] != want or any(t.dtype != torch.float32 or not t.is_contiguous() for t in slabs):
+        raise ValueError(f"input_proj_x6: slabs must be contiguous float32 tensors of shapes {want}")
+    PA, IA = ctypes.c_void_p * L, ctypes.c_int * L
+    _lib.launch("egtr_input_proj_x6_f32", L, PA(*[x.data_ptr() for x in maps]), PA(*[w.data_ptr() for w in w_tiled]),
+                PA(*[s.data_ptr() for s in slabs]), IA(*rows), IA(*Ks), (ctypes.c_int * (4 * L))(*geom), IA(*splits), 256)
+    return slabs, splits, shapes

@@ -10,7 +10,7 @@ from .derived import cached_weights
 
 __all__ = ["dropout_add_layernorm", "dropout_add_layernorm_backward", "add_layer_norm_into", "box_decode", "bias_mask_rows_",
            "add_layer_norm_pos", "scale_rows_multi", "sine_position_embedding", "input_proj_groupnorm_flatten",
-           "input_proj_groupnorm_tokens", "level_geometry"]
+           "input_proj_groupnorm_tokens", "input_proj_groupnorm_token_slabs", "level_geometry"]
 
 
 def dropout_add_layernorm(x, residual, keep, scale, weight, bias, eps, flag=None):
@@ -243,6 +243,34 @@ def input_proj_groupnorm_tokens(token_outputs, input_projs):
     _lib.launch(entry, L, PA(*[x.data_ptr() for x in xs]), PA(*[k[0].data_ptr() for k in keep]),
                 PA(*[k[1].data_ptr() for k in keep]), PA(*[k[2].data_ptr() for k in keep]), IA(*toks), B, 256, 32,
                 float(gn0.eps), stats.data_ptr(), out.data_ptr())
+    return out
+
+
+def input_proj_groupnorm_token_slabs(slabs, input_projs):
+    """``input_proj_groupnorm_tokens`` on K-split partial products (egtr_input_proj_groupnorm_token_slabs_f32): ``slabs[l]`` is
+    [S_l, B, H_l*W_l, 256] fp32 (``input_proj_x6``).  The statistics pass adds the slabs in order and leaves the sum in
+    ``slabs[l][0]`` (the argument is MODIFIED); with S_l = 1 this is ``input_proj_groupnorm_tokens``.  Returns [B, S, 256]."""
+    import ctypes
+    lib = _lib.lib()
+    L = len(slabs)
+    B = slabs[0].shape[1]
+    gn0 = input_projs[0][1]
+    xs = [_chk(x, "slabs", torch.float32) for x in slabs]
+    for proj, x in zip(input_projs[:L], xs):
+        conv, gn = proj[0], proj[1]
+        if gn.num_groups != 32 or gn.eps != gn0.eps or conv.bias is None or x.dim() != 4 or x.shape[-1] != 256 or x.shape[1] != B:
+            raise ValueError("input_proj_groupnorm_token_slabs: [S, B, tokens, 256] slabs, 32 groups, one GroupNorm configuration")
+    srcs = [t for proj in input_projs[:L] for t in (proj[0].bias, proj[1].weight, proj[1].bias)]
+    flat = cached_weights(input_projs, "gn_params_f32", srcs, lambda: [t.detach().float().contiguous() for t in srcs])
+    keep = [tuple(flat[3 * l:3 * l + 3]) for l in range(L)]
+    toks = [int(x.shape[2]) for x in xs]
+    out = torch.empty(B, sum(toks), 256, dtype=torch.float32, device=xs[0].device)
+    PA, IA = ctypes.c_void_p * L, ctypes.c_int * L
+    splits = IA(*[int(x.shape[0]) for x in xs])
+    stats = torch.empty(int(lib.egtr_input_proj_groupnorm_token_slabs_workspace_floats(L, IA(*toks), splits, B)),
+                        dtype=torch.float32, device=xs[0].device)
+    _lib.launch("egtr_input_proj_groupnorm_token_slabs_f32", L, PA(*[x.data_ptr() for x in xs]), splits, PA(*[k[0].data_ptr() for k in keep]), PA(*[k[1].data_ptr() for k in keep]),
+                PA(*[k[2].data_ptr() for k in keep]), IA(*toks), B, 256, 32, float(gn0.eps), stats.data_ptr(), out.data_ptr())
     return out
 
 

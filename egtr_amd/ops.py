@@ -866,7 +866,8 @@ def decoder_layer_train(layer, x, pos, ref, value, spatial_shapes, level_start_i
 #   EGTR_GEMM_SPLIT_BF16=0      ops.GEMM_SPLIT_BF16         token-sized linears: split-bf16 matrix cores  ->  vendor fp32 GEMM; also the
 #                                                           fp32 backbone's own split-bf16 kernels (stem, 3x3 convolutions, bottleneck
 #                                                           tails: backbone.STEM_FUSED / CONV2_X6 / CONV3_FUSED / CONV1_X6)  ->  MIOpen /
-#                                                           vendor GEMM + passes
+#                                                           vendor GEMM + passes; and the grouped input projections
+#                                                           (input_proj_x6_groupnorm)  ->  vendor GEMMs + MIOpen
 #   EGTR_REL_HEAD_SPLIT_BF16=0  ops.REL_HEAD_SPLIT_BF16     relation head at inference: split-bf16  ->  exact-f32 MFMA kernel
 #   EGTR_FFN_FUSED=0            ops.FFN_FUSED               encoder FFN / layer tail row-panel kernels  ->  separate launches
 #   EGTR_BACKBONE_NHWC=0        backbone.NHWC_F32 / _BF16   inference backbone channels-last  ->  NCHW
@@ -935,6 +936,45 @@ def gemm_split_supported(x, N, K):
                 and rows >= GEMM_SPLIT_MIN_ROWS)
     return _gate("gemm_split", eligible, eligible and K % 32 == 0 and N % 128 == 0,
                  lambda: f"{rows} x {K} -> {N}: K must be a multiple of 32 and N of 128 (vendor GEMM instead)")
+
+
+def input_proj_x6_supported(feature_maps, input_proj):
+    """Shapes the grouped input-projection launch serves (csrc/input_proj_x6.hip): fp32 inference with the split-bf16 products
+    on, channels-last fp32 feature maps whose channel counts are multiples of 32, at most four levels of Conv2d -> 256 channels:
+    a 1x1 / stride 1 convolution per map and at most one extra level, 3x3 / stride 2 / padding 1 of the last map."""
+    maps = list(feature_maps)
+    L = len(input_proj)
+    eligible = (GEMM_SPLIT_BF16 and len(maps) > 0 and not torch.is_grad_enabled()
+                and all(fm.is_cuda and fm.dtype == torch.float32 for fm in maps)
+                and all(p[0].weight.dtype == torch.float32 for p in input_proj))
+    if not eligible:
+        return False
+
+    def conv_ok(c, k, s, p):
+        return (tuple(c.kernel_size) == (k, k) and tuple(c.stride) == (s, s) and tuple(c.padding) == (p, p)
+                and tuple(c.dilation) == (1, 1) and c.groups == 1 and c.out_channels == 256 and c.in_channels % 32 == 0)
+    ok = (len(maps) <= L <= min(len(maps) + 1, 4)
+          and all(fm.dim() == 4 and fm.is_contiguous(memory_format=torch.channels_last) and fm.data_ptr() % 16 == 0
+                  and fm.shape[0] == maps[0].shape[0] for fm in maps)
+          and all(conv_ok(input_proj[l][0], 1, 1, 0) and input_proj[l][0].in_channels == maps[l].shape[1]
+                  for l in range(len(maps)))
+          and (L == len(maps) or (conv_ok(input_proj[L - 1][0], 3, 2, 1)
+                                  and input_proj[L - 1][0].in_channels == maps[-1].shape[1])))
+    return _gate("input_proj_x6", True, ok,
+                 lambda: f"maps {[tuple(fm.shape) for fm in maps]}: channels-last, channels a multiple of 32, 1x1 projections to "
+                         "256 channels and at most one 3x3 / stride 2 extra level are served (vendor products instead)")
+
+
+def input_proj_x6_groupnorm(feature_maps, input_proj):
+    """Input projections + conv bias + GroupNorm(32) + concatenation of all levels in four launches: the grouped K-split product
+    (``input_proj_x6``) and the token GroupNorm whose statistics pass sums the K ranges.  Returns ([B, S, 256], [(H_l, W_l)])."""
+    L = len(input_proj)
+    wts = [cached_weights(input_proj[l][0], "input_proj_x6_weights", [input_proj[l][0].weight],
+                          lambda l=l: input_proj_x6_weights(input_proj[l][0].weight)) for l in range(L)]
+    maps = list(feature_maps)
+    extra = L - len(maps)
+    slabs, _, shapes = input_proj_x6(maps + maps[-1:] * extra, wts, [False] * len(maps) + [True] * extra)
+    return input_proj_groupnorm_token_slabs(slabs, input_proj), shapes
 
 
 def conv1x1_tail_supported(a, N):

@@ -712,6 +712,35 @@ int egtr_input_proj_groupnorm_tokens_f32(egtr_stream_t stream, int num_levels, c
                                          const int* level_tokens, int batch, int channels, int num_groups, float eps,
                                          float* stats, float* out);   /* fp32 twin */
 
+/* ---- input projections of all levels as one grouped, K-split launch (csrc/input_proj_x6.hip) -------------- */
+/* Level l is a bias-free product [rows[l], K[l]] x W_l^T -> 256 channels with the six-term split-bf16 arithmetic of
+ * egtr_linear_split_bf16_f32; w_tiled[l] is egtr_gemm_split_tile_weights_f32 of the [256, K[l]] weight matrix.
+ *   plain level (conv_geometry[4 l + 3] == 0, or conv_geometry NULL): x[l] is the [rows, K] token matrix of a channels-last
+ *     feature map (a 1x1 convolution);
+ *   3x3 / stride 2 / padding 1 level: conv_geometry[4 l ..] = {B, H, W, C}, x[l] the channels-last map [B, H, W, C],
+ *     K[l] = 9 C with the weight matrix laid out [n][dy][dx][c], rows[l] = B ceil(H / 2) ceil(W / 2).
+ * K is cut into splits[l] equal ranges (each a multiple of 32); range s of level l writes its partial products to
+ * workspace[l] + s rows[l] 256 ([splits][rows][256] fp32, every in-range element written, no atomics).
+ * egtr_input_proj_groupnorm_token_slabs_f32 sums the slabs.
+ * egtr_input_proj_x6_workspace_floats: the plan for given shapes (HOST arrays; tap_channels[l] = C of a 3x3 level, 0 of a
+ * plain one, NULL = all plain): writes splits[l] and returns sum splits[l] rows[l] 256, 0 for shapes the kernel does not
+ * serve.  A function of its arguments alone (no device query).
+ * EGTR_E_UNSUPPORTED: N != 256, more than 4 levels, K or C not a multiple of 32, pointers not 16-byte aligned. */
+long long egtr_input_proj_x6_workspace_floats(int num_levels, const int* rows, const int* K, const int* tap_channels,
+                                              int* splits);
+int egtr_input_proj_x6_f32(egtr_stream_t stream, int num_levels, const float* const* x, const uint16_t* const* w_tiled,
+                           float* const* workspace, const int* rows, const int* K, const int* conv_geometry,
+                           const int* splits, int N);
+/* egtr_input_proj_groupnorm_tokens_f32 on such slabs: slabs[l] is [splits[l]][B, level_tokens[l], 256].  The statistics pass
+ * adds the slabs of an element in slab order (bit-reproducible), writes the sum into slab 0 (slabs[l] is MODIFIED) and
+ * accumulates the statistics of sum + conv bias; with splits[l] == 1 it is the pass of the entry above, bit for bit. */
+long long egtr_input_proj_groupnorm_token_slabs_workspace_floats(int num_levels, const int* level_tokens, const int* splits,
+                                                                int batch);   /* floats of `stats` below */
+int egtr_input_proj_groupnorm_token_slabs_f32(egtr_stream_t stream, int num_levels, float* const* slabs, const int* splits,
+                                              const float* const* conv_bias, const float* const* gamma,
+                                              const float* const* beta, const int* level_tokens, int batch, int channels,
+                                              int num_groups, float eps, float* stats, float* out);
+
 /* ---- EGTR relation head ---------------------------------------------------------------------------------- */
 /* Inputs are the separable pieces of egtr.py:366-401 (see DESIGN.md "relation head algebra"):
  *   gate_q [B, N, T], gate_k [B, N, T]   : w_g[:d].q^[i,t]  and  w_g[d:].k^[j,t] + b_g      (T = Ld + 1 slots)
