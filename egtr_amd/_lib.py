@@ -34,6 +34,9 @@ SIGNATURES = {
     "egtr_msda_backward_f64": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P],
     "egtr_msda_backward_bf16": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
     "egtr_msda_backward_bf16_workspace_floats": [_I, _I, _I, _I, _I, _I, _I],
+    "egtr_msda_backward_det_workspace_bytes": [_I, _I, _I, _I],
+    "egtr_msda_backward_det_f32": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
+    "egtr_msda_backward_det_bf16": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
     "egtr_msda_forward_bf16": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "egtr_msda_forward_fused_bf16": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _I, _P, _P],
     "egtr_self_attn_forward_f32": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P],
@@ -112,6 +115,9 @@ SIGNATURES = {
     "egtr_relation_loss_f32": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, ctypes.c_float, _I, _I, _P, _P, _P, _P],
     "egtr_relation_loss_workspace_bytes": [_I, _I],
     "egtr_relation_loss_bits_f32": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, ctypes.c_float, _I, _I, _P, _P, _P, _P],
+    "egtr_relation_loss_det_workspace_bytes": [_I, _I],
+    "egtr_relation_loss_det_f32": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, ctypes.c_float, _I, _I, _P, _P, _P, _P],
+    "egtr_relation_loss_det_bits_f32": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, ctypes.c_float, _I, _I, _P, _P, _P, _P],
     "egtr_pack_relations_u64": [_P, _P, _P, _I, _I, _I, _I, _P],
     "egtr_rel_head_forward_bf16w": [_P] * 16 + [_I] * 6 + [_P] * 3,
     "egtr_ffn_layernorm_bf16": [_P] * 7 + [ctypes.c_float, _P, _I, _P, _P, _I, _I, _I],
@@ -168,6 +174,8 @@ _RESTYPES = {"egtr_status_string": ctypes.c_char_p, "egtr_last_hip_error": ctype
              "egtr_input_proj_x6_workspace_floats": ctypes.c_longlong,
              "egtr_input_proj_groupnorm_token_slabs_workspace_floats": ctypes.c_longlong,
              "egtr_msda_backward_bf16_workspace_floats": ctypes.c_longlong,
+             "egtr_msda_backward_det_workspace_bytes": ctypes.c_longlong,
+             "egtr_relation_loss_det_workspace_bytes": ctypes.c_longlong,
              "egtr_hungarian_match_scratch_doubles": ctypes.c_longlong,
              "egtr_relation_loss_workspace_bytes": ctypes.c_longlong,
              "egtr_column_sum_workspace_floats": ctypes.c_longlong,

@@ -288,15 +288,63 @@ __global__ __launch_bounds__(kLT) void rel_loss_find(ImgState* st, const unsigne
   }
 }
 
-// ---- final pass: loss terms, dense gradient, pair flags (target connectivity in query order) ---------------------------
+// ---- deterministic route, tie count: candidates EQUAL to the threshold key per (image, query row, problem) --------------------
+// The final pass of that route takes the need[prob] tied candidates with the LOWEST flat index (qa N + qb) R + r: the counts of
+// the rows in front of a row are the rank its first tied candidate starts at.  Integer counts: order-free.
 template <class Tgt>
+__global__ __launch_bounds__(kLT) void rel_loss_tie_count(const float* __restrict__ pred_rel, const Tgt target_rel, int N, int R,
+                                                          const ImgState* __restrict__ st, const int* __restrict__ tq,
+                                                          const unsigned char* __restrict__ mq, int* __restrict__ tiecnt) {
+  __shared__ int s_c[2];
+  const int b = blockIdx.y, tid = threadIdx.x;
+  const ImgState s = st[b];
+  const int* tq_b = tq + (size_t)b * N;
+  const unsigned char* mq_b = mq + (size_t)b * N;
+  const typename Tgt::Image rel = target_rel.image(b, N, R);
+  const float* pr = pred_rel + (size_t)b * N * N * R;
+  const int NR = N * R;
+  const float invR = 1.0f / (float)R;
+  for (int row = 0; row < kRowsPerWg; ++row) {
+    const int qa = blockIdx.x * kRowsPerWg + row;
+    if (qa >= N) break;
+    if (tid < 2) s_c[tid] = 0;
+    __syncthreads();
+    const bool ma = mq_b[qa] != 0;
+    const size_t trow = (size_t)tq_b[qa] * N;
+    int c0 = 0, c1 = 0;
+    for (int e = tid; e < NR; e += kLT) {
+      const int qb = (int)(((float)e + 0.5f) * invR);
+      const bool blk = ma && mq_b[qb];
+      const int prob = blk ? 0 : 1;
+      if (s.k[prob] <= 0) continue;
+      if (blk && !(rel.pair(trow + tq_b[qb]).at(e - qb * R) != 1.0f)) continue;
+      const bool tie = key_of(pr[(size_t)qa * NR + e]) == s.thr[prob];
+      c0 += (tie && blk) ? 1 : 0;
+      c1 += (tie && !blk) ? 1 : 0;
+    }
+    for (int o = 32; o > 0; o >>= 1) { c0 += __shfl_xor(c0, o); c1 += __shfl_xor(c1, o); }
+    if ((tid & 63) == 0) { atomicAdd(&s_c[0], c0); atomicAdd(&s_c[1], c1); }
+    __syncthreads();
+    if (tid < 2) tiecnt[((size_t)b * N + qa) * 2 + tid] = s_c[tid];
+    __syncthreads();
+  }
+}
+
+// ---- final pass: loss terms, dense gradient, pair flags (target connectivity in query order) ---------------------------
+// DET (deterministic route): candidates equal to the threshold key are taken by their rank in flat-index order -- the tied
+// candidates of the rows in front (tiecnt), of the earlier kLT-wide steps of this row (a running base: a step covers kLT
+// consecutive indices) and of the lower threads of this step (ballot + popcount) -- instead of by ticket; no ticket is drawn.
+template <class Tgt, bool DET = false>
 __global__ __launch_bounds__(kLT) void rel_loss_final(const float* __restrict__ pred_rel,
                                                       const Tgt target_rel, int N, int R,
                                                       ImgState* st, const int* __restrict__ tq,
                                                       const float* __restrict__ wq, const unsigned char* __restrict__ mq,
                                                       const int* __restrict__ total_sel, float* __restrict__ grad_rel,
-                                                      unsigned char* __restrict__ pairflag, double* __restrict__ partial) {
+                                                      unsigned char* __restrict__ pairflag, double* __restrict__ partial,
+                                                      const int* __restrict__ tiecnt) {
   __shared__ double s_red[kLT / 64];
+  __shared__ int s_wc[DET ? 2 : 1][kLT / 64][2];   // DET: tied candidates per wave of a step, double-buffered
+  __shared__ int s_base[2];                        // DET: tied candidates of the rows in front of this one
   const int b = blockIdx.y, tid = threadIdx.x;
   const ImgState s = st[b];
   const int* tq_b = tq + (size_t)b * N;
@@ -316,6 +364,68 @@ __global__ __launch_bounds__(kLT) void rel_loss_final(const float* __restrict__ 
     const bool ma = mq_b[qa] != 0;
     const size_t trow = (size_t)tq_b[qa] * N;
     const float wa = wq_b[qa];
+    if constexpr (DET) {
+      const int lane = tid & 63, wave = tid >> 6;
+      if (tid < 2) s_base[tid] = 0;
+      __syncthreads();
+      int b0 = 0, b1 = 0;
+      for (int r = tid; r < qa; r += kLT) {
+        b0 += tiecnt[((size_t)b * N + r) * 2 + 0];
+        b1 += tiecnt[((size_t)b * N + r) * 2 + 1];
+      }
+      for (int o = 32; o > 0; o >>= 1) { b0 += __shfl_xor(b0, o); b1 += __shfl_xor(b1, o); }
+      if (lane == 0) { atomicAdd(&s_base[0], b0); atomicAdd(&s_base[1], b1); }
+      __syncthreads();
+      int run0 = s_base[0], run1 = s_base[1];   // rank of the next tied candidate of problem 0 / 1
+      int par = 0;
+      for (int e0 = 0; e0 < NR; e0 += kLT) {    // every thread takes every step: the barrier below is uniform
+        const int e = e0 + tid;
+        const bool in = e < NR;
+        float t = 0.f, x = 0.f;
+        int qb = 0, mult = 0;
+        bool blk = false, tie = false;
+        if (in) {
+          qb = (int)(((float)e + 0.5f) * invR);
+          t = rel.pair(trow + tq_b[qb]).at(e - qb * R);
+          if (t != 0.f) pf[(size_t)qa * N + qb] = 1;
+          blk = ma && mq_b[qb];
+          x = pr[(size_t)qa * NR + e];
+          const int prob = blk ? 0 : 1;
+          if (blk && t != 0.f) mult = 1;
+          if ((!blk || t != 1.0f) && s.k[prob] > 0) {
+            const unsigned key = key_of(x);
+            if (key > s.thr[prob]) mult += 1;
+            else tie = key == s.thr[prob];
+          }
+        }
+        const unsigned long long m0 = __ballot(tie && blk), m1 = __ballot(tie && !blk);
+        if (lane == 0) {
+          s_wc[par][wave][0] = __popcll(m0);
+          s_wc[par][wave][1] = __popcll(m1);
+        }
+        __syncthreads();
+        const unsigned long long below = (1ull << lane) - 1ull;
+        int r0 = run0 + __popcll(m0 & below), r1 = run1 + __popcll(m1 & below);
+#pragma unroll
+        for (int w = 0; w < kLT / 64; ++w) {
+          const int c0 = s_wc[par][w][0], c1 = s_wc[par][w][1];
+          if (w < wave) { r0 += c0; r1 += c1; }
+          run0 += c0;
+          run1 += c1;
+        }
+        par ^= 1;
+        if (tie && (blk ? r0 < s.need[0] : r1 < s.need[1])) mult += 1;
+        if (in) {
+          float g = 0.f;
+          if (mult) {
+            const float y = t * (wa * wq_b[qb]);
+            acc += (double)((float)mult * bce_logits(x, y));
+            g = (float)mult * (1.0f / (1.0f + expf(-x)) - y) * inv_cnt;
+          }
+          gr[(size_t)qa * NR + e] = g;
+        }
+      }
+    } else
     for (int e = tid; e < NR; e += kLT) {
       const int qb = (int)(((float)e + 0.5f) * invR);
       const float t = rel.pair(trow + tq_b[qb]).at(e - qb * R);
@@ -424,6 +534,13 @@ extern "C" long long egtr_relation_loss_workspace_bytes(int batch, int num_query
   return bytes + 256;
 }
 
+// deterministic route: the same layout, followed by the tie counts int32 [batch, N, 2]
+extern "C" long long egtr_relation_loss_det_workspace_bytes(int batch, int num_query) {
+  const long long base = egtr_relation_loss_workspace_bytes(batch, num_query);
+  if (base <= 0) return 0;
+  return ((base + 15) / 16) * 16 + (long long)batch * num_query * 2 * 4;
+}
+
 // The launches of both entries.  pred_idx / tgt_idx / match_cost / out_offsets: the matcher's packed outputs
 // (egtr_hungarian_match_f32).  workspace: device, egtr_relation_loss_workspace_bytes() bytes, contents irrelevant (zeroed
 // here).  loss_out[0] = loss_rel, loss_out[1] = loss_connectivity; grad_rel [B,N,N,R] / grad_conn [B,N,N] = d loss / d logits.
@@ -432,7 +549,7 @@ static int relation_loss_launch(egtr_stream_t stream, const float* pred_rel, con
                                 const int64_t* pred_idx, const int64_t* tgt_idx, const float* match_cost,
                                 const int* out_offsets, int batch, int num_query, int num_rel, float nonmatching_cost,
                                 int sample_negatives, int sample_nonmatching, float* loss_out, float* grad_rel,
-                                float* grad_conn, void* workspace) {
+                                float* grad_conn, void* workspace, bool det = false) {
   if (!pred_rel || !pred_conn || !pred_idx || !tgt_idx || !match_cost || !out_offsets || !loss_out || !grad_rel ||
       !grad_conn || !workspace)
     return EGTR_E_ARG;
@@ -442,7 +559,9 @@ static int relation_loss_launch(egtr_stream_t stream, const float* pred_rel, con
   const long long B = batch, N = num_query;
   const int rows = (int)((N + kRowsPerWg - 1) / kRowsPerWg);
   const long long wsb = egtr_relation_loss_workspace_bytes(batch, num_query);
-  if (hipMemsetAsync(workspace, 0, (size_t)wsb, st) != hipSuccess) return EGTR_E_LAUNCH;
+  const long long wsb_all = det ? egtr_relation_loss_det_workspace_bytes(batch, num_query) : wsb;
+  if (hipMemsetAsync(workspace, 0, (size_t)wsb_all, st) != hipSuccess) return EGTR_E_LAUNCH;
+  int* tiecnt = reinterpret_cast<int*>(static_cast<char*>(workspace) + ((wsb + 15) / 16) * 16);   // det only
   char* p = static_cast<char*>(workspace);
   int* total_sel = reinterpret_cast<int*>(p);
   unsigned* done = reinterpret_cast<unsigned*>(p + 64);
@@ -475,8 +594,15 @@ static int relation_loss_launch(egtr_stream_t stream, const float* pred_rel, con
   hipLaunchKernelGGL((rel_loss_hist<2, Tgt>), gh, dim3(kLT), 0, st, pred_rel, target_rel, num_query, num_rel, state, tq, mq,
                      hist);
   hipLaunchKernelGGL(rel_loss_find<2>, gf, dim3(kLT), 0, st, state, hist);
-  hipLaunchKernelGGL(rel_loss_final<Tgt>, gh, dim3(kLT), 0, st, pred_rel, target_rel, num_query, num_rel, state, tq, wq, mq,
-                     total_sel, grad_rel, pairflag, partial_rel);
+  if (det) {
+    hipLaunchKernelGGL(rel_loss_tie_count<Tgt>, gh, dim3(kLT), 0, st, pred_rel, target_rel, num_query, num_rel, state, tq, mq,
+                       tiecnt);
+    hipLaunchKernelGGL((rel_loss_final<Tgt, true>), gh, dim3(kLT), 0, st, pred_rel, target_rel, num_query, num_rel, state, tq,
+                       wq, mq, total_sel, grad_rel, pairflag, partial_rel, (const int*)tiecnt);
+  } else {
+    hipLaunchKernelGGL(rel_loss_final<Tgt>, gh, dim3(kLT), 0, st, pred_rel, target_rel, num_query, num_rel, state, tq, wq, mq,
+                       total_sel, grad_rel, pairflag, partial_rel, (const int*)nullptr);
+  }
   const long long n_pairs = B * N * N;
   const int cblocks = (int)std::min<long long>((n_pairs + kLT - 1) / kLT, 1024);
   hipLaunchKernelGGL(conn_loss, dim3(cblocks), dim3(kLT), 0, st, pred_conn, pairflag, n_pairs, grad_conn, partial_conn,
@@ -511,6 +637,34 @@ extern "C" int egtr_relation_loss_bits_f32(egtr_stream_t stream, const float* pr
                               PackedTarget{reinterpret_cast<const unsigned long long*>(rel_bits)}, pred_idx, tgt_idx,
                               match_cost, out_offsets, batch, num_query, num_rel, nonmatching_cost, sample_negatives,
                               sample_nonmatching, loss_out, grad_rel, grad_conn, workspace);
+}
+
+// ---- deterministic entries: the same arguments, workspace of egtr_relation_loss_det_workspace_bytes().  Among the candidates
+// equal to the threshold key of an (image, problem) the `need` ones with the lowest flat index (qa N + qb) R + r are taken
+// (query order), one extra pass over pred_rel; everything else is the code of the entries above.
+extern "C" int egtr_relation_loss_det_f32(egtr_stream_t stream, const float* pred_rel, const float* pred_conn,
+                                          const float* const* target_rel, const int64_t* pred_idx, const int64_t* tgt_idx,
+                                          const float* match_cost, const int* out_offsets, int batch, int num_query,
+                                          int num_rel, float nonmatching_cost, int sample_negatives, int sample_nonmatching,
+                                          float* loss_out, float* grad_rel, float* grad_conn, void* workspace) {
+  if (!target_rel) return EGTR_E_ARG;
+  return relation_loss_launch(stream, pred_rel, pred_conn, DenseTarget{target_rel}, pred_idx, tgt_idx, match_cost,
+                              out_offsets, batch, num_query, num_rel, nonmatching_cost, sample_negatives,
+                              sample_nonmatching, loss_out, grad_rel, grad_conn, workspace, true);
+}
+
+extern "C" int egtr_relation_loss_det_bits_f32(egtr_stream_t stream, const float* pred_rel, const float* pred_conn,
+                                               const uint64_t* rel_bits, const int64_t* pred_idx, const int64_t* tgt_idx,
+                                               const float* match_cost, const int* out_offsets, int batch, int num_query,
+                                               int num_rel, float nonmatching_cost, int sample_negatives,
+                                               int sample_nonmatching, float* loss_out, float* grad_rel, float* grad_conn,
+                                               void* workspace) {
+  if (!rel_bits) return EGTR_E_ARG;
+  if (num_rel > 64) return EGTR_E_UNSUPPORTED;
+  return relation_loss_launch(stream, pred_rel, pred_conn,
+                              PackedTarget{reinterpret_cast<const unsigned long long*>(rel_bits)}, pred_idx, tgt_idx,
+                              match_cost, out_offsets, batch, num_query, num_rel, nonmatching_cost, sample_negatives,
+                              sample_nonmatching, loss_out, grad_rel, grad_conn, workspace, true);
 }
 
 // ---- detection losses of one output set (labels / boxes / cardinality, egtr:611-659, 661-670, 692-712) ------------------

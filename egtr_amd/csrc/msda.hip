@@ -26,6 +26,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "fixed_accum.h"
 #include "msda_common.h"
 
 namespace {
@@ -512,7 +513,10 @@ __device__ __forceinline__ float group8_sum(float v) {
 // BF: grad_out and value hold raw bfloat16 (the backward of a bf16 model): rows of 512 bytes instead of 1024 -- the record
 // offsets, built for the fp32 grad_value rows, are halved for the value gather -- widened on load; everything behind the loads
 // is the fp32 kernel (same instructions, same results as widening the operands first).
-template <bool VALUE_ATOMICS, int SPLIT = 1, bool BF = false>
+// DET (deterministic route, fixed_accum.h): `grad_value` is the int64 accumulator array of the deterministic workspace (rows of
+// 2048 bytes, the 64-byte header with the two maxima right in front of it); contributions are added as 64-bit fixed point with
+// integer atomics -- the same products, the same records, twice the byte offsets.  grad_loc / grad_attn are untouched by it.
+template <bool VALUE_ATOMICS, int SPLIT = 1, bool BF = false, bool DET = false>
 __global__ __launch_bounds__(kWaves * 64) void msda_bwd_q64_f32(
     const void* __restrict__ grad_out_, const void* __restrict__ value_, const int64_t* __restrict__ shapes,
     const int64_t* __restrict__ lsi, const float* __restrict__ loc, const float* __restrict__ attn,
@@ -536,7 +540,12 @@ __global__ __launch_bounds__(kWaves * 64) void msda_bwd_q64_f32(
   const int b = q / Lq;
   const size_t boff = (size_t)b * S * (256 * 4);
   const char* vbase = reinterpret_cast<const char*>(value_) + (BF ? boff / 2 : boff);
-  char* gvbase = reinterpret_cast<char*>(grad_value) + boff;
+  char* gvbase = reinterpret_cast<char*>(grad_value) + (DET ? boff * 2 : boff);
+  egtr_fixed::Scale fx = {0, false};
+  if constexpr (DET && VALUE_ATOMICS) {
+    const unsigned* hdr = reinterpret_cast<const unsigned*>(reinterpret_cast<const char*>(grad_value) - egtr_fixed::kHeaderBytes);
+    fx = egtr_fixed::make_scale(hdr[0], hdr[1], (unsigned long long)Lq * L * P);
+  }
   auto widen4 = [](uint2 u) {
     return make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16),
                        __uint_as_float(u.y & 0xffff0000u));
@@ -550,8 +559,15 @@ __global__ __launch_bounds__(kWaves * 64) void msda_bwd_q64_f32(
   const float2 aw = reinterpret_cast<const float2*>(attn + (size_t)q * 128)[lane];
   // encoder-shaped calls without atomics here (Lq == S, the value-tile kernel accumulates grad_value behind this launch): query q
   // clears row q of grad_value, 1 KiB per wave -- the caller's 51 MB zero-fill launch folded into this gather-bound kernel
-  if (!VALUE_ATOMICS && zero_value_rows)
-    reinterpret_cast<float4*>(gvbase + (size_t)(q - b * Lq) * 1024)[lane] = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (!VALUE_ATOMICS && zero_value_rows) {
+    if constexpr (DET) {   // the accumulator row: 2 KiB
+      float4* row = reinterpret_cast<float4*>(gvbase + (size_t)(q - b * Lq) * 2048);
+      row[lane] = make_float4(0.f, 0.f, 0.f, 0.f);
+      row[lane + 64] = make_float4(0.f, 0.f, 0.f, 0.f);
+    } else {
+      reinterpret_cast<float4*>(gvbase + (size_t)(q - b * Lq) * 1024)[lane] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+  }
   const int head_s = lane >> 3, s0 = (lane & 7) * 2;
   int4* my_off = s_off + wave * 128;
   float4* my_cf = s_cf + wave * 128 * 3;
@@ -609,10 +625,24 @@ __global__ __launch_bounds__(kWaves * 64) void msda_bwd_q64_f32(
         const int b2 = __float_as_int(r2.x);
         const float lh2 = r2.y, lw2 = r2.z, hh2 = 1.f - lh2, hw2 = 1.f - lw2;
         const float t2 = gs[h2 * 32 + ch] * r2.w;  // top = grad_out * attn (cuh:114)
+        if constexpr (DET) {
+          // one instruction covers 64 contiguous 8-byte accumulators = four 128-byte lines
+          auto add = [&](int off, float c) {
+            atomicAdd(reinterpret_cast<unsigned long long*>(gvbase + 2 * (size_t)(unsigned)off) + ch,
+                      (unsigned long long)egtr_fixed::to_fixed(c, fx.k));
+          };
+          if (!fx.poisoned) {
+            if (b2 & 1) add(o2.x, hh2 * hw2 * t2);
+            if (b2 & 2) add(o2.y, hh2 * lw2 * t2);
+            if (b2 & 4) add(o2.z, lh2 * hw2 * t2);
+            if (b2 & 8) add(o2.w, lh2 * lw2 * t2);
+          }
+        } else {
         if (b2 & 1) unsafeAtomicAdd(reinterpret_cast<float*>(gvbase + (unsigned)o2.x) + ch, hh2 * hw2 * t2);
         if (b2 & 2) unsafeAtomicAdd(reinterpret_cast<float*>(gvbase + (unsigned)o2.y) + ch, hh2 * lw2 * t2);
         if (b2 & 4) unsafeAtomicAdd(reinterpret_cast<float*>(gvbase + (unsigned)o2.z) + ch, lh2 * hw2 * t2);
         if (b2 & 8) unsafeAtomicAdd(reinterpret_cast<float*>(gvbase + (unsigned)o2.w) + ch, lh2 * lw2 * t2);
+        }
       }
     }
     const float4 cf = my_cf[e * 3 + which];
@@ -653,13 +683,19 @@ __global__ __launch_bounds__(kWaves * 64) void msda_bwd_q64_f32(
 }
 
 // Generic backward: one thread per (b,q,m,l,p) sample, loops over the D channels; atomics for grad_value.
-template <typename T>
+// DET: grad_value is the int64 accumulator array of the deterministic workspace (fixed_accum.h), fp32 operands only.
+template <typename T, bool DET = false>
 __global__ void msda_bwd_generic(const T* __restrict__ grad_out, const T* __restrict__ value,
                                      const int64_t* __restrict__ shapes, const int64_t* __restrict__ lsi,
                                      const T* __restrict__ loc, const T* __restrict__ attn,
                                      T* __restrict__ grad_value, T* __restrict__ grad_loc,
                                      T* __restrict__ grad_attn, long long n, int S, int M, int D, int L, int Lq,
                                      int P) {
+  egtr_fixed::Scale fx = {0, false};
+  if constexpr (DET) {
+    const unsigned* hdr = reinterpret_cast<const unsigned*>(reinterpret_cast<const char*>(grad_value) - egtr_fixed::kHeaderBytes);
+    fx = egtr_fixed::make_scale(hdr[0], hdr[1], (unsigned long long)Lq * L * P);
+  }
   for (long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x; idx < n;
        idx += (long long)gridDim.x * blockDim.x) {
     long long t = idx / P;
@@ -686,10 +722,21 @@ __global__ void msda_bwd_generic(const T* __restrict__ grad_out, const T* __rest
         const T v0 = k0 ? value[o0 + c] : (T)0, v1 = k1 ? value[o1 + c] : (T)0, v2 = k2 ? value[o2 + c] : (T)0,
                 v3 = k3 ? value[o3 + c] : (T)0;
         const T top = go[c] * a;
+        if constexpr (DET) {
+          unsigned long long* acc = reinterpret_cast<unsigned long long*>(grad_value);
+          auto add = [&](size_t o, float v) { atomicAdd(acc + o + c, (unsigned long long)egtr_fixed::to_fixed(v, fx.k)); };
+          if (!fx.poisoned) {
+            if (k0) add(o0, hh * hw * top);
+            if (k1) add(o1, hh * lw * top);
+            if (k2) add(o2, lh * hw * top);
+            if (k3) add(o3, lh * lw * top);
+          }
+        } else {
         if (k0) unsafeAtomicAdd(grad_value + o0 + c, hh * hw * top);
         if (k1) unsafeAtomicAdd(grad_value + o1 + c, hh * lw * top);
         if (k2) unsafeAtomicAdd(grad_value + o2 + c, lh * hw * top);
         if (k3) unsafeAtomicAdd(grad_value + o3 + c, lh * lw * top);
+        }
         ga += go[c] * (hh * hw * v0 + hh * lw * v1 + lh * hw * v2 + lh * lw * v3);
         gw += (-hh * v0 + hh * v1 - lh * v2 + lh * v3) * top;
         gh += (-hw * v0 - lw * v1 + hw * v2 + lw * v3) * top;
@@ -875,8 +922,149 @@ extern "C" int egtr_msda_forward_fused_bf16(egtr_stream_t stream, const uint16_t
 
 int egtr_launch_msda_bwd_value_tile_f32(hipStream_t st, const void* grad_out, bool grad_out_bf16, const int64_t* shapes,
                                         const int64_t* lsi, const float* loc, const float* attn, float* grad_value,
-                                        int B, int Lq, int S, int L, int P, unsigned* counters);
+                                        int B, int Lq, int S, int L, int P, unsigned* counters, bool det);
 unsigned* egtr_msda_tile_counters(hipStream_t st);   // eight work counters private to one launch pair (msda_tile.hip)
+
+
+// ---- deterministic route (fixed_accum.h): grad_value accumulated in 64-bit fixed point with integer atomics ----------------
+// workspace = [64-byte header: bits of max|attn_weight|, bits of max|grad_out|] [int64 accumulators, B * S * M * D].
+// Launches: clear (memset) | maxima | the kernels of the default route with DET = true | convert.  Everything the kernels need
+// to choose the scale is on the device: no host synchronisation, capturable into a HIP graph.
+namespace {
+// max|x| of both operands as bit patterns: unsigned max over |x| is order-free, and NaN / inf compare above every finite value.
+// One atomic pair per WORKGROUP and at most 256 workgroups: atomics on one address are served one after the other (~15 ns
+// each here -- a first version with one pair per wave of 2048 workgroups spent 190 us in this kernel, all of it waiting).
+// vec: both operands 16-byte aligned -- 16-byte loads, the tails element by element.
+template <bool GO_BF16>
+__global__ __launch_bounds__(256) void msda_det_maxima(const void* __restrict__ grad_out_, long long n_go,
+                                                       const float* __restrict__ attn, long long n_attn,
+                                                       unsigned* __restrict__ hdr, int vec) {
+  __shared__ unsigned s_m[2][4];
+  unsigned ma = 0u, mg = 0u;
+  const long long stride = (long long)gridDim.x * blockDim.x, t0 = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+  constexpr int kGoVec = GO_BF16 ? 8 : 4;   // elements per 16-byte load of grad_out
+  const long long na_v = vec ? n_attn / 4 : 0, ng_v = vec ? n_go / kGoVec : 0;
+  for (long long i = t0; i < na_v; i += stride) {
+    const uint4 v = reinterpret_cast<const uint4*>(attn)[i];
+    ma = max(max(ma, v.x & 0x7fffffffu), max(max(v.y & 0x7fffffffu, v.z & 0x7fffffffu), v.w & 0x7fffffffu));
+  }
+  for (long long i = na_v * 4 + t0; i < n_attn; i += stride) ma = max(ma, egtr_fixed::abs_bits(attn[i]));
+  for (long long i = t0; i < ng_v; i += stride) {
+    const uint4 v = reinterpret_cast<const uint4*>(grad_out_)[i];
+    if constexpr (GO_BF16) {   // two bfloat16 per word: the high one in place, the low one shifted up
+      auto two = [](unsigned w) { return max(w & 0x7fff0000u, (w << 16) & 0x7fffffffu); };
+      mg = max(max(mg, two(v.x)), max(max(two(v.y), two(v.z)), two(v.w)));
+    } else {
+      mg = max(max(mg, v.x & 0x7fffffffu), max(max(v.y & 0x7fffffffu, v.z & 0x7fffffffu), v.w & 0x7fffffffu));
+    }
+  }
+  for (long long i = ng_v * kGoVec + t0; i < n_go; i += stride) {
+    if constexpr (GO_BF16) mg = max(mg, ((unsigned)static_cast<const uint16_t*>(grad_out_)[i] << 16) & 0x7fffffffu);
+    else mg = max(mg, egtr_fixed::abs_bits(static_cast<const float*>(grad_out_)[i]));
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    ma = max(ma, (unsigned)__shfl_xor((int)ma, o));
+    mg = max(mg, (unsigned)__shfl_xor((int)mg, o));
+  }
+  if ((threadIdx.x & 63) == 0) {
+    s_m[0][threadIdx.x >> 6] = ma;
+    s_m[1][threadIdx.x >> 6] = mg;
+  }
+  __syncthreads();
+  if (threadIdx.x < 2) {
+    const unsigned m = max(max(s_m[threadIdx.x][0], s_m[threadIdx.x][1]), max(s_m[threadIdx.x][2], s_m[threadIdx.x][3]));
+    if (m) atomicMax(hdr + threadIdx.x, m);
+  }
+}
+
+// grad_value = fp32(sum / 2^k): the one rounding of the route.  NaN everywhere when an operand held a non-finite value.
+__global__ __launch_bounds__(256) void msda_det_convert(const long long* __restrict__ acc, float* __restrict__ grad_value,
+                                                        long long n, unsigned long long terms) {
+  const unsigned* hdr = reinterpret_cast<const unsigned*>(reinterpret_cast<const char*>(acc) - egtr_fixed::kHeaderBytes);
+  const egtr_fixed::Scale fx = egtr_fixed::make_scale(hdr[0], hdr[1], terms);
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+    grad_value[i] = fx.poisoned ? __builtin_nanf("") : egtr_fixed::from_fixed(acc[i], fx.k);
+}
+
+template <bool VA, int SPLIT>
+void launch_bwd_q64_det(bool bf16_ops, int nblk, hipStream_t st, const void* grad_out, const void* value,
+                        const int64_t* shapes, const int64_t* lsi, const float* loc, const float* attn, float* acc,
+                        float* grad_loc, float* grad_attn, int nq, int Lq, int S, int L, int P, unsigned* counters,
+                        int zero_rows) {
+  if (bf16_ops)
+    hipLaunchKernelGGL((msda_bwd_q64_f32<VA, SPLIT, true, true>), dim3(nblk), dim3(kWaves * 64), 0, st, grad_out, value,
+                       shapes, lsi, loc, attn, acc, grad_loc, grad_attn, nq, Lq, S, L, P, nblk, counters, zero_rows);
+  else
+    hipLaunchKernelGGL((msda_bwd_q64_f32<VA, SPLIT, false, true>), dim3(nblk), dim3(kWaves * 64), 0, st, grad_out, value,
+                       shapes, lsi, loc, attn, acc, grad_loc, grad_attn, nq, Lq, S, L, P, nblk, counters, zero_rows);
+}
+
+// variant: already resolved (1, 2 or 3) by msda_backward_f32_impl, shapes already checked there
+int msda_backward_det(hipStream_t st, const void* grad_out, const void* value, const int64_t* spatial_shapes,
+                      const int64_t* level_start_index, const float* sampling_loc, const float* attn_weight, int batch,
+                      int spatial_size, int num_heads, int channels, int num_levels, int num_query, int num_point,
+                      float* grad_value, float* grad_sampling_loc, float* grad_attn_weight, int variant, bool bf16_ops,
+                      void* det_ws) {
+  if ((reinterpret_cast<uintptr_t>(det_ws) & 15) != 0) return EGTR_E_ARG;
+  const long long nq = (long long)batch * num_query;
+  const long long nv = (long long)batch * spatial_size * num_heads * channels;
+  unsigned* hdr = static_cast<unsigned*>(det_ws);
+  long long* acc = reinterpret_cast<long long*>(static_cast<char*>(det_ws) + egtr_fixed::kHeaderBytes);
+  float* accf = reinterpret_cast<float*>(acc);   // the kernels' grad_value argument (reinterpreted under DET)
+  // encoder-shaped tile route: the wave-per-query kernel clears accumulator row q as it clears grad_value row q by default
+  const bool zero_in_kernel = variant == 2 && num_query == spatial_size;
+  const size_t clear = zero_in_kernel ? (size_t)egtr_fixed::kHeaderBytes : (size_t)egtr_fixed::kHeaderBytes + (size_t)nv * 8;
+  if (hipMemsetAsync(det_ws, 0, clear, st) != hipSuccess) return EGTR_E_LAUNCH;
+  const long long n_go = nq * num_heads * channels, n_attn = nq * num_heads * num_levels * num_point;
+  const int mblocks = (int)std::min<long long>((std::max(n_go, n_attn) + 4095) / 4096, 256ll);
+  const int vec = ((reinterpret_cast<uintptr_t>(grad_out) | reinterpret_cast<uintptr_t>(attn_weight)) & 15) == 0 ? 1 : 0;
+  if (bf16_ops)
+    hipLaunchKernelGGL(msda_det_maxima<true>, dim3(mblocks), dim3(256), 0, st, grad_out, n_go, attn_weight, n_attn, hdr, vec);
+  else
+    hipLaunchKernelGGL(msda_det_maxima<false>, dim3(mblocks), dim3(256), 0, st, grad_out, n_go, attn_weight, n_attn, hdr, vec);
+  int stt = egtr_check_launch();
+  if (stt != EGTR_OK) return stt;
+  if (variant == 2) {
+    const int nblk = (int)((nq + kWaves - 1) / kWaves);
+    unsigned* counters = egtr_msda_tile_counters(st);
+    if (counters == nullptr) return EGTR_E_LAUNCH;
+    launch_bwd_q64_det<false, 1>(bf16_ops, nblk, st, grad_out, value, spatial_shapes, level_start_index, sampling_loc,
+                                 attn_weight, accf, grad_sampling_loc, grad_attn_weight, (int)nq, num_query, spatial_size,
+                                 num_levels, num_point, counters, zero_in_kernel ? 1 : 0);
+    stt = egtr_check_launch();
+    if (stt != EGTR_OK) return stt;
+    stt = egtr_launch_msda_bwd_value_tile_f32(st, grad_out, bf16_ops, spatial_shapes, level_start_index, sampling_loc,
+                                              attn_weight, accf, batch, num_query, spatial_size, num_levels, num_point,
+                                              counters, true);
+  } else if (variant == 1 && nq * 4 <= 16384 && (num_point == 4 || num_point == 8 || num_point == 16)) {
+    const int nblk = (int)((nq * 4 + kWaves - 1) / kWaves);
+    launch_bwd_q64_det<true, 4>(bf16_ops, nblk, st, grad_out, value, spatial_shapes, level_start_index, sampling_loc,
+                                attn_weight, accf, grad_sampling_loc, grad_attn_weight, (int)nq, num_query, spatial_size,
+                                num_levels, num_point, nullptr, 0);
+    stt = egtr_check_launch();
+  } else if (variant == 1) {
+    const int nblk = (int)((nq + kWaves - 1) / kWaves);
+    launch_bwd_q64_det<true, 1>(bf16_ops, nblk, st, grad_out, value, spatial_shapes, level_start_index, sampling_loc,
+                                attn_weight, accf, grad_sampling_loc, grad_attn_weight, (int)nq, num_query, spatial_size,
+                                num_levels, num_point, nullptr, 0);
+    stt = egtr_check_launch();
+  } else {
+    const long long n = nq * num_heads * num_levels * num_point;
+    const int blocks = (int)std::min<long long>((n + 255) / 256, 65535ll * 16);
+    hipLaunchKernelGGL((msda_bwd_generic<float, true>), dim3(blocks), dim3(256), 0, st, static_cast<const float*>(grad_out),
+                       static_cast<const float*>(value), spatial_shapes, level_start_index, sampling_loc, attn_weight,
+                       accf, grad_sampling_loc, grad_attn_weight, n, spatial_size, num_heads, channels, num_levels,
+                       num_query, num_point);
+    stt = egtr_check_launch();
+  }
+  if (stt != EGTR_OK) return stt;
+  const int cblocks = (int)std::min<long long>((nv + 1023) / 1024, 4096ll);
+  hipLaunchKernelGGL(msda_det_convert, dim3(cblocks), dim3(256), 0, st, acc, grad_value, nv,
+                     (unsigned long long)num_query * num_levels * num_point);
+  return egtr_check_launch();
+}
+}  // namespace
 
 // variant: 0 = automatic, 1 = wave-per-query with per-sample global atomics (reference scheme), 2 = two kernels:
 // wave-per-query for grad_attn / grad_loc (no atomics) + query-tile x head MFMA accumulation of grad_value
@@ -892,7 +1080,7 @@ int msda_backward_f32_impl(egtr_stream_t stream, const void* grad_out, const voi
                            int spatial_size, int num_heads, int channels, int num_levels,
                            int num_query, int num_point, float* grad_value,
                            float* grad_sampling_loc, float* grad_attn_weight, int variant, bool zero_inside,
-                           bool bf16_ops = false) {
+                           bool bf16_ops = false, void* det_ws = nullptr) {
   if (!grad_out || !value || !spatial_shapes || !level_start_index || !sampling_loc || !attn_weight || !grad_value ||
       !grad_sampling_loc || !grad_attn_weight)
     return EGTR_E_ARG;
@@ -906,6 +1094,10 @@ int msda_backward_f32_impl(egtr_stream_t stream, const void* grad_out, const voi
   if (variant == 0) variant = fast ? ((num_query == spatial_size && num_query >= 256) ? 2 : 1) : 3;
   if ((variant == 1 || variant == 2) && !fast) return EGTR_E_UNSUPPORTED;
   if (bf16_ops && variant == 3) return EGTR_E_UNSUPPORTED;
+  if (det_ws != nullptr)
+    return msda_backward_det(st, grad_out, value, spatial_shapes, level_start_index, sampling_loc, attn_weight, batch,
+                             spatial_size, num_heads, channels, num_levels, num_query, num_point, grad_value,
+                             grad_sampling_loc, grad_attn_weight, variant, bf16_ops, det_ws);
   const bool zero_in_kernel = zero_inside && variant == 2 && num_query == spatial_size;
   if (zero_inside && !zero_in_kernel &&
       hipMemsetAsync(grad_value, 0, (size_t)batch * spatial_size * num_heads * channels * sizeof(float), st) != hipSuccess)
@@ -928,7 +1120,7 @@ int msda_backward_f32_impl(egtr_stream_t stream, const void* grad_out, const voi
     if (st1 != EGTR_OK) return st1;
     return egtr_launch_msda_bwd_value_tile_f32(st, grad_out, bf16_ops, spatial_shapes, level_start_index, sampling_loc,
                                                attn_weight, grad_value, batch, num_query, spatial_size, num_levels,
-                                               num_point, counters);
+                                               num_point, counters, false);
   }
   if (variant == 1 && nq * 4 <= 16384 && (num_point == 4 || num_point == 8 || num_point == 16)) {
     // short query list: 4 waves per query (one level's samples each for L = P = 4)
@@ -1090,4 +1282,37 @@ extern "C" int egtr_msda_backward_bf16(egtr_stream_t stream, const uint16_t* gra
   return egtr_msda_backward_f32(stream, workspace + nv, workspace, spatial_shapes, level_start_index, sampling_loc,
                                 attn_weight, batch, spatial_size, num_heads, channels, num_levels, num_query, num_point,
                                 grad_value, grad_sampling_loc, grad_attn_weight);
+}
+
+// ---- deterministic entries: the arguments of egtr_msda_backward_out_f32 / egtr_msda_backward_bf16 plus the
+// workspace of egtr_msda_backward_det_workspace_bytes(); same automatic choice of kernels, grad_value arrives uninitialised.
+extern "C" long long egtr_msda_backward_det_workspace_bytes(int batch, int spatial_size, int num_heads, int channels) {
+  if (batch <= 0 || spatial_size <= 0 || num_heads <= 0 || channels <= 0) return 0;
+  return (long long)egtr_fixed::kHeaderBytes + 8ll * batch * spatial_size * num_heads * channels;
+}
+
+extern "C" int egtr_msda_backward_det_f32(egtr_stream_t stream, const float* grad_out, const float* value,
+                                          const int64_t* spatial_shapes, const int64_t* level_start_index,
+                                          const float* sampling_loc, const float* attn_weight, int batch,
+                                          int spatial_size, int num_heads, int channels, int num_levels, int num_query,
+                                          int num_point, float* grad_value, float* grad_sampling_loc,
+                                          float* grad_attn_weight, void* workspace) {
+  if (!workspace) return EGTR_E_ARG;
+  return msda_backward_f32_impl(stream, grad_out, value, spatial_shapes, level_start_index, sampling_loc, attn_weight, batch,
+                                spatial_size, num_heads, channels, num_levels, num_query, num_point, grad_value,
+                                grad_sampling_loc, grad_attn_weight, 0, true, false, workspace);
+}
+
+// bf16 grad_out / value, fast shapes only (M = 8, D = 32, L * P = 16): EGTR_E_UNSUPPORTED otherwise -- the caller widens the
+// operands and uses the fp32 entry.
+extern "C" int egtr_msda_backward_det_bf16(egtr_stream_t stream, const uint16_t* grad_out, const uint16_t* value,
+                                           const int64_t* spatial_shapes, const int64_t* level_start_index,
+                                           const float* sampling_loc, const float* attn_weight, int batch,
+                                           int spatial_size, int num_heads, int channels, int num_levels, int num_query,
+                                           int num_point, float* grad_value, float* grad_sampling_loc,
+                                           float* grad_attn_weight, void* workspace) {
+  if (!workspace) return EGTR_E_ARG;
+  return msda_backward_f32_impl(stream, grad_out, value, spatial_shapes, level_start_index, sampling_loc, attn_weight, batch,
+                                spatial_size, num_heads, channels, num_levels, num_query, num_point, grad_value,
+                                grad_sampling_loc, grad_attn_weight, 0, true, true, workspace);
 }

@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "common.h"
+#include "fixed_accum.h"
 #include "msda_common.h"
 
 using namespace egtr_msda;
@@ -49,7 +50,10 @@ constexpr int kGraphSlots = 8192;     // captured launches: one-way
 __device__ unsigned g_tile_counters[(kCounterSlots + kGraphSlots) * 8];
 
 // GO_BF16: grad_out holds raw bfloat16 (the backward of a bf16 model); widened on load, everything else is unchanged.
-template <bool GO_BF16>
+// DET: grad_value is the int64 accumulator array of the deterministic workspace (fixed_accum.h; rows of 2048 bytes behind the
+// 64-byte header): an item's partial G -- formed in a fixed order above -- is added as 64-bit fixed point with an integer atomic,
+// so that neither the dynamic hand-out of the items nor their overlapping windows can change the sum.
+template <bool GO_BF16, bool DET = false>
 __global__ __launch_bounds__(kThreads, 2) void msda_bwd_value_tile_f32(
     const void* __restrict__ grad_out_, const int64_t* __restrict__ shapes, const int64_t* __restrict__ lsi,
     const float* __restrict__ loc, const float* __restrict__ attn, float* __restrict__ grad_value, int B, int Lq,
@@ -77,6 +81,11 @@ __global__ __launch_bounds__(kThreads, 2) void msda_bwd_value_tile_f32(
   // workgroup took 814 k cycles against a mean of 685 k).  An index is drawn two items ahead of its use -- the operands of
   // the next item are in flight while the current one is multiplied out, and the atomic's result is picked up an item later.
   const int head = blockIdx.x & 7;
+  egtr_fixed::Scale fx = {0, false};
+  if constexpr (DET) {
+    const unsigned* hdr = reinterpret_cast<const unsigned*>(reinterpret_cast<const char*>(grad_value) - egtr_fixed::kHeaderBytes);
+    fx = egtr_fixed::make_scale(hdr[0], hdr[1], (unsigned long long)Lq * L * P);
+  }
   const int nitems = B * tm.ntiles;
   unsigned* ctr = counters + head;
   // A is zero whenever a chunk starts building it: zeroed once here, and every element a chunk filled is zeroed again by the
@@ -120,7 +129,7 @@ __global__ __launch_bounds__(kThreads, 2) void msda_bwd_value_tile_f32(
 
   while (cur < nitems) {
     const int b = cur % B;
-    char* gvbase = reinterpret_cast<char*>(grad_value) + (size_t)b * S * 1024;
+    char* gvbase = reinterpret_cast<char*>(grad_value) + (size_t)b * S * (DET ? 2048 : 1024);
 
     if (tid < 16) s_bbox[tid] = (tid & 1) ? INT_MIN : INT_MAX;
     if (tid == 0) {
@@ -308,7 +317,13 @@ __global__ __launch_bounds__(kThreads, 2) void msda_bwd_value_tile_f32(
             const int col = mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hf;
             const int4 p4 = po[r >> 2];
             const int pix = (r & 3) == 0 ? p4.x : (r & 3) == 1 ? p4.y : (r & 3) == 2 ? p4.z : p4.w;
+            if constexpr (DET) {   // 32 lanes = 256 contiguous bytes
+              if (col < ncols && acc[r] != 0.f && !fx.poisoned)
+                atomicAdd(reinterpret_cast<unsigned long long*>(gvbase + 2 * (size_t)(unsigned)pix) + li,
+                          (unsigned long long)egtr_fixed::to_fixed(acc[r], fx.k));
+            } else {
             if (col < ncols && acc[r] != 0.f) unsafeAtomicAdd(reinterpret_cast<float*>(gvbase + (unsigned)pix) + li, acc[r]);
+            }
           }
         }
       }
@@ -344,7 +359,16 @@ unsigned* egtr_msda_tile_counters(hipStream_t st) {
 // Launcher used by egtr_msda_backward_f32 (msda.hip): grad_value of encoder-shaped calls (M = 8, D = 32, L*P = 16).
 int egtr_launch_msda_bwd_value_tile_f32(hipStream_t st, const void* grad_out, bool grad_out_bf16, const int64_t* shapes,
                                         const int64_t* lsi, const float* loc, const float* attn, float* grad_value,
-                                        int B, int Lq, int S, int L, int P, unsigned* counters) {
+                                        int B, int Lq, int S, int L, int P, unsigned* counters, bool det) {
+  if (det) {   // grad_value: the accumulators of the deterministic workspace
+    if (grad_out_bf16)
+      hipLaunchKernelGGL((msda_bwd_value_tile_f32<true, true>), dim3(kBwdGrid), dim3(kThreads), 0, st, grad_out, shapes, lsi,
+                         loc, attn, grad_value, B, Lq, S, L, P, counters);
+    else
+      hipLaunchKernelGGL((msda_bwd_value_tile_f32<false, true>), dim3(kBwdGrid), dim3(kThreads), 0, st, grad_out, shapes, lsi,
+                         loc, attn, grad_value, B, Lq, S, L, P, counters);
+    return egtr_check_launch();
+  }
   if (grad_out_bf16)
     hipLaunchKernelGGL(msda_bwd_value_tile_f32<true>, dim3(kBwdGrid), dim3(kThreads), 0, st, grad_out, shapes, lsi, loc, attn,
                        grad_value, B, Lq, S, L, P, counters);

@@ -177,9 +177,10 @@ def pack_relation_bits(triplets, offsets, batch, total, num_query, num_rel):
 
 
 def relation_loss_launch(pred_rel, pred_conn, target, packed, pred_idx, tgt_idx, match_cost, out_off, nonmatching_cost,
-                         sample_negatives, sample_nonmatching):
+                         sample_negatives, sample_nonmatching, deterministic=False):
     """egtr_relation_loss_f32 (``target``: the device table of per-image pointers to dense fp32 targets) or, with
-    ``packed``, egtr_relation_loss_bits_f32 (``target``: the words int64 [B, N, N]).  Returns (loss [2], grad_rel, grad_conn)."""
+    ``packed``, egtr_relation_loss_bits_f32 (``target``: the words int64 [B, N, N]).  Returns (loss [2], grad_rel, grad_conn).
+    ``deterministic``: the egtr_relation_loss_det_* forms (ties at the selection threshold taken lowest flat index first)."""
     B, N, _, R = pred_rel.shape
     dev = pred_rel.device
     if packed and tuple(_chk(target, "rel_bits", torch.int64).shape) != (B, N, N):
@@ -187,8 +188,12 @@ def relation_loss_launch(pred_rel, pred_conn, target, packed, pred_idx, tgt_idx,
     loss = torch.empty(2, dtype=torch.float32, device=dev)
     grad_rel = torch.empty_like(pred_rel)
     grad_conn = torch.empty_like(pred_conn)
-    ws = torch.empty(int(_lib.lib().egtr_relation_loss_workspace_bytes(B, N)), dtype=torch.uint8, device=dev)
-    _lib.launch("egtr_relation_loss_bits_f32" if packed else "egtr_relation_loss_f32", pred_rel.data_ptr(),
+    if deterministic:
+        nbytes, entry = _lib.lib().egtr_relation_loss_det_workspace_bytes(B, N), "egtr_relation_loss_det_"
+    else:
+        nbytes, entry = _lib.lib().egtr_relation_loss_workspace_bytes(B, N), "egtr_relation_loss_"
+    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+    _lib.launch(entry + ("bits_f32" if packed else "f32"), pred_rel.data_ptr(),
                 pred_conn.data_ptr(), target.data_ptr(), pred_idx.data_ptr(), tgt_idx.data_ptr(), match_cost.data_ptr(),
                 out_off.data_ptr(), B, N, R, float(nonmatching_cost), int(sample_negatives), int(sample_nonmatching),
                 loss.data_ptr(), grad_rel.data_ptr(), grad_conn.data_ptr(), ws.data_ptr())

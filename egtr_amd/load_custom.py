@@ -157,6 +157,10 @@ class _MultiScaleDeformableAttention:
     @staticmethod
     def ms_deform_attn_backward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output,
                                 im2col_step):
+        from . import ops   # (at call time: ops imports this module)
+        if ops.is_deterministic():
+            return _MultiScaleDeformableAttention._backward_deterministic(value, spatial_shapes, level_start_index, sampling_loc,
+                                                                          attn_weight, grad_output)
         lib = _lib.lib()
         B, S, M, D = value.shape
         L = spatial_shapes.shape[0]
@@ -202,6 +206,41 @@ class _MultiScaleDeformableAttention:
                     level_start_index.data_ptr(), sampling_loc.data_ptr(), attn_weight.data_ptr(), B, S, M, D, L, Lq, P,
                     grad_value.data_ptr(), grad_loc.data_ptr(), grad_attn.data_ptr(), what="ms_deform_attn_backward")
         return grad_value, grad_loc, grad_attn
+
+    @staticmethod
+    def _backward_deterministic(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output):
+        """``ms_deform_attn_backward`` under ``ops.is_deterministic()``: grad_value accumulated in 64-bit fixed point with integer
+        atomics (egtr_msda_backward_det_f32 / _bf16, csrc/fixed_accum.h) -- bit-reproducible; grad_loc / grad_attn are the
+        default route's bits.  A non-finite value in grad_output or attn_weight makes every element of grad_value NaN."""
+        if value.dtype == torch.float64:
+            raise RuntimeError("ms_deform_attn_backward does not have a deterministic implementation for float64 operands "
+                               "(64-bit fixed-point accumulation cannot hold a double), but egtr_amd.ops.is_deterministic() is "
+                               "set; leave the deterministic mode for this call or use float32")
+        lib = _lib.lib()
+        B, S, M, D = value.shape
+        L = spatial_shapes.shape[0]
+        Lq, P = sampling_loc.shape[1], sampling_loc.shape[4]
+        _chk(spatial_shapes, "spatial_shapes", torch.int64)
+        _chk(level_start_index, "level_start_index", torch.int64)
+        bf = value.dtype == torch.bfloat16
+        _chk(sampling_loc, "sampling_loc", torch.float32)
+        _chk(attn_weight, "attn_weight", torch.float32)
+        if bf and not (M == 8 and D == 32 and 1 <= L <= 4 and L * P == 16):   # the bf16 kernels serve the model's shapes
+            gv, gl, ga = _MultiScaleDeformableAttention._backward_deterministic(
+                value.float(), spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output.float())
+            return gv.to(torch.bfloat16), gl, ga
+        dt = torch.bfloat16 if bf else torch.float32
+        _chk(value, "value", dt)
+        _chk(grad_output, "grad_output", dt)
+        grad_value = torch.empty(value.shape, dtype=torch.float32, device=value.device)
+        grad_loc = torch.empty_like(sampling_loc)
+        grad_attn = torch.empty_like(attn_weight)
+        ws = torch.empty(int(lib.egtr_msda_backward_det_workspace_bytes(B, S, M, D)), dtype=torch.uint8, device=value.device)
+        _lib.launch("egtr_msda_backward_det_bf16" if bf else "egtr_msda_backward_det_f32", grad_output.data_ptr(),
+                    value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(), sampling_loc.data_ptr(),
+                    attn_weight.data_ptr(), B, S, M, D, L, Lq, P, grad_value.data_ptr(), grad_loc.data_ptr(),
+                    grad_attn.data_ptr(), ws.data_ptr(), what="ms_deform_attn_backward (deterministic)")
+        return (grad_value.to(torch.bfloat16) if bf else grad_value), grad_loc, grad_attn
 
 
 def load_hip_kernels():

@@ -873,9 +873,52 @@ def decoder_layer_train(layer, x, pos, ref, value, spatial_shapes, level_start_i
 #   EGTR_BACKBONE_NHWC=0        backbone.NHWC_F32 / _BF16   inference backbone channels-last  ->  NCHW
 #   EGTR_ENCODER_TRAIN_FUSED=0  ops.ENCODER_TRAIN_FUSED     training nodes (encoder / decoder layer, values, LayerNorm)  ->  per-op autograd
 #   EGTR_TOKEN_LINEAR=0         ops.TOKEN_LINEAR            token-sized linears under autograd: TokenLinearFunction  ->  F.linear
+#   EGTR_DETERMINISTIC=1        ops.DETERMINISTIC           (opt-IN) training: fp32 atomics / first-come tie tickets  ->  the order-free
+#                                                           routes (fixed-point MSDA grad_value, indexed loss ties, gate means
+#                                                           reduced in a fixed order); see set_deterministic() below
 # Not route switches: EGTR_HIP_LIBRARY (another build of the library), EGTR_STRICT_FAST_PATH (below), EGTR_TRUST_CHECKPOINT_PICKLE.
 ENV_ROUTE_SWITCHES = ("EGTR_DECODER_CLUSTER", "EGTR_GEMM_SPLIT_BF16", "EGTR_REL_HEAD_SPLIT_BF16", "EGTR_FFN_FUSED",
-                      "EGTR_BACKBONE_NHWC", "EGTR_ENCODER_TRAIN_FUSED", "EGTR_TOKEN_LINEAR")
+                      "EGTR_BACKBONE_NHWC", "EGTR_ENCODER_TRAIN_FUSED", "EGTR_TOKEN_LINEAR", "EGTR_DETERMINISTIC")
+
+# ---- deterministic mode ------------------------------------------------------------------------------
+# Opt-in: the same inputs on the same device with the same build give the same bits from the library's own kernels and this
+# package's autograd Functions.  Three places on the training path depend on the order in which the hardware serves atomics; under
+# the mode each takes an order-free route, consulted AT CALL TIME (a route switch, not a fall-off: nothing is counted in FALLBACKS):
+#   MSDA backward, grad_value   fp32 atomics  ->  64-bit fixed point with integer atomics (egtr_msda_backward_det_*); float64 raises
+#   relation loss, tied logits  tickets       ->  lowest flat index first (egtr_relation_loss_det_*)
+#   rel_gate_{t} logging        fp32 atomics  ->  a torch reduction (fixed order); the model output never depended on it
+# Not covered: vendor kernels (MIOpen convolutions, rocBLAS GEMMs), ATen operations without a deterministic form, equality
+# across batch sizes / devices / builds, or between this route and the default one.  torch's own global switch
+# (torch.use_deterministic_algorithms) is honoured and never set from here.
+DETERMINISTIC = os.environ.get("EGTR_DETERMINISTIC", "0") == "1"
+
+
+def set_deterministic(flag):
+    """Turn the library's deterministic routes on or off (process-wide; returns the previous setting)."""
+    global DETERMINISTIC
+    prev = DETERMINISTIC
+    DETERMINISTIC = bool(flag)
+    return prev
+
+
+def is_deterministic():
+    """True when the order-free routes are taken: ``ops.DETERMINISTIC`` or torch's global deterministic-algorithms switch."""
+    return bool(DETERMINISTIC) or torch.are_deterministic_algorithms_enabled()
+
+
+class deterministic:
+    """``with ops.deterministic():`` -- the mode for a block (``flag=False``: off for a block); restores the previous setting."""
+
+    def __init__(self, flag=True):
+        self.flag = bool(flag)
+
+    def __enter__(self):
+        self.prev = set_deterministic(self.flag)
+        return self
+
+    def __exit__(self, *exc):
+        set_deterministic(self.prev)
+        return False
 
 # ---- leaving a HIP fast path is never silent ------------------------------------------------------------------------------
 # Every route from a hand-written kernel to an ATen composition (unsupported shape, misaligned operand, a device that
@@ -1351,6 +1394,15 @@ def relation_head(gate_q, gate_k, uq, uk, b1, w2r, b2r, w3r, b3r, w2c, b2c, w3c,
                   node_cls=None, want_gate_mean=False, owner=None, sigmoid=False):
     """``owner`` (optional nn.Module): where the derived split-bf16 weight streams of the inference kernel are cached.
     ``sigmoid``: return sigmoid(logits) (the model outputs) instead of the logits -- in the inference kernel's epilogue."""
+    if want_gate_mean and is_deterministic() and gate_q.is_cuda:
+        # the kernels add the logged gate means with fp32 atomics: under the mode they get no gate_mean buffer and the means are
+        # reduced by torch (fixed order); the model outputs do not depend on them
+        rel, conn, _ = relation_head(gate_q, gate_k, uq, uk, b1, w2r, b2r, w3r, b3r, w2c, b2c, w3c, b3c, triplet_dist,
+                                     node_cls, False, owner, sigmoid)
+        with torch.no_grad():
+            gq, gk = gate_q.detach().float(), gate_k.detach().float()
+            gm = torch.sigmoid(gq[:, :, None, :] + gk[:, None, :, :]).mean(dim=(0, 1, 2))
+        return rel, conn, gm
     if sigmoid:
         rel, conn, gm = _relation_head(gate_q, gate_k, uq, uk, b1, w2r, b2r, w3r, b3r, w2c, b2c, w3c, b3c, triplet_dist,
                                        node_cls, want_gate_mean, owner, True)
@@ -1399,7 +1451,8 @@ class RelationLossFunction(Function):
         pr = _chk(pred_rel.detach().contiguous(), "pred_rel", torch.float32)
         pc = _chk(pred_conn.detach().contiguous(), "pred_connectivity", torch.float32)
         loss, grad_rel, grad_conn = relation_loss_launch(pr, pc, target, packed, pred_idx, tgt_idx, match_cost, out_off,
-                                                         nonmatching_cost, sample_negatives, sample_nonmatching)
+                                                         nonmatching_cost, sample_negatives, sample_nonmatching,
+                                                         deterministic=is_deterministic())
         ctx.save_for_backward(grad_rel, grad_conn)
         return loss[0], loss[1]
 

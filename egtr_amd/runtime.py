@@ -307,7 +307,7 @@ class DataParallelTrainer:
     clip-grad-norm 0.1 and AdamW.  ``num_boxes`` stays per-rank (model/egtr.py:976-980)."""
 
     def __init__(self, model, optimizer=None, accumulate=2, clip=0.1, bucket_cap_mb=25, graph=False, force_ddp=False,
-                 grad_compression=None):
+                 grad_compression=None, deterministic=False):
         """graph=True (single process, GPU, fixed image size): the static-shape part of the step -- backbone, encoder,
         decoder, detection + relation heads, forward AND backward -- is captured once into two HIP graphs
         (torch.cuda.make_graphed_callables over ``model.forward_tensors``) and replayed; the Hungarian matcher and the
@@ -318,7 +318,17 @@ class DataParallelTrainer:
         ``grad_compression``: None (fp32 all-reduce, the reference's DDP), "bf16" or "fp16" -- DDP's communication hook that
         casts every gradient bucket to 16 bits for the all-reduce and back (torch's ``bf16_compress_hook`` / ``fp16_compress_hook``):
         half the bytes per link for the bandwidth-bound stress configuration (165 MB fp32 per step otherwise).  The
-        averaged gradient is then rounded to 8 / 11 significant bits before clipping -- opt-in, not the parity configuration."""
+        averaged gradient is then rounded to 8 / 11 significant bits before clipping -- opt-in, not the parity configuration.
+
+        ``deterministic=True``: every step runs under ``ops.deterministic()`` -- the library's order-free routes (fixed-point MSDA
+        grad_value, indexed loss ties, gate means reduced in a fixed order): same inputs, device and build give the same bits
+        from the library's own kernels -- and ``torch.backends.cudnn.deterministic`` is set, which REQUESTS deterministic MIOpen
+        algorithms; MIOpen's compliance is requested, not promised, and vendor GEMMs / ATen operations without a deterministic
+        form are outside the guarantee.  Works with ``graph=True``: the mode is part of the key of the captured
+        step, so a step captured under one setting is never replayed under the other."""
+        self.deterministic = bool(deterministic)
+        if self.deterministic:
+            torch.backends.cudnn.deterministic = True
         self.world = dist.get_world_size() if dist.is_initialized() else 1
         self.raw = model
         self.grad_compression = None
@@ -347,7 +357,8 @@ class DataParallelTrainer:
         self._micro = 0
 
     def _graphed_body(self, pixel_values, pixel_mask):
-        key = (tuple(pixel_values.shape), pixel_values.dtype, tuple(pixel_mask.shape), pixel_mask.dtype)
+        from . import ops
+        key = (tuple(pixel_values.shape), pixel_values.dtype, tuple(pixel_mask.shape), pixel_mask.dtype, ops.is_deterministic())
         if self._graphed is None or key != self._graph_key:
             raw = self.raw
 
@@ -415,7 +426,9 @@ class DataParallelTrainer:
         boundary = self._micro % self.accumulate == 0
         wrapped = self.model is not self.raw
         ctx = contextlib.nullcontext() if (boundary or not wrapped) else self.model.no_sync()
-        with ctx:
+        from . import ops
+        mode = ops.deterministic(True) if self.deterministic else contextlib.nullcontext()
+        with ctx, mode:
             loss, loss_dict = self.common_step(batch)
             (loss / self.accumulate).backward()
         if boundary:

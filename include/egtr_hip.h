@@ -138,6 +138,28 @@ int egtr_msda_backward_bf16(egtr_stream_t stream, const uint16_t* grad_out, cons
                             int num_levels, int num_query, int num_point, float* grad_value, float* grad_sampling_loc,
                             float* grad_attn_weight, float* workspace);
 
+/* Deterministic backward: the arguments of egtr_msda_backward_out_f32 (grad_value need not be initialised) plus
+ * a workspace of egtr_msda_backward_det_workspace_bytes() = 64 + 8 * B * S * M * D bytes (16-byte aligned, contents
+ * irrelevant).  grad_value is accumulated as 64-bit fixed point with integer atomics -- the sum does not depend on the order of
+ * the additions -- and rounded to fp32 once; the scale is chosen on the device from max|grad_out|, max|attn_weight| and
+ * Lq * L * P (csrc/fixed_accum.h), so the call neither synchronises nor is it barred from graph capture.  The same automatic
+ * choice of kernels as the other entries; grad_sampling_loc / grad_attn_weight are the other entries' bits.  All-zero grad_out
+ * gives all-zero grad_value; a non-finite value anywhere in grad_out or attn_weight (or maxima whose product with Lq * L * P
+ * exceeds 2^127) makes EVERY element of grad_value NaN, where the other entries poison the touched pixels only.
+ * The bf16 entry takes raw bfloat16 grad_out / value and serves M = 8, D = 32, L * P = 16 (EGTR_E_UNSUPPORTED otherwise:
+ * widen the operands and call the f32 entry).  There is no float64 form: 64 bits of fixed point cannot hold a double. */
+long long egtr_msda_backward_det_workspace_bytes(int batch, int spatial_size, int num_heads, int channels);
+int egtr_msda_backward_det_f32(egtr_stream_t stream, const float* grad_out, const float* value,
+                               const int64_t* spatial_shapes, const int64_t* level_start_index,
+                               const float* sampling_loc, const float* attn_weight, int batch, int spatial_size,
+                               int num_heads, int channels, int num_levels, int num_query, int num_point,
+                               float* grad_value, float* grad_sampling_loc, float* grad_attn_weight, void* workspace);
+int egtr_msda_backward_det_bf16(egtr_stream_t stream, const uint16_t* grad_out, const uint16_t* value,
+                                const int64_t* spatial_shapes, const int64_t* level_start_index,
+                                const float* sampling_loc, const float* attn_weight, int batch, int spatial_size,
+                                int num_heads, int channels, int num_levels, int num_query, int num_point,
+                                float* grad_value, float* grad_sampling_loc, float* grad_attn_weight, void* workspace);
+
 /* bf16 storage (uint16_t = raw bfloat16 bits), fp32 accumulation.  The reference dispatches float/double only
  * (cu:67,137); this is the added path for the bf16 stress configuration.  loc / attn stay fp32; the per-corner sample weight
  * (bilinear x attention, formed in fp32) is rounded to bf16 as the second operand of v_dot2_f32_bf16. */
@@ -486,6 +508,23 @@ int egtr_relation_loss_bits_f32(egtr_stream_t stream, const float* pred_rel, con
                                 const float* match_cost, const int* out_offsets, int batch, int num_query, int num_rel,
                                 float nonmatching_cost, int sample_negatives, int sample_nonmatching, float* loss_out,
                                 float* grad_rel, float* grad_conn, void* workspace);
+
+/* Deterministic forms of the two entries above: among the candidates whose logit equals the k-th largest of an (image,
+ * problem), the ones with the LOWEST flat index (qa * N + qb) * R + r (query order) are taken instead of the first to arrive,
+ * so the selected set -- and with it loss and gradient -- is a function of the inputs alone (the reference's topk leaves the
+ * order among ties unspecified: any fixed rule conforms).  One more pass over pred_rel; workspace:
+ * egtr_relation_loss_det_workspace_bytes() bytes.  The two det entries return the same bits on the same targets. */
+long long egtr_relation_loss_det_workspace_bytes(int batch, int num_query);
+int egtr_relation_loss_det_f32(egtr_stream_t stream, const float* pred_rel, const float* pred_conn,
+                               const float* const* target_rel, const int64_t* pred_idx, const int64_t* tgt_idx,
+                               const float* match_cost, const int* out_offsets, int batch, int num_query, int num_rel,
+                               float nonmatching_cost, int sample_negatives, int sample_nonmatching, float* loss_out,
+                               float* grad_rel, float* grad_conn, void* workspace);
+int egtr_relation_loss_det_bits_f32(egtr_stream_t stream, const float* pred_rel, const float* pred_conn,
+                                    const uint64_t* rel_bits, const int64_t* pred_idx, const int64_t* tgt_idx,
+                                    const float* match_cost, const int* out_offsets, int batch, int num_query, int num_rel,
+                                    float nonmatching_cost, int sample_negatives, int sample_nonmatching, float* loss_out,
+                                    float* grad_rel, float* grad_conn, void* workspace);
 
 /* IoU matrix of the reference's native evaluator routine, lib/fpn/box_intersections_cpu/bbox.pyx: mode 0 =
  * bbox_overlaps (:21-61), mode 1 = bbox_intersections (:64-108).  boxes [num_boxes, 4], query_boxes [num_query, 4]

@@ -3,7 +3,7 @@
 sampling locations distributed like the model's: reference grid + the ring offset pattern of
 DeformableDetrMultiscaleDeformableAttention._reset_parameters (+- 1..4 px per head) + jitter.
 
-    python tools/msda_bench.py [--lq enc|dec] [--iters 200] [--bwd] [--jitter 0.5] [--batch 1]
+    python tools/msda_bench.py [--lq enc|dec] [--iters 200] [--bwd [--deterministic]] [--jitter 0.5] [--batch 1]
 Used under rocprofv3 (--kernel-trace --stats, and separate --pmc passes) for the roofline numbers in DESIGN.md.
 """
 import argparse
@@ -60,12 +60,19 @@ def main():
     ap.add_argument("--variant", type=int, default=0, help="kernel choice of the *_variant entries (include/egtr_hip_test.h)")
     ap.add_argument("--fused", action="store_true", help="fused-prologue entry (offsets | logits block + ref points)")
     ap.add_argument("--lib", default=None, help="load this build of libegtr_hip.so instead of the in-tree one (A/B of kernel builds)")
+    ap.add_argument("--deterministic", action="store_true",
+                    help="with --bwd: the order-free route (ops.set_deterministic: fixed-point grad_value, DESIGN.md 4.2)")
     a = ap.parse_args()
     if a.lib:
         from egtr_amd import _lib
         _lib.LIB_PATH = os.path.abspath(a.lib)
     from egtr_amd.load_custom import load_hip_kernels
     k = load_hip_kernels()
+    if a.deterministic:
+        if not a.bwd or a.variant:
+            ap.error("--deterministic selects the route of the backward entry: use it with --bwd and without --variant")
+        from egtr_amd import ops
+        ops.set_deterministic(True)
     dev = "cuda:0"
     shapes = [(100, 167), (50, 84), (25, 42), (13, 21)] if a.big else SHAPES
     value, shp, lsi, loc, attn = make_inputs(a.batch, a.lq, a.jitter, dev, shapes,
@@ -123,7 +130,7 @@ def main():
     alg = reads + B * Lq * 256 * e
     if a.bwd:
         alg = reads + B * (Lq * 256 * 4 + 2 * S * 256 * 4 + Lq * 256 * 4 + Lq * 128 * 4)
-    print(f"msda {'bwd' if a.bwd else 'fwd'} variant={a.variant} jitter={a.jitter} lq={a.lq} B={B} S={S} Lq={Lq} {'bf16' if a.bf16 else 'f32'}: "
+    print(f"msda {'bwd' if a.bwd else 'fwd'}{' deterministic' if a.deterministic else ''} variant={a.variant} jitter={a.jitter} lq={a.lq} B={B} S={S} Lq={Lq} {'bf16' if a.bf16 else 'f32'}: "
           f"{us:.2f} us/launch (incl. the zero-fill of grad_value for bwd), algorithmic {alg / 1e6:.2f} MB -> "
           f"{alg / us / 1e3:.1f} GB/s = {alg / us / 1e3 / 8000 * 100:.1f}% of 8 TB/s")
 
