@@ -27,6 +27,7 @@ namespace {
 using x6::bf16x8;
 using x6::f32x16;
 using x6::static_for;
+using x6::xcd_tile;
 
 constexpr int kBM = 64, kBN = 256, kNTW = 2, kMT = 2;
 constexpr int kPatchPitch = 64 + 8;   // bf16 elements per row of a wave's 32 x 64 output patch (144 bytes: 16-byte aligned rows)
@@ -51,10 +52,6 @@ __device__ __forceinline__ unsigned pk_bf16(float a, float b) {   // v_cvt_pk_bf
   v[0] = (__bf16)a;
   v[1] = (__bf16)b;
   return __builtin_bit_cast(unsigned, v);
-}
-__device__ __forceinline__ int xcd_tile(int bid, int total) {
-  const int q = total >> 3, r = total & 7, x = bid & 7;
-  return x * q + min(x, r) + (bid >> 3);
 }
 
 template <int KS>

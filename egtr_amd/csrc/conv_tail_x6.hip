@@ -34,7 +34,6 @@
 
 namespace {
 using namespace x6;
-typedef float f32x4v __attribute__((ext_vector_type(4)));
 
 struct TailArgs {
   const float* a;         // [M, lda]
@@ -47,11 +46,6 @@ struct TailArgs {
   int relu_in, relu_out;
   int row_major;   // tile order: 1 = the column blocks of a row panel are neighbours, 0 = the row panels of a column block
 };
-
-__device__ __forceinline__ int xcd_tile(int bid, int total) {
-  const int q = total >> 3, r = total & 7, x = bid & 7;
-  return x * q + min(x, r) + (bid >> 3);
-}
 
 #ifdef EGTR_TAIL_TIMING
 // debugging aid (tools/tail_timing.py): per workgroup of the LAST launch (no atomics: they would be the bottleneck), the

@@ -12,7 +12,7 @@
 // Tiling: a workgroup of 8 waves owns a 128 x 128 (or 64 x 128) tile of C, each wave 32 x 64 (32 x 32) of it on
 // v_mfma_f32_32x32x16_bf16.  K runs in stages of 32: the fp32 A tile is split into its three pieces on the way into
 // LDS; W arrives pre-split and pre-tiled from the host (one contiguous 24 KiB block per stage:
-// wt[N/128][K/32][3 pieces][128 rows][32] bf16, egtr_amd/ops.py::gemm_split_weights).  The global loads of stage s + 1
+// wt[N/128][K/32][3 pieces][128 rows][32] bf16, egtr_amd/kernels/linear.py::gemm_split_weights).  The global loads of stage s + 1
 // are in flight (inline asm, counted) while stage s is multiplied out of LDS; rows are 80 bytes apart in LDS, which
 // makes the 16-byte operand reads of 32 consecutive rows conflict-free.  60 (45) KiB of LDS and <= 128 registers per
 // lane: two workgroups = sixteen waves per CU.
@@ -21,36 +21,15 @@
 #include <stdlib.h>
 
 #include "common.h"
-#include "xs_format.h"
+#include "x6_staged.h"
 
 namespace {
+using namespace x6;   // the staged main loop and its geometry (kBN, kBK, kPitch): x6_staged.h
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-constexpr int kBN = 128, kBK = 32;
-constexpr int kPitch = 40;  // bf16 elements per LDS row: 32 + 8 (80 bytes)
-
-__device__ __forceinline__ f32x16 mfma_bf16(bf16x8 a, bf16x8 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x4v gload(const void* p) {
-  f32x4v v;
-  asm volatile("global_load_dwordx4 %0, %1, off" : "=&v"(v) : "v"(p));
-  return v;
-}
-__device__ __forceinline__ void vm_wait0(f32x4v& v) { asm volatile("s_waitcnt vmcnt(0)" : "+v"(v)); }
-
-// exact truncation split (rel_head.hip): pieces as fp32 bit patterns with zero low halves.  xs::split3_fast (round 4; the
-// inf-safe xs::split3 until then): 4 VALU operations per element instead of 10 -- these kernels split every activation
-// element N / 128 times over, and the weight-gradient kernel both operands: 3-4.5 % off the forward / data-gradient products
-// and 8-9 % off the weight gradients at the training size (abl/gemm_fast.sh, two alternations on one box).  For a non-finite
-// element the lower pieces come out NaN (inf - inf), so ITS output row (weight gradient: its column) is NaN instead of a mix of
-// +-inf and NaN -- non-finite either way and nothing else is touched (tests/test_gpu_pinning.py).
-using Split3 = xs::Split3;
-__device__ __forceinline__ Split3 split3(float x) { return xs::split3_fast(x); }
-__device__ __forceinline__ unsigned pack_hi16(unsigned a, unsigned b) { return __builtin_amdgcn_perm(b, a, 0x07060302u); }
+// The activations are split with xs::split3_fast (round 4; the inf-safe xs::split3 until then): 4 VALU operations per element
+// instead of 10 -- these kernels split every activation element N / 128 times over, and the weight-gradient kernel both
+// operands: 3-4.5 % off the forward / data-gradient products and 8-9 % off the weight gradients at the training size
+// (abl/gemm_fast.sh, two alternations on one box).  What that does to a non-finite element: x6_staged.h, tests/test_gpu_pinning.py.
 
 // A workgroup is 8 waves on a BM x 128 tile, BM = 128 (wave tile 32 x 64) or 64 (wave tile 32 x 32; chosen when 128-row
 // tiles would not give every CU two workgroups).  <= 128 registers per lane: four waves per SIMD, so that the load /
@@ -61,14 +40,8 @@ __device__ __forceinline__ unsigned pack_hi16(unsigned a, unsigned b) { return _
 // Up to kMaxProblems independent products with the same M and K in ONE launch (the value projection and the offsets /
 // attention-weights projection of an encoder layer; the six value projections of the decoder): their tiles share the
 // grid, so that products which do not fill the chip on their own (196-588 tiles on 512 workgroup slots) fill it together.
-// Workgroups are dealt round-robin to the 8 XCDs (blockIdx % 8), each with its own L2.  Logical tile t = xcd_tile(...)
-// hands every XCD a CONTIGUOUS range of tiles, so that the tiles running side by side on one XCD are neighbours in the
-// tile order below and find the operand rows they share in that XCD's L2 (instead of every n block of a row tile
-// fetching the activation rows again through another L2).
-__device__ __forceinline__ int xcd_tile(int bid, int total) {
-  const int q = total >> 3, r = total & 7, x = bid & 7;
-  return x * q + min(x, r) + (bid >> 3);
-}
+// The tile order goes through xcd_tile (x6_common.h): the tiles running side by side on one XCD are neighbours in the order
+// below (instead of every n block of a row tile fetching the activation rows again through another L2).
 
 constexpr int kMaxProblems = 16;   // (the relation head's 14 slot products share one grid)
 struct GemmProblem {
@@ -140,7 +113,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     const int row = min(m0 + (idx >> 3), M - 1);
     arow[q] = A + (size_t)row * lda + 4 * (idx & 7);
   }
-  const char* wblk = reinterpret_cast<const char*>(Wt) + (size_t)nb * nk * (3 * kBN * kBK * 2) + (size_t)tid * 16;
+  const char* wblk = w_stage0(Wt, nb, nk, tid);
   const bool has_pos = G.pos != nullptr;   // uniform per workgroup
   const float* prow[AQ];
 #pragma unroll
@@ -158,17 +131,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 #pragma unroll
       for (int q = 0; q < AQ; ++q) rp[q] = gload(prow[q] + s * kBK);
     }
-    const char* wp = wblk + (size_t)s * (3 * kBN * kBK * 2);
-#pragma unroll
-    for (int q = 0; q < 3; ++q) rw[q] = gload(wp + q * 8192);
+    issue_w(rw, wblk, s);
   };
   auto stash = [&]() {
-    __bf16* sA = sbase;
-    __bf16* sW = sA + 3 * BM * kPitch;
-#pragma unroll
-    for (int q = 0; q < AQ; ++q) vm_wait0(ra[q]);
-#pragma unroll
-    for (int q = 0; q < 3; ++q) vm_wait0(rw[q]);
+    vm_wait0(ra);
+    vm_wait0(rw);
     if (has_pos) {
 #pragma unroll
       for (int q = 0; q < AQ; ++q) {
@@ -179,19 +146,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 #pragma unroll
     for (int q = 0; q < AQ; ++q) {
       const int idx = tid + 512 * q;
-      const int row = idx >> 3, c4 = idx & 7;
-      const Split3 s0 = split3(ra[q].x), s1 = split3(ra[q].y), s2 = split3(ra[q].z), s3 = split3(ra[q].w);
-      __bf16* p = sA + row * kPitch + 4 * c4;
-      *reinterpret_cast<uint2*>(p) = make_uint2(pack_hi16(s0.hi, s1.hi), pack_hi16(s2.hi, s3.hi));
-      *reinterpret_cast<uint2*>(p + BM * kPitch) = make_uint2(pack_hi16(s0.mid, s1.mid), pack_hi16(s2.mid, s3.mid));
-      *reinterpret_cast<uint2*>(p + 2 * BM * kPitch) = make_uint2(pack_hi16(s0.lo, s1.lo), pack_hi16(s2.lo, s3.lo));
+      stash_a4(sA + (idx >> 3) * kPitch + 4 * (idx & 7), ra[q], BM * kPitch);
     }
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      const int idx = tid + 512 * q;          // chunk of the stage block: [piece][row 128][4 chunks of 8 bf16]
-      const int piece = idx >> 9, row = (idx >> 2) & 127, c = idx & 3;
-      *reinterpret_cast<f32x4v*>(sW + (piece * kBN + row) * kPitch + 8 * c) = rw[q];
-    }
+    stash_w(sW, rw, tid);
   };
 
   f32x16 acc[NT];
@@ -200,48 +157,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[a][r] = 0.f;
 
-  issue(0);
-  stash();
-  __syncthreads();
-  const __bf16* pa0 = sA + (wm * 32 + li) * kPitch + 8 * hf;
-  const __bf16* pw0 = sW + (wn * (32 * NT) + li) * kPitch + 8 * hf;
-  auto compute = [&]() {
-    const __bf16* pa = pa0;
-    const __bf16* pw = pw0;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      bf16x8 a[3], w[NT][3];
-#pragma unroll
-      for (int p = 0; p < 3; ++p) {
-        a[p] = *reinterpret_cast<const bf16x8*>(pa + p * BM * kPitch + 16 * ks);
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-          w[t][p] = *reinterpret_cast<const bf16x8*>(pw + (p * kBN + t * 32) * kPitch + 16 * ks);
-      }
-#pragma unroll
-      for (int nt = 0; nt < NT; ++nt) {
-        f32x16 c = acc[nt];
-        c = mfma_bf16(w[nt][2], a[0], c);
-        c = mfma_bf16(w[nt][0], a[2], c);
-        c = mfma_bf16(w[nt][1], a[1], c);
-        c = mfma_bf16(w[nt][1], a[0], c);
-        c = mfma_bf16(w[nt][0], a[1], c);
-        c = mfma_bf16(w[nt][0], a[0], c);
-        acc[nt] = c;
-      }
-    }
-  };
-  // every iteration issues the loads of the NEXT stage, multiplies the current one out of LDS and stores the next one
-  // (issue and stash unconditionally paired: no path leaves a load in flight); the last stage is peeled
-#pragma unroll 1
-  for (int s = 0; s + 1 < nk; ++s) {
-    issue(s + 1);
-    compute();
-    __syncthreads();   // every wave has read stage s out of LDS
-    stash();
-    __syncthreads();
-  }
-  compute();
+  const __bf16* pa = sA + (wm * 32 + li) * kPitch + 8 * hf;
+  const __bf16* pw = sW + (wn * (32 * NT) + li) * kPitch + 8 * hf;
+  staged_loop(nk, issue, [&]() { stage_product<NT, BM>(pa, pw, acc); }, stash);
 
   // epilogue: D[i = n][j = m]; accumulator r <-> column n = (r & 3) + 8 (r >> 2) + 4 hf of the 32-wide n tile, row m =
   // lane & 31: one float4 (4 consecutive columns) per accumulator quad
@@ -386,19 +304,20 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
       }
     }
   };
+  // eight reduction rows of one column -> three 16-byte LDS row segments, one per piece
   auto stash_one = [&](const float (&v)[8], __bf16* base) {
-    Split3 sp[8];
+    xs::Split3 sp[8];
 #pragma unroll
-    for (int e = 0; e < 8; ++e) sp[e] = split3(v[e]);
+    for (int e = 0; e < 8; ++e) sp[e] = xs::split3_fast(v[e]);
     __bf16* p = base + col * kPitch + mq * 8;
-    *reinterpret_cast<uint4*>(p) = make_uint4(pack_hi16(sp[0].hi, sp[1].hi), pack_hi16(sp[2].hi, sp[3].hi),
-                                              pack_hi16(sp[4].hi, sp[5].hi), pack_hi16(sp[6].hi, sp[7].hi));
+    *reinterpret_cast<uint4*>(p) = make_uint4(xs::pack_hi16(sp[0].hi, sp[1].hi), xs::pack_hi16(sp[2].hi, sp[3].hi),
+                                              xs::pack_hi16(sp[4].hi, sp[5].hi), xs::pack_hi16(sp[6].hi, sp[7].hi));
     *reinterpret_cast<uint4*>(p + BM * kPitch) =
-        make_uint4(pack_hi16(sp[0].mid, sp[1].mid), pack_hi16(sp[2].mid, sp[3].mid), pack_hi16(sp[4].mid, sp[5].mid),
-                   pack_hi16(sp[6].mid, sp[7].mid));
+        make_uint4(xs::pack_hi16(sp[0].mid, sp[1].mid), xs::pack_hi16(sp[2].mid, sp[3].mid), xs::pack_hi16(sp[4].mid, sp[5].mid),
+                   xs::pack_hi16(sp[6].mid, sp[7].mid));
     *reinterpret_cast<uint4*>(p + 2 * BM * kPitch) =
-        make_uint4(pack_hi16(sp[0].lo, sp[1].lo), pack_hi16(sp[2].lo, sp[3].lo), pack_hi16(sp[4].lo, sp[5].lo),
-                   pack_hi16(sp[6].lo, sp[7].lo));
+        make_uint4(xs::pack_hi16(sp[0].lo, sp[1].lo), xs::pack_hi16(sp[2].lo, sp[3].lo), xs::pack_hi16(sp[4].lo, sp[5].lo),
+                   xs::pack_hi16(sp[6].lo, sp[7].lo));
   };
   auto stash = [&]() {
     stash_one(rg, sG);
@@ -413,29 +332,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 
   const __bf16* pa = sG + (wm * 32 + li) * kPitch + 8 * hf;
   const __bf16* pw = sX + (wn * 64 + li) * kPitch + 8 * hf;
-  auto compute = [&]() {
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      bf16x8 a[3], w[2][3];
-#pragma unroll
-      for (int p = 0; p < 3; ++p) {
-        a[p] = *reinterpret_cast<const bf16x8*>(pa + p * BM * kPitch + 16 * ks);
-#pragma unroll
-        for (int q = 0; q < 2; ++q) w[q][p] = *reinterpret_cast<const bf16x8*>(pw + (p * kBN + q * 32) * kPitch + 16 * ks);
-      }
-#pragma unroll
-      for (int nt = 0; nt < 2; ++nt) {
-        f32x16 c = acc[nt];
-        c = mfma_bf16(w[nt][2], a[0], c);
-        c = mfma_bf16(w[nt][0], a[2], c);
-        c = mfma_bf16(w[nt][1], a[1], c);
-        c = mfma_bf16(w[nt][1], a[0], c);
-        c = mfma_bf16(w[nt][0], a[1], c);
-        c = mfma_bf16(w[nt][0], a[0], c);
-        acc[nt] = c;
-      }
-    }
-  };
+  // This kernel keeps its own copy of x6::staged_loop and of the stash: routed through the shared ones its instruction stream
+  // changed (the other two kernels' did too, within their parents' run-to-run spread) and every weight gradient measured 0.3-0.4 us
+  // (1 %) slower, outside that spread (profiles/x6_staged_refactor.txt).  As written here the stream is the earlier one, bit for bit.
+  auto compute = [&]() { stage_product<2, BM>(pa, pw, acc); };
   if (nstage > 0) {
     issue(0);
     stash();
@@ -444,7 +344,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     for (int s = 0; s + 1 < nstage; ++s) {
       issue(s + 1);
       compute();
-      __syncthreads();
+      __syncthreads();   // every wave has read stage s out of LDS
       stash();
       __syncthreads();
     }
@@ -502,10 +402,24 @@ WgradPlan wgrad_plan(int M, int N, int K) {
 // W [N, K] fp32 (or its transpose: `transposed`, element (n, k) at w[k * ldw + n]) -> the operand stream of the kernel
 // above, [N/128][K/32][3 pieces][128][32] bf16.  Pieces are rounded to nearest even like ops._split3_bf16 (the residuals
 // stay exact in fp32); one thread per element, consecutive threads along k of one row -> 64-byte output segments.
-__device__ __forceinline__ unsigned bf16_rne(float x) {
-  const unsigned u = __float_as_uint(x);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return 0x7fc0u;
-  return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+// Thread idx of a [N, K] weight takes element (k = idx & 31, n = (idx >> 5) & 127) of stage block idx >> 12: returns the slot
+// of its hi piece in the stream, (n, k) the element's place in the weight.
+__device__ __forceinline__ unsigned short* tiled_slot(unsigned short* out, int idx, int K, int& n, int& k) {
+  const int kk = idx & 31, nn = (idx >> 5) & 127, blk = idx >> 12;
+  const int ktiles = K / kBK;
+  n = (blk / ktiles) * kBN + nn;
+  k = (blk % ktiles) * kBK + kk;
+  return out + (size_t)blk * kWStageElems + nn * kBK + kk;
+}
+// (xs::bf16_rne_bits, not xs::split3_rne: a non-finite weight keeps the NaN residuals inf - inf it always had here)
+__device__ __forceinline__ void store_split_rne(unsigned short* o, float x) {
+  const unsigned hi = xs::bf16_rne_bits(x);
+  const float r1 = x - __uint_as_float(hi);
+  const unsigned mid = xs::bf16_rne_bits(r1);
+  const unsigned lo = xs::bf16_rne_bits(r1 - __uint_as_float(mid));
+  o[0] = (unsigned short)(hi >> 16);
+  o[kWPieceElems] = (unsigned short)(mid >> 16);
+  o[2 * kWPieceElems] = (unsigned short)(lo >> 16);
 }
 // `pair`: the second half of the grid writes the tiling of W^T behind the first one (out + 3 N K), so that the forward
 // of a training step prepares the operand of its data-gradient product in the same launch.
@@ -521,18 +435,9 @@ __global__ __launch_bounds__(256) void tile_weights_f32(const float* __restrict_
     K = t;
   }
   if (idx >= N * K) return;
-  const int kk = idx & 31, nn = (idx >> 5) & 127, blk = idx >> 12;
-  const int ktiles = K / kBK, kt = blk % ktiles, nt = blk / ktiles;
-  const int n = nt * kBN + nn, k = kt * kBK + kk;
-  const float x = transposed ? w[(size_t)k * ldw + n] : w[(size_t)n * ldw + k];
-  const unsigned hi = bf16_rne(x);
-  const float r1 = x - __uint_as_float(hi << 16);
-  const unsigned mid = bf16_rne(r1);
-  const unsigned lo = bf16_rne(r1 - __uint_as_float(mid << 16));
-  unsigned short* o = out + (size_t)blk * (3 * kBN * kBK) + nn * kBK + kk;
-  o[0] = (unsigned short)hi;
-  o[kBN * kBK] = (unsigned short)mid;
-  o[2 * kBN * kBK] = (unsigned short)lo;
+  int n, k;
+  unsigned short* o = tiled_slot(out, idx, K, n, k);
+  store_split_rne(o, transposed ? w[(size_t)k * ldw + n] : w[(size_t)n * ldw + k]);
 }
 
 // Several weights in ONE launch (a training step re-tiles every encoder weight after each optimizer step: 5 launches + 2
@@ -564,19 +469,10 @@ __global__ __launch_bounds__(256) void tile_weights_multi_f32(TileProblems P, in
     K = t;
   }
   if (idx >= N * K) return;
-  const int kk = idx & 31, nn = (idx >> 5) & 127, blk = idx >> 12;
-  const int ktiles = K / kBK, kt = blk % ktiles, nt = blk / ktiles;
-  const int n = nt * kBN + nn, k = kt * kBK + kk;
+  int n, k;
+  unsigned short* o = tiled_slot(out, idx, K, n, k);
   const int r = transposed ? k : n, c = transposed ? n : k;   // element (r, c) of the untransposed weight
-  const float x = r < T.split ? T.w[(size_t)r * T.ldw + c] : T.w2[(size_t)(r - T.split) * T.ldw2 + c];
-  const unsigned hi = bf16_rne(x);
-  const float r1 = x - __uint_as_float(hi << 16);
-  const unsigned mid = bf16_rne(r1);
-  const unsigned lo = bf16_rne(r1 - __uint_as_float(mid << 16));
-  unsigned short* o = out + (size_t)blk * (3 * kBN * kBK) + nn * kBK + kk;
-  o[0] = (unsigned short)hi;
-  o[kBN * kBK] = (unsigned short)mid;
-  o[2 * kBN * kBK] = (unsigned short)lo;
+  store_split_rne(o, r < T.split ? T.w[(size_t)r * T.ldw + c] : T.w2[(size_t)(r - T.split) * T.ldw2 + c]);
 }
 
 }  // namespace

@@ -11,8 +11,9 @@
 //
 // Arithmetic and main loop: those of gemm_split_bf16_f32<64> (gemm_split.hip) -- activations split by truncation on their way
 // into LDS, weights pre-split round-to-nearest and pre-tiled [N/128][K/32][3 pieces][128][32] bf16 (one contiguous 24 KiB
-// block per K stage, so a K range is a range of blocks), six bf16 MFMAs per K = 16, fp32 accumulation.  Nothing is shared
-// with that file through a header: its compiled code is untouched.
+// block per K stage, so a K range is a range of blocks), six bf16 MFMAs per K = 16, fp32 accumulation.  The loop and its
+// pieces are the shared ones of x6_staged.h; this file keeps the unit mapping, the A-row addressing, the split accumulator
+// and the plan.
 //
 // A-row addressing: *plain* -- row r of the level's [M, K] token matrix; *3x3 / stride 2 / padding 1* -- an implicit GEMM over
 // the channels-last map [B, H, W, C] with K = 9 C laid out [dy][dx][c]: output pixel (b, y, x) reads input pixel
@@ -22,29 +23,15 @@
 #include <stdint.h>
 
 #include "common.h"
-#include "xs_format.h"
+#include "x6_staged.h"
 
 namespace {
+using namespace x6;   // the staged main loop and its geometry (kBN, kBK, kPitch): x6_staged.h
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-constexpr int kBM = 64, kBN = 128, kBK = 32, kN = 256;
-constexpr int kPitch = 40;        // bf16 elements per LDS row: 32 + 8 (80 bytes: conflict-free 16-byte operand reads)
+constexpr int kBM = 64, kN = 256;
 constexpr int kMaxLevels = 4;
 constexpr int kMaxPiece = 512;    // no unit walks more than this much of K
 constexpr int kSlots = 512;       // resident workgroups of the chip: 256 CUs x 2 (45 KiB of LDS, 16 waves per CU)
-
-__device__ __forceinline__ f32x16 mfma_bf16(bf16x8 a, bf16x8 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x4v gload(const void* p) {
-  f32x4v v;
-  asm volatile("global_load_dwordx4 %0, %1, off" : "=&v"(v) : "v"(p));
-  return v;
-}
-__device__ __forceinline__ void vm_wait0(f32x4v& v) { asm volatile("s_waitcnt vmcnt(0)" : "+v"(v)); }
 
 struct IpLevel {
   const float* A;             // plain: [M, K]; 3x3: [B, H, W, C]
@@ -104,7 +91,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     ix0 = 2 * x - 1;
     aimg = A + (size_t)b * G.H * G.W * G.C + 4 * c4;
   }
-  const char* wblk = reinterpret_cast<const char*>(G.Wt) + (size_t)nb * (G.K / kBK) * (3 * kBN * kBK * 2) + (size_t)tid * 16;
+  const char* wblk = w_stage0(G.Wt, nb, G.K / kBK, tid);
 
   f32x4v ra, rw[3];
   bool live = true;   // false: this row's tap of the stage in flight lies outside the image
@@ -120,76 +107,25 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
       ap = aplain + (size_t)st * kBK;
     }
     ra = gload(ap);
-    const char* wp = wblk + (size_t)st * (3 * kBN * kBK * 2);
-#pragma unroll
-    for (int q = 0; q < 3; ++q) rw[q] = gload(wp + q * 8192);
+    issue_w(rw, wblk, st);
   };
   auto stash = [&]() {
     vm_wait0(ra);
-#pragma unroll
-    for (int q = 0; q < 3; ++q) vm_wait0(rw[q]);
+    vm_wait0(rw);
     if (!live) ra = f32x4v{0.f, 0.f, 0.f, 0.f};
-    {
-      const xs::Split3 s0 = xs::split3_fast(ra.x), s1 = xs::split3_fast(ra.y), s2 = xs::split3_fast(ra.z),
-                       s3 = xs::split3_fast(ra.w);
-      __bf16* p = sA + lrow * kPitch + 4 * c4;
-      *reinterpret_cast<uint2*>(p) = make_uint2(xs::pack_hi16(s0.hi, s1.hi), xs::pack_hi16(s2.hi, s3.hi));
-      *reinterpret_cast<uint2*>(p + kBM * kPitch) = make_uint2(xs::pack_hi16(s0.mid, s1.mid), xs::pack_hi16(s2.mid, s3.mid));
-      *reinterpret_cast<uint2*>(p + 2 * kBM * kPitch) = make_uint2(xs::pack_hi16(s0.lo, s1.lo), xs::pack_hi16(s2.lo, s3.lo));
-    }
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      const int idx = tid + 512 * q;   // chunk of the stage block: [piece][row 128][4 chunks of 8 bf16]
-      const int piece = idx >> 9, wr = (idx >> 2) & 127, c = idx & 3;
-      *reinterpret_cast<f32x4v*>(sW + (piece * kBN + wr) * kPitch + 8 * c) = rw[q];
-    }
+    stash_a4(sA + lrow * kPitch + 4 * c4, ra, kBM * kPitch);
+    stash_w(sW, rw, tid);
   };
 
-  // Two accumulators: the leading products w_hi a_hi in one, the five small cross terms (2^-8 and less of them) in the other,
-  // added once at the end.  The matrix pipe aligns the accumulator with the largest product of an instruction and drops what
-  // falls below its last place TOWARDS ZERO; with one accumulator the small terms gathered so far lose those bits in every
-  // k-step, a bias that grows with the chain -- at K = 18 432 it reached 20 x the six-term model's own error on operands whose
-  // leading products cancel (tests/test_gpu_input_proj_x6.py), whatever the number of K ranges.
+  // Two accumulators (x6::mfma6_split says why): the five small cross terms in one, the leading products w_hi a_hi in the
+  // other, added once at the end.  MFMA roles as in gemm_split: A operand = weight piece (i = n), B operand = activation piece
   f32x16 acc, acc_hi;
 #pragma unroll
   for (int r = 0; r < 16; ++r) acc[r] = acc_hi[r] = 0.f;
 
-  issue(0);
-  stash();
-  __syncthreads();
-  const __bf16* pa0 = sA + (wm * 32 + li) * kPitch + 8 * hf;
-  const __bf16* pw0 = sW + (wn * 32 + li) * kPitch + 8 * hf;
-  // MFMA roles as in gemm_split: A operand = weight piece (i = n), B operand = activation piece (j = m); small terms first
-  auto compute = [&]() {
-#pragma unroll
-    for (int k2 = 0; k2 < 2; ++k2) {
-      bf16x8 a[3], w[3];
-#pragma unroll
-      for (int p = 0; p < 3; ++p) {
-        a[p] = *reinterpret_cast<const bf16x8*>(pa0 + p * kBM * kPitch + 16 * k2);
-        w[p] = *reinterpret_cast<const bf16x8*>(pw0 + p * kBN * kPitch + 16 * k2);
-      }
-      f32x16 c = acc;
-      c = mfma_bf16(w[2], a[0], c);
-      c = mfma_bf16(w[0], a[2], c);
-      c = mfma_bf16(w[1], a[1], c);
-      c = mfma_bf16(w[1], a[0], c);
-      c = mfma_bf16(w[0], a[1], c);
-      acc = c;
-      acc_hi = mfma_bf16(w[0], a[0], acc_hi);
-    }
-  };
-  // every iteration issues the loads of the NEXT stage, multiplies the current one out of LDS and stores the next one (issue
-  // and stash unconditionally paired: no path leaves a load in flight); the last stage is peeled
-#pragma unroll 1
-  for (int s = 0; s + 1 < nstage; ++s) {
-    issue(s + 1);
-    compute();
-    __syncthreads();   // every wave has read stage s out of LDS
-    stash();
-    __syncthreads();
-  }
-  compute();
+  const __bf16* pa = sA + (wm * 32 + li) * kPitch + 8 * hf;
+  const __bf16* pw = sW + (wn * 32 + li) * kPitch + 8 * hf;
+  staged_loop(nstage, issue, [&]() { stage_product_split<kBM>(pa, pw, acc, acc_hi); }, stash);
 #pragma unroll
   for (int r = 0; r < 16; ++r) acc[r] += acc_hi[r];
 

@@ -604,10 +604,8 @@ constexpr int kHp = 264;  // bf16 elements per LDS row of an h1 piece
 // them are packed into one dword of bf16 pairs with a single v_perm_b32.
 // (xs_format.h: non-finite x keeps the inf / a quiet NaN in hi alone, mid = lo = 0 -- `x - hi` would be inf - inf)
 typedef float f32x2v __attribute__((ext_vector_type(2)));
-using Split3 = xs::Split3;
-__device__ __forceinline__ Split3 split3(float x) { return xs::split3(x); }
-// {bf16(a) in the low half, bf16(b) in the high half} from two fp32 bit patterns with zero low halves
-__device__ __forceinline__ unsigned pack_hi16(unsigned a, unsigned b) { return __builtin_amdgcn_perm(b, a, 0x07060302u); }
+using xs::pack_hi16;
+using xs::Split3;
 
 __device__ __forceinline__ f32x4v gload_b128_s(unsigned voff, const void* sbase) {
   f32x4v v;

@@ -54,11 +54,6 @@ struct X6Problems {
   X6Problem p[kMaxProblems];
 };
 
-__device__ __forceinline__ int xcd_tile(int bid, int total) {   // every XCD owns a contiguous range of the tile order
-  const int q = total >> 3, r = total & 7, x = bid & 7;
-  return x * q + min(x, r) + (bid >> 3);
-}
-
 // MT = 32-row MFMA tiles per wave along m (2: workgroup tile 128 x 128).
 template <int MT>
 __global__ __launch_bounds__(256, 2) void gemm_x6_kernel(X6Problems P, int nprob, int M, int K) {
