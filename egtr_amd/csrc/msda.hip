@@ -924,6 +924,9 @@ int egtr_launch_msda_bwd_value_tile_f32(hipStream_t st, const void* grad_out, bo
                                         const int64_t* lsi, const float* loc, const float* attn, float* grad_value,
                                         int B, int Lq, int S, int L, int P, unsigned* counters, bool det);
 unsigned* egtr_msda_tile_counters(hipStream_t st);   // eight work counters private to one launch pair (msda_tile.hip)
+// Largest spatial_size the value-tile kernel serves: the window of one (query tile, head) item holds at most sum H_l W_l <=
+// spatial_size pixels (the levels do not overlap), and the kernel packs a window pixel id into 16 bits.
+constexpr int kTileMaxSpatial = 65536;
 
 
 // ---- deterministic route (fixed_accum.h): grad_value accumulated in 64-bit fixed point with integer atomics ----------------
@@ -1069,7 +1072,8 @@ int msda_backward_det(hipStream_t st, const void* grad_out, const void* value, c
 // variant: 0 = automatic, 1 = wave-per-query with per-sample global atomics (reference scheme), 2 = two kernels:
 // wave-per-query for grad_attn / grad_loc (no atomics) + query-tile x head MFMA accumulation of grad_value
 // (msda_tile.hip), 3 = generic.  Automatic = 2 for encoder-shaped calls (Lq == S: queries are the pixels, so tiles
-// have compact windows), 1 for short / arbitrary query lists, 3 for shapes other than M = 8, D = 32, L*P = 16.
+// have compact windows) of at most 65 536 pixels, 1 for short / arbitrary query lists and larger encoder-shaped calls, 3 for
+// shapes other than M = 8, D = 32, L*P = 16.  An explicit 2 above 65 536 pixels is EGTR_E_UNSUPPORTED.
 namespace {
 // zero_inside: grad_value arrives uninitialised and is cleared here -- by the wave-per-query kernel itself where the value-tile
 // kernel follows it (variant 2), by a memset on the stream otherwise
@@ -1091,8 +1095,11 @@ int msda_backward_f32_impl(egtr_stream_t stream, const void* grad_out, const voi
   const long long nq = (long long)batch * num_query;
   const bool fast = fast_shape(num_heads, channels, num_levels, num_point) &&
                     (long long)spatial_size * 1024 < (1ll << 31) && nq < (1ll << 27);
-  if (variant == 0) variant = fast ? ((num_query == spatial_size && num_query >= 256) ? 2 : 1) : 3;
+  // the value-tile kernel keeps window pixel ids in 16 bits (kTileMaxSpatial above): larger encoder-shaped calls take variant 1
+  if (variant == 0)
+    variant = fast ? ((num_query == spatial_size && num_query >= 256 && spatial_size <= kTileMaxSpatial) ? 2 : 1) : 3;
   if ((variant == 1 || variant == 2) && !fast) return EGTR_E_UNSUPPORTED;
+  if (variant == 2 && spatial_size > kTileMaxSpatial) return EGTR_E_UNSUPPORTED;
   if (bf16_ops && variant == 3) return EGTR_E_UNSUPPORTED;
   if (det_ws != nullptr)
     return msda_backward_det(st, grad_out, value, spatial_shapes, level_start_index, sampling_loc, attn_weight, batch,

@@ -28,8 +28,11 @@ constexpr int kRecStride = 17;  // record entries per query (16 samples + 1 pad:
 //   T[q, c]     (64 x 32)           = grad_out of the tile for this head,
 // evaluated on the matrix cores with v_mfma_f32_32x32x2_f32 (exact f32); G is then added to global memory with ONE
 // coalesced atomic per window element (32 lanes = 128 contiguous bytes).  The windows of the L levels are concatenated
-// into one virtual pixel range that is processed in chunks of kChunk columns, so any window size is handled (more
-// chunks, never a different code path).  History: per-(sample, corner, channel) global atomics as in
+// into one virtual pixel range that is processed in chunks of kChunk columns, so a window of up to 65 536 pixels is handled
+// (more chunks, never a different code path).  That limit is the 16-bit pixel id of the per-sample records (s_vp): an id is
+// below ntot = the sum of the level windows of the item.  Precondition: the levels do not overlap (sum H_l W_l <= S), so
+// ntot <= S, and the callers in msda.hip send only calls with S <= 65 536 here (larger ones take the per-sample atomics of
+// variant 1; an explicit variant 2 is refused with EGTR_E_UNSUPPORTED).  History: per-(sample, corner, channel) global atomics as in
 // the reference (cuh:125-152) = 2.4 ms per encoder launch; LDS ds_add_f32 accumulation = 1.2 ms (LDS float atomics
 // are serialised per lane, ~130 cycles per instruction).
 // kChunk: columns of A per pass (multiple of 32).  448 -> 115 KB of A, one workgroup per CU.  Measured round 2 with two

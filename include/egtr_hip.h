@@ -94,7 +94,11 @@ int egtr_msda_forward_fused_box_f32(egtr_stream_t stream, const float* value, co
                                     const float* value_bias);
 
 /* grad_value [B,S,M,D] MUST be zero-initialised by the caller (accumulated with atomics, as cu:124 relies on);
- * grad_sampling_loc [B,Lq,M,L,P,2] and grad_attn_weight [B,Lq,M,L,P] are fully overwritten. */
+ * grad_sampling_loc [B,Lq,M,L,P,2] and grad_attn_weight [B,Lq,M,L,P] are fully overwritten.
+ * Precondition of every backward entry: the levels do not overlap (level l owns rows level_start_index[l] ..
+ * + H_l * W_l of value, so sum H_l * W_l <= spatial_size).  Encoder-shaped calls (num_query == spatial_size >= 256) of the
+ * fast shapes accumulate grad_value per query tile on the matrix cores up to spatial_size = 65 536 (window pixel ids are 16
+ * bits wide there); larger ones take the per-sample atomics of every other call. */
 int egtr_msda_backward_f32(egtr_stream_t stream, const float* grad_out, const float* value,
                            const int64_t* spatial_shapes, const int64_t* level_start_index,
                            const float* sampling_loc, const float* attn_weight, int batch, int spatial_size,
@@ -103,7 +107,7 @@ int egtr_msda_backward_f32(egtr_stream_t stream, const float* grad_out, const fl
 
 /* The same backward with ALL three gradients written by the call: grad_value need not be initialised -- what the reference's
  * op does one level up, where `ms_deform_attn_cuda_backward` allocates `at::zeros_like(value)` itself
- * (model/custom_kernel/cuda/ms_deform_attn_cuda.cu:124).  Encoder-shaped calls (num_query == spatial_size) clear grad_value
+ * (model/custom_kernel/cuda/ms_deform_attn_cuda.cu:124).  Encoder-shaped calls (num_query == spatial_size <= 65 536) clear grad_value
  * inside the first kernel of the pair instead of in a 4 * B * S * 256-byte fill launch; other shapes run a memset on the stream. */
 int egtr_msda_backward_out_f32(egtr_stream_t stream, const float* grad_out, const float* value,
                                const int64_t* spatial_shapes, const int64_t* level_start_index,

@@ -22,7 +22,8 @@ int egtr_msda_forward_f32_variant(egtr_stream_t stream, const float* value, cons
 
 /* Same with an explicit kernel choice (A/B parity tests): 0 = automatic, 1 = wave-per-query with one global atomic per
  * (sample, corner, channel) like the reference, 2 = grad_attn / grad_loc by the wave-per-query kernel + grad_value as a
- * dense product per (query tile, head) on the matrix cores (encoder-shaped calls), 3 = generic. */
+ * dense product per (query tile, head) on the matrix cores (encoder-shaped calls; spatial_size <= 65 536, else
+ * EGTR_E_UNSUPPORTED: window pixel ids are 16 bits wide), 3 = generic. */
 int egtr_msda_backward_f32_variant(egtr_stream_t stream, const float* grad_out, const float* value,
                                    const int64_t* spatial_shapes, const int64_t* level_start_index,
                                    const float* sampling_loc, const float* attn_weight, int batch, int spatial_size,
