@@ -304,6 +304,19 @@ def _pos_rows(position_embeddings):
     return p.reshape(-1, p.shape[-1])
 
 
+def _pair(out):
+    """The result of a fused kernel that returns y, or (y, y + pos) when it was handed position rows, as (y, y + pos or None)."""
+    return out if isinstance(out, tuple) else (out, None)
+
+
+def _head_maps(states, num_heads):
+    """[B, N, d] projections as the retained maps [B, M, N, D] of dd:1179-1185.  These are pure re-layouts: handed out as
+    transposed VIEWS -- same shape and values as the reference's tensors, no copy, and gradients flow back through ordinary
+    autograd (the relation head reshapes them straight back to [B, N, M*D])."""
+    b, n, d = states.shape
+    return states.reshape(b, n, num_heads, d // num_heads).transpose(1, 2)
+
+
 # ---------------------------------------------------------------------------------------- attention modules
 class DeformableDetrMultiscaleDeformableAttention(nn.Module):
     """Multi-scale deformable attention (dd:963-1104); the sample + weighted-sum core runs in HIP."""
@@ -347,10 +360,10 @@ class DeformableDetrMultiscaleDeformableAttention(nn.Module):
     def with_pos_embed(self, tensor: torch.Tensor, position_embeddings: Optional[Tensor]):
         return tensor if position_embeddings is None else tensor + position_embeddings
 
-    def lazy_pos_supported(self, hidden_states, encoder_hidden_states):
-        """True when forward() takes the route whose offsets / weights projection can add the position embeddings itself
-        (token-sized self-attention at inference: value projection and that projection share one split-GEMM launch)."""
-        if not (ops.LAZY_POS and torch.is_tensor(hidden_states) and ops.inference_fast_path(hidden_states)):
+    def _shares_split_launch(self, hidden_states, encoder_hidden_states):
+        """True when the value projection and the offsets / weights projection share one split-GEMM launch: token-sized
+        self-attention at inference (the two read the same number of rows and neither fills the chip)."""
+        if not (torch.is_tensor(hidden_states) and ops.inference_fast_path(hidden_states)):
             return False
         rows = hidden_states.shape[0] * hidden_states.shape[1]
         return (rows > ops.SKINNY_MAX_ROWS and hidden_states.shape[:2] == encoder_hidden_states.shape[:2]
@@ -358,30 +371,32 @@ class DeformableDetrMultiscaleDeformableAttention(nn.Module):
                 and ops.gemm_split_supported(hidden_states, 3 * self.n_heads * self.n_levels * self.n_points,
                                              hidden_states.shape[-1]))
 
+    def lazy_pos_supported(self, hidden_states, encoder_hidden_states):
+        """True when forward() takes the route whose offsets / weights projection can add the position embeddings itself."""
+        return ops.LAZY_POS and self._shares_split_launch(hidden_states, encoder_hidden_states)
+
     def forward(self, hidden_states: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
                 encoder_hidden_states=None, encoder_attention_mask=None,
                 position_embeddings: Optional[torch.Tensor] = None, reference_points=None, spatial_shapes=None,
                 level_start_index=None, output_attentions: bool = False, spatial_shapes_list=None,
-                hidden_with_pos=None, precomputed_value=None, residual_ln=None, mask_bits=None):
+                hidden_with_pos=None, precomputed_value=None, mask_bits=None):
+        output, attention_weights = self.sample(
+            hidden_states, attention_mask, encoder_hidden_states, position_embeddings, reference_points, spatial_shapes,
+            level_start_index, output_attentions, spatial_shapes_list, hidden_with_pos, precomputed_value, mask_bits)
+        return ops.module_linear(self.output_proj, output), attention_weights
+
+    def sample(self, hidden_states, attention_mask=None, encoder_hidden_states=None, position_embeddings=None,
+               reference_points=None, spatial_shapes=None, level_start_index=None, output_attentions=False,
+               spatial_shapes_list=None, hidden_with_pos=None, precomputed_value=None, mask_bits=None):
+        """forward() up to, not including, ``output_proj``: (sampled values [B, Lq, d], attention weights).  A caller that
+        fuses the output projection into its own tail (the encoder layer) calls this instead of forward()."""
         # mask_bits: ``attention_mask`` packed one bit per token (ops.level_geometry's fifth result), handed down explicitly
         # by DeformableDetrModel.forward for the fused inference kernel; None: the kernel reads / packs the byte mask.
         # hidden_with_pos / precomputed_value: inference-only hand-ins that save launches (the previous LayerNorm
         # kernel also wrote hidden + pos; the decoder projects the values of all its layers in one batched GEMM)
-        deferred = hidden_states if isinstance(hidden_states, ops.DeferredLayerNorm) else None
-        lazy_pos = None
-        if deferred is not None:
-            pass   # LayerNorm (+ pos) runs as the prologue of the offsets / weights projection below
-        elif hidden_with_pos is not None:
-            hidden_states = hidden_with_pos
-        elif position_embeddings is not None:
-            if precomputed_value is None and self.lazy_pos_supported(hidden_states, encoder_hidden_states):
-                # encoder self-attention at inference: the split GEMM of the offsets / weights projection adds the position
-                # rows while it loads its operand -- `hidden + pos` (dd:1041) is never materialised
-                lazy_pos = _pos_rows(position_embeddings)
-            else:
-                hidden_states = self.with_pos_embed(hidden_states, position_embeddings)
-        batch_size, num_queries, _ = hidden_states.shape
-        batch_size, sequence_length, _ = encoder_hidden_states.shape
+        query, lazy_pos = self._query_input(hidden_states, encoder_hidden_states, position_embeddings, hidden_with_pos,
+                                            precomputed_value)
+        sequence_length = encoder_hidden_states.shape[1]
         # dd:1044-1047; done on the host copy of the shapes when the caller has one (no device sync)
         if spatial_shapes_list is not None:
             total = sum(h * w for h, w in spatial_shapes_list)
@@ -389,45 +404,69 @@ class DeformableDetrMultiscaleDeformableAttention(nn.Module):
             total = int((spatial_shapes[:, 0] * spatial_shapes[:, 1]).sum())
         if total != sequence_length:
             raise ValueError("Make sure to align the spatial shapes with the sequence length of the encoder hidden states")
+        value, value_bias, value_is_masked = self._project_value(query, encoder_hidden_states, attention_mask,
+                                                                 precomputed_value)
+        value, offsets, logits, joint = self._project_offsets_weights(query, encoder_hidden_states, position_embeddings,
+                                                                      lazy_pos, value)
+        return self._sample(value, value_bias, value_is_masked, sequence_length, offsets, logits, joint, reference_points,
+                            spatial_shapes, level_start_index, attention_mask, mask_bits, output_attentions)
 
-        fast = deferred is not None or ops.inference_fast_path(hidden_states)
-        value_is_masked = True
-        value_bias = None
-        both_train = None
+    def _query_input(self, hidden_states, encoder_hidden_states, position_embeddings, hidden_with_pos, precomputed_value):
+        """The operand of the offsets / weights projection (dd:1041 ``hidden + pos``): (operand, the position rows that
+        projection still has to add -- or None)."""
+        if isinstance(hidden_states, ops.DeferredLayerNorm):
+            return hidden_states, None   # LayerNorm (+ pos) runs as the prologue of the offsets / weights projection
+        if hidden_with_pos is not None:
+            return hidden_with_pos, None
+        if position_embeddings is None:
+            return hidden_states, None
+        if precomputed_value is None and self.lazy_pos_supported(hidden_states, encoder_hidden_states):
+            # encoder self-attention at inference: the split GEMM of the offsets / weights projection adds the position
+            # rows while it loads its operand -- `hidden + pos` (dd:1041) is never materialised
+            return hidden_states, _pos_rows(position_embeddings)
+        return self.with_pos_embed(hidden_states, position_embeddings), None
+
+    def _project_value(self, query, encoder_hidden_states, attention_mask, precomputed_value):
+        """Stage 1, the value projection (dd:1050-1052): (value, the bias still to add, whether its padded rows need no
+        zeroing any more).  ``value`` None: the projection shares the launch of stage 2."""
         if isinstance(precomputed_value, tuple):
-            # (W x, b): the bias-free projection; bias and padding mask are applied by the fused kernel below
-            value, value_bias = precomputed_value
-            value_is_masked = attention_mask is None
-        elif precomputed_value is not None:
-            value = precomputed_value
-        else:
-            value = None   # projected below (token-sized inputs: together with the offsets / weights projection)
-            value_is_masked = attention_mask is None
-            if not (fast and batch_size * num_queries > ops.SKINNY_MAX_ROWS
-                    and hidden_states.shape[:2] == encoder_hidden_states.shape[:2]
-                    and ops.gemm_split_supported(encoder_hidden_states, *self.value_proj.weight.shape)
-                    and ops.gemm_split_supported(hidden_states, 3 * self.n_heads * self.n_levels * self.n_points,
-                                                 hidden_states.shape[-1])):
-                value = ops.module_linear(self.value_proj, encoder_hidden_states)
-        if deferred is not None:
+            # (W x, b): the bias-free projection; bias and padding mask are applied by the fused kernel of stage 3
+            return precomputed_value[0], precomputed_value[1], attention_mask is None
+        if precomputed_value is not None:
+            return precomputed_value, None, True
+        if self._shares_split_launch(query, encoder_hidden_states):
+            return None, None, attention_mask is None   # token-sized inputs: projected together with the offsets / weights
+        return ops.module_linear(self.value_proj, encoder_hidden_states), None, attention_mask is None
+
+    def _project_offsets_weights(self, query, encoder_hidden_states, position_embeddings, lazy_pos, value):
+        """Stage 2, the sampling-offset and attention-weight projections of ``query`` (dd:1053-1054), and the value projection
+        where stage 1 left it to this launch: (value, offsets [B, Lq, M*L*P*2], logits [B, Lq, M*L*P], the [B, Lq, 3*M*L*P]
+        buffer that both are column blocks of on the training route -- or None)."""
+        deferred = isinstance(query, ops.DeferredLayerNorm)
+        batch_size, num_queries, _ = query.shape
+        fast = deferred or ops.inference_fast_path(query)
+        if deferred:
             dpos = _pos_rows(position_embeddings) if position_embeddings is not None else None
             sampling_offsets, attention_weights = ops.linear_grouped([
-                dict(x=deferred, pos=dpos, w=self.sampling_offsets.weight, b=self.sampling_offsets.bias),
-                dict(x=deferred, pos=dpos, w=self.attention_weights.weight, b=self.attention_weights.bias)])
-        elif fast and batch_size * num_queries <= ops.SKINNY_MAX_ROWS:
+                dict(x=query, pos=dpos, w=self.sampling_offsets.weight, b=self.sampling_offsets.bias),
+                dict(x=query, pos=dpos, w=self.attention_weights.weight, b=self.attention_weights.bias)])
+            return value, sampling_offsets, attention_weights, None
+        if fast and batch_size * num_queries <= ops.SKINNY_MAX_ROWS:
             sampling_offsets, attention_weights = ops.linear_grouped([
-                dict(x=hidden_states, w=self.sampling_offsets.weight, b=self.sampling_offsets.bias),
-                dict(x=hidden_states, w=self.attention_weights.weight, b=self.attention_weights.bias)])
-        elif fast:
+                dict(x=query, w=self.sampling_offsets.weight, b=self.sampling_offsets.bias),
+                dict(x=query, w=self.attention_weights.weight, b=self.attention_weights.bias)])
+            return value, sampling_offsets, attention_weights, None
+        n_off = self.sampling_offsets.weight.shape[0]
+        if fast:
             # token-sized input: both Linears read the same rows -> one vendor GEMM over the concatenated weights; the
-            # kernel below reads the two column blocks in place (row stride = 3 * M * L * P)
+            # kernel of stage 3 reads the two column blocks in place (row stride = 3 * M * L * P)
             w_cat, b_cat = ops.cached_weights(
                 self, "msda_offsets_weights",
                 [self.sampling_offsets.weight, self.attention_weights.weight, self.sampling_offsets.bias,
                  self.attention_weights.bias],
                 lambda: (torch.cat([self.sampling_offsets.weight, self.attention_weights.weight], 0).contiguous(),
                          torch.cat([self.sampling_offsets.bias, self.attention_weights.bias], 0).contiguous()))
-            if ops.gemm_split_supported(hidden_states, w_cat.shape[0], w_cat.shape[1]):
+            if ops.gemm_split_supported(query, w_cat.shape[0], w_cat.shape[1]):
                 wt = ops.cached_weights(self, "msda_offsets_weights_split",
                                         [self.sampling_offsets.weight, self.attention_weights.weight],
                                         lambda: ops.gemm_split_weights(w_cat))
@@ -438,32 +477,33 @@ class DeformableDetrMultiscaleDeformableAttention(nn.Module):
                     wv = ops.cached_weights(vp, "gemm_split_bf16", [vp.weight], lambda: ops.gemm_split_weights(vp.weight))
                     value, both = ops.linear_split_bf16_grouped([
                         dict(x=encoder_hidden_states, wt=wv, N=vp.weight.shape[0], b=vp.bias),
-                        dict(x=hidden_states, wt=wt, N=w_cat.shape[0], b=b_cat, pos=lazy_pos)])
-                    value = value.view(batch_size, sequence_length, -1)
+                        dict(x=query, wt=wt, N=w_cat.shape[0], b=b_cat, pos=lazy_pos)])
+                    value = value.view(batch_size, encoder_hidden_states.shape[1], -1)
                     both = both.view(batch_size, num_queries, -1)
                 else:
-                    both = ops.linear_split_bf16(hidden_states, wt, b_cat, w_cat.shape[0])
+                    both = ops.linear_split_bf16(query, wt, b_cat, w_cat.shape[0])
             else:
-                both = F.linear(hidden_states, w_cat, b_cat)
-            n_off = self.sampling_offsets.weight.shape[0]
-            sampling_offsets, attention_weights = both[..., :n_off], both[..., n_off:]
-        elif (hidden_states.is_cuda and batch_size * num_queries > ops.SKINNY_MAX_ROWS and torch.is_grad_enabled()
-              and hidden_states.dtype == torch.float32 and ops.MSDA_GEOMETRY):
+                both = F.linear(query, w_cat, b_cat)
+            return value, both[..., :n_off], both[..., n_off:], None
+        if (query.is_cuda and batch_size * num_queries > ops.SKINNY_MAX_ROWS and torch.is_grad_enabled()
+                and query.dtype == torch.float32 and ops.MSDA_GEOMETRY):
             # training, token-sized input: both Linears read the same rows -> ONE linear over the concatenated weights
             # (one forward / data-gradient / weight-gradient product instead of two, one gradient accumulation less);
-            # MSDAGeometryFunction below reads the two column blocks in place and writes their gradient as one buffer
-            both_train = ops.linear(hidden_states,
-                                    torch.cat([self.sampling_offsets.weight, self.attention_weights.weight], 0),
-                                    torch.cat([self.sampling_offsets.bias, self.attention_weights.bias], 0))
-            n_off = self.sampling_offsets.weight.shape[0]
-            sampling_offsets, attention_weights = both_train[..., :n_off], both_train[..., n_off:]
-        else:
-            sampling_offsets = ops.module_linear(self.sampling_offsets, hidden_states)
-            attention_weights = ops.module_linear(self.attention_weights, hidden_states)
-        offsets_flat, logits_flat = sampling_offsets, attention_weights   # [B, Lq, M*L*P*2], [B, Lq, M*L*P]
-        sampling_offsets = sampling_offsets.reshape(batch_size, num_queries, self.n_heads, self.n_levels, self.n_points, 2)
-        attention_weights = attention_weights.reshape(batch_size, num_queries, self.n_heads,
-                                                      self.n_levels * self.n_points)
+            # MSDAGeometryFunction in stage 3 reads the two column blocks in place and writes their gradient as one buffer
+            both = ops.linear(query, torch.cat([self.sampling_offsets.weight, self.attention_weights.weight], 0),
+                              torch.cat([self.sampling_offsets.bias, self.attention_weights.bias], 0))
+            return value, both[..., :n_off], both[..., n_off:], both
+        return (value, ops.module_linear(self.sampling_offsets, query), ops.module_linear(self.attention_weights, query),
+                None)
+
+    def _sample(self, value, value_bias, value_is_masked, sequence_length, offsets_flat, logits_flat, joint,
+                reference_points, spatial_shapes, level_start_index, attention_mask, mask_bits, output_attentions):
+        """Stage 3, softmax, sampling locations and the weighted sum of the sampled values (dd:1055-1101): (output [B, Lq, d],
+        attention weights).  ``value`` still lacks ``value_bias`` (if not None) and, unless ``value_is_masked``, the zeroing of
+        its padded rows (dd:1052); ``joint``: see stage 2."""
+        batch_size, num_queries = offsets_flat.shape[:2]
+        sampling_offsets = offsets_flat.reshape(batch_size, num_queries, self.n_heads, self.n_levels, self.n_points, 2)
+        attention_weights = logits_flat.reshape(batch_size, num_queries, self.n_heads, self.n_levels * self.n_points)
         if reference_points.shape[-1] not in (2, 4):
             raise ValueError(f"Last dim of reference_points must be 2 or 4, but got {reference_points.shape[-1]}")
         if value_bias is not None and value.dtype != torch.float32:
@@ -478,55 +518,38 @@ class DeformableDetrMultiscaleDeformableAttention(nn.Module):
             # inference: softmax + sampling locations (dd:1055-1073) are formed inside the HIP kernel, which also
             # skips padded tokens (== the zeroed value rows of dd:1052) when the values were not masked above
             value = value.view(batch_size, sequence_length, self.n_heads, self.d_model // self.n_heads)
-            output, attention_weights = ops.msda_forward_fused(
+            return ops.msda_forward_fused(
                 value.contiguous(), spatial_shapes, level_start_index, sampling_offsets, attention_weights,
                 reference_points.contiguous(), want_weights=output_attentions,
                 keep_mask=None if value_is_masked else attention_mask,
                 value_bias=value_bias if value.dtype == torch.float32 else None,
                 keep_bits=None if value_is_masked else mask_bits)
+        if value_bias is not None:
+            value = value + value_bias
+        if not value_is_masked:
+            # dd:1052 `value.masked_fill(~mask[..., None], 0)` as one select (no mask inversion, no clone)
+            value = torch.where(attention_mask[..., None], value, _zero_scalar(value))
+        value = value.view(batch_size, sequence_length, self.n_heads, self.d_model // self.n_heads)
+        if ops.msda_geometry_supported(offsets_flat, logits_flat, reference_points, self.n_heads, self.n_levels,
+                                       self.n_points):
+            # softmax + sampling locations (dd:1055-1073) and their backward as one HIP pass per direction
+            sampling_locations, attention_weights = ops.MSDAGeometryFunction.apply(
+                joint if joint is not None else offsets_flat, None if joint is not None else logits_flat,
+                reference_points, spatial_shapes, self.n_heads, self.n_levels, self.n_points)
         else:
-            if value_bias is not None:
-                value = value + value_bias
-            if not value_is_masked:
-                # dd:1052 `value.masked_fill(~mask[..., None], 0)` as one select (no mask inversion, no clone)
-                value = torch.where(attention_mask[..., None], value, _zero_scalar(value))
-            value = value.view(batch_size, sequence_length, self.n_heads, self.d_model // self.n_heads)
-            if ops.msda_geometry_supported(offsets_flat, logits_flat, reference_points, self.n_heads, self.n_levels,
-                                           self.n_points):
-                # softmax + sampling locations (dd:1055-1073) and their backward as one HIP pass per direction
-                sampling_locations, attention_weights = ops.MSDAGeometryFunction.apply(
-                    both_train if both_train is not None else offsets_flat,
-                    None if both_train is not None else logits_flat, reference_points, spatial_shapes, self.n_heads,
-                    self.n_levels, self.n_points)
+            attention_weights = F.softmax(attention_weights, -1).view(
+                batch_size, num_queries, self.n_heads, self.n_levels, self.n_points)
+            if reference_points.shape[-1] == 2:
+                offset_normalizer = torch.stack([spatial_shapes[..., 1], spatial_shapes[..., 0]], -1)  # (W, H)
+                sampling_locations = (reference_points[:, :, None, :, None, :]
+                                      + sampling_offsets / offset_normalizer[None, None, None, :, None, :])
             else:
-                attention_weights = F.softmax(attention_weights, -1).view(
-                    batch_size, num_queries, self.n_heads, self.n_levels, self.n_points)
-                if reference_points.shape[-1] == 2:
-                    offset_normalizer = torch.stack([spatial_shapes[..., 1], spatial_shapes[..., 0]], -1)  # (W, H)
-                    sampling_locations = (reference_points[:, :, None, :, None, :]
-                                          + sampling_offsets / offset_normalizer[None, None, None, :, None, :])
-                else:
-                    sampling_locations = (reference_points[:, :, None, :, None, :2]
-                                          + sampling_offsets / self.n_points * reference_points[:, :, None, :, None, 2:] * 0.5)
-            # HIP kernel; NO try/except fallback (the reference swallows every exception here, dd:1096-1101)
-            output = MultiScaleDeformableAttentionFunction.apply(
-                value.contiguous(), spatial_shapes, level_start_index, sampling_locations.contiguous(),
-                attention_weights.contiguous(), self.im2col_step)
-        if residual_ln is not None:
-            # inference plumbing: (residual, LayerNorm) of the enclosing layer -- the output projection, the residual add
-            # and the LayerNorm (dd:1102, 1326-1330) as ONE launch where it applies; the third result says whether it did
-            residual, ln = residual_ln[:2]
-            tail = residual_ln[2] if len(residual_ln) > 2 else None
-            if tail is not None and ops.encoder_tail_fused_supported(output, self.output_proj, ln, tail["fc1"], tail["fc2"],
-                                                                     tail["ln"]):
-                # the enclosing encoder layer's WHOLE tail -- this projection, its LayerNorm, the FFN block and the closing
-                # LayerNorm (dd:1102, 1326-1345) -- as one launch; the third result says so
-                return (ops.encoder_tail_fused(output, residual, self.output_proj, ln, tail["fc1"], tail["fc2"], tail["ln"],
-                                               tail["pos"]), attention_weights, "tail")
-            if ops.proj_ln_fused_supported(output, self.output_proj, ln):
-                return ops.proj_ln_fused(output, self.output_proj, residual, ln), attention_weights, True
-            return ops.module_linear(self.output_proj, output), attention_weights, False
-        output = ops.module_linear(self.output_proj, output)
+                sampling_locations = (reference_points[:, :, None, :, None, :2]
+                                      + sampling_offsets / self.n_points * reference_points[:, :, None, :, None, 2:] * 0.5)
+        # HIP kernel; NO try/except fallback (the reference swallows every exception here, dd:1096-1101)
+        output = MultiScaleDeformableAttentionFunction.apply(
+            value.contiguous(), spatial_shapes, level_start_index, sampling_locations.contiguous(),
+            attention_weights.contiguous(), self.im2col_step)
         return output, attention_weights
 
 
@@ -563,7 +586,6 @@ class DeformableDetrMultiheadAttention(nn.Module):
                 position_embeddings: Optional[torch.Tensor] = None, output_attentions: bool = False,
                 output_attention_states: bool = False, hidden_with_pos=None):
         need_map = attention_mask is not None or output_attentions or (self.dropout != 0.0 and self.training)
-        hidden_states_original = hidden_states
         if isinstance(hidden_states, ops.DeferredLayerNorm):
             # the previous layer's closing LayerNorm (+ pos for q / k) runs as the prologue of the three projections
             dpos = _pos_rows(position_embeddings) if position_embeddings is not None else None
@@ -571,21 +593,18 @@ class DeformableDetrMultiheadAttention(nn.Module):
                 dict(x=hidden_states, pos=dpos, w=self.q_proj.weight, b=self.q_proj.bias, alpha=self.scaling),
                 dict(x=hidden_states, pos=dpos, w=self.k_proj.weight, b=self.k_proj.bias),
                 dict(x=hidden_states, w=self.v_proj.weight, b=self.v_proj.bias)])
-        elif hidden_with_pos is not None:
-            hidden_states = hidden_with_pos
-        elif position_embeddings is not None:
-            hidden_states = self.with_pos_embed(hidden_states, position_embeddings)
-        if isinstance(hidden_states_original, ops.DeferredLayerNorm):
-            pass
-        elif ops.inference_fast_path(hidden_states):  # q / k / v projections in one launch
-            query_states, key_states, value_states = ops.linear_grouped([
-                dict(x=hidden_states, w=self.q_proj.weight, b=self.q_proj.bias, alpha=self.scaling),
-                dict(x=hidden_states, w=self.k_proj.weight, b=self.k_proj.bias),
-                dict(x=hidden_states_original, w=self.v_proj.weight, b=self.v_proj.bias)])
         else:
-            query_states = ops.module_linear(self.q_proj, hidden_states, alpha=self.scaling)  # dd:1166, scale fused
-            key_states = ops.module_linear(self.k_proj, hidden_states)
-            value_states = ops.module_linear(self.v_proj, hidden_states_original)
+            with_pos = (hidden_with_pos if hidden_with_pos is not None
+                        else self.with_pos_embed(hidden_states, position_embeddings))
+            if ops.inference_fast_path(with_pos):  # q / k / v projections in one launch
+                query_states, key_states, value_states = ops.linear_grouped([
+                    dict(x=with_pos, w=self.q_proj.weight, b=self.q_proj.bias, alpha=self.scaling),
+                    dict(x=with_pos, w=self.k_proj.weight, b=self.k_proj.bias),
+                    dict(x=hidden_states, w=self.v_proj.weight, b=self.v_proj.bias)])
+            else:
+                query_states = ops.module_linear(self.q_proj, with_pos, alpha=self.scaling)  # dd:1166, scale fused
+                key_states = ops.module_linear(self.k_proj, with_pos)
+                value_states = ops.module_linear(self.v_proj, hidden_states)
         attn_weights = None
         if need_map:
             attn_output, attn_weights = self._attention_with_map(query_states, key_states, value_states,
@@ -595,12 +614,7 @@ class DeformableDetrMultiheadAttention(nn.Module):
                                                            want_maps=False)
         q_maps = k_maps = None
         if output_attention_states:
-            # the retained maps [B, M, N, D] (dd:1179-1185) are pure re-layouts of the projections: hand them out
-            # as transposed VIEWS -- same shape and values as the reference's tensors, no copy, and gradients flow
-            # back through ordinary autograd (the relation head reshapes them straight back to [B, N, M*D])
-            b_, n_, _ = query_states.shape
-            q_maps = query_states.view(b_, n_, self.num_heads, self.head_dim).transpose(1, 2)
-            k_maps = key_states.view(b_, n_, self.num_heads, self.head_dim).transpose(1, 2)
+            q_maps, k_maps = _head_maps(query_states, self.num_heads), _head_maps(key_states, self.num_heads)
         attn_output = ops.module_linear(self.out_proj, attn_output)
         return attn_output, attn_weights, q_maps, k_maps
 
@@ -656,61 +670,54 @@ class DeformableDetrEncoderLayer(nn.Module):
             out = ops.encoder_layer_train(self, hidden_states, attention_mask, position_embeddings, reference_points,
                                           spatial_shapes, level_start_index)
             return (out, None) if return_with_pos else (out,)
-        residual = hidden_states
         fuse = not self.training and ops.inference_fast_path(hidden_states)
-        tail = None
-        if fuse and self.activation_fn is F.relu and not output_attentions:
-            tail = dict(fc1=self.fc1, fc2=self.fc2, ln=self.final_layer_norm,
-                        pos=_pos_rows(position_embeddings) if return_with_pos and position_embeddings is not None else None)
-        res = self.self_attn(
-            hidden_states=hidden_states, attention_mask=attention_mask, encoder_hidden_states=hidden_states,
-            encoder_attention_mask=attention_mask, position_embeddings=position_embeddings,
-            reference_points=reference_points, spatial_shapes=spatial_shapes, level_start_index=level_start_index,
-            output_attentions=output_attentions, spatial_shapes_list=spatial_shapes_list,
-            hidden_with_pos=hidden_with_pos, mask_bits=mask_bits,
-            residual_ln=(residual, self.self_attn_layer_norm, tail) if fuse else None)
-        if fuse and res[2] == "tail":      # the attention module ran the layer's whole tail (one launch)
-            out = res[0]
-            outputs = (out[0] if isinstance(out, tuple) else out,)
-            if return_with_pos:
-                outputs += (out[1] if isinstance(out, tuple) else None,)
-            return outputs
-        hidden_states, attn_weights = res[0], res[1]
-        if not (fuse and res[2]):
+        whole_tail = fuse and self.activation_fn is F.relu and not output_attentions
+        want_pos = return_with_pos and position_embeddings is not None
+        tail_pos = _pos_rows(position_embeddings) if whole_tail and want_pos else None   # for the one-launch tail
+        sampled, attn_weights = self.self_attn.sample(
+            hidden_states, attention_mask, hidden_states, position_embeddings, reference_points, spatial_shapes,
+            level_start_index, output_attentions, spatial_shapes_list, hidden_with_pos, mask_bits=mask_bits)
+        hidden_states, next_with_pos = self._tail(sampled, hidden_states, position_embeddings if want_pos else None, fuse,
+                                                  whole_tail, tail_pos)
+        outputs = (hidden_states,)
+        if output_attentions:
+            outputs += (attn_weights,)
+        if return_with_pos:
+            outputs += (next_with_pos,)
+        return outputs
+
+    def _tail(self, sampled, residual, position_embeddings, fuse, whole_tail, tail_pos):
+        """The layer after the attention's sampling -- output projection, residual, LayerNorm, FFN block, closing LayerNorm
+        (dd:1102, 1326-1351) -- by the widest fused route that applies: (states, states + position_embeddings for the next
+        layer where the closing kernel can write them too -- else None).  ``fuse``: inference fast path; ``whole_tail`` /
+        ``tail_pos``: the one-launch route may be tried, and the position rows for it."""
+        out_proj, ln = self.self_attn.output_proj, self.self_attn_layer_norm
+        if whole_tail and ops.encoder_tail_fused_supported(sampled, out_proj, ln, self.fc1, self.fc2, self.final_layer_norm):
+            # the WHOLE tail -- this projection, its LayerNorm, the FFN block and the closing LayerNorm (dd:1102, 1326-1345)
+            # -- as one launch
+            return _pair(ops.encoder_tail_fused(sampled, residual, out_proj, ln, self.fc1, self.fc2, self.final_layer_norm,
+                                                tail_pos))
+        if fuse and ops.proj_ln_fused_supported(sampled, out_proj, ln):
+            # the output projection, the residual add and the LayerNorm (dd:1102, 1326-1330) as ONE launch
+            hidden_states = ops.proj_ln_fused(sampled, out_proj, residual, ln)
+        else:
+            hidden_states = ops.module_linear(out_proj, sampled)
             hidden_states = F.dropout(hidden_states, p=self.dropout, training=self.training)
-            hidden_states = ops.add_layer_norm(hidden_states, residual, self.self_attn_layer_norm)
+            hidden_states = ops.add_layer_norm(hidden_states, residual, ln)
         residual = hidden_states
         if (self.activation_fn is F.relu and not self.training
                 and ops.ffn_fused_supported(hidden_states, self.fc1, self.fc2, self.final_layer_norm)):
             # inference: fc1 + ReLU + fc2 + residual + LayerNorm (+ the position embeddings for the next layer) in ONE
             # launch; the [S, 1024] hidden activation (51 MB at 600x1000) never leaves the compute units
-            next_with_pos = None
-            if return_with_pos and position_embeddings is not None:
-                hidden_states, next_with_pos = ops.ffn_fused(hidden_states, self.fc1, self.fc2, self.final_layer_norm,
-                                                             _pos_rows(position_embeddings))
-            else:
-                hidden_states = ops.ffn_fused(hidden_states, self.fc1, self.fc2, self.final_layer_norm)
-            outputs = (hidden_states,)
-            if output_attentions:
-                outputs += (attn_weights,)
-            if return_with_pos:
-                outputs += (next_with_pos,)
-            return outputs
+            pos = _pos_rows(position_embeddings) if position_embeddings is not None else None
+            return _pair(ops.ffn_fused(hidden_states, self.fc1, self.fc2, self.final_layer_norm, pos))
         if (self.activation_fn is F.relu and not self.training
                 and ops.ffn_bf16_supported(hidden_states, self.fc1, self.fc2, self.final_layer_norm)):
             # bf16 model at inference: the same block on the bf16 matrix cores, one launch (csrc/ffn_bf16.hip)
-            next_with_pos = None
-            if (return_with_pos and position_embeddings is not None and position_embeddings.dtype == torch.bfloat16):
-                hidden_states, next_with_pos = ops.ffn_layernorm_bf16(hidden_states, self.fc1, self.fc2, self.final_layer_norm,
-                                                                      _pos_rows(position_embeddings))
-            else:
-                hidden_states = ops.ffn_layernorm_bf16(hidden_states, self.fc1, self.fc2, self.final_layer_norm)
-            outputs = (hidden_states,)
-            if output_attentions:
-                outputs += (attn_weights,)
-            if return_with_pos:
-                outputs += (next_with_pos,)
-            return outputs
+            pos = None
+            if position_embeddings is not None and position_embeddings.dtype == torch.bfloat16:
+                pos = _pos_rows(position_embeddings)
+            return _pair(ops.ffn_layernorm_bf16(hidden_states, self.fc1, self.fc2, self.final_layer_norm, pos))
         if self.activation_fn is F.relu:
             hidden_states = ops.module_linear(self.fc1, hidden_states, relu=True)
         else:
@@ -719,7 +726,7 @@ class DeformableDetrEncoderLayer(nn.Module):
         hidden_states = ops.module_linear(self.fc2, hidden_states)
         hidden_states = F.dropout(hidden_states, p=self.dropout, training=self.training)
         next_with_pos = None
-        if return_with_pos and position_embeddings is not None and (
+        if position_embeddings is not None and (
                 ops.inference_fast_path(hidden_states)
                 or (hidden_states.is_cuda and hidden_states.dtype == torch.bfloat16 and not torch.is_grad_enabled()
                     and position_embeddings.dtype == torch.bfloat16 and residual.dtype == torch.bfloat16
@@ -736,12 +743,7 @@ class DeformableDetrEncoderLayer(nn.Module):
             # capturable in a HIP graph): the "any non-finite" flag stays on the device; the clamp pass (and the gradient
             # mask of the backward) return at once while it is clear (ops.clamp_nonfinite_).
             hidden_states = ops.clamp_nonfinite_(hidden_states)
-        outputs = (hidden_states,)
-        if output_attentions:
-            outputs += (attn_weights,)
-        if return_with_pos:
-            outputs += (next_with_pos,)
-        return outputs
+        return hidden_states, next_with_pos
 
 
 class DeformableDetrDecoderLayer(nn.Module):
@@ -791,11 +793,8 @@ class DeformableDetrDecoderLayer(nn.Module):
             y3, qs, ks = ops.decoder_layer_train(self, hidden_states, position_embeddings, reference_points,
                                                  precomputed_value, spatial_shapes, level_start_index, masks=dropout_masks)
             outputs = (y3,)
-            if output_attention_states:   # the retained maps [B, M, N, D] (dd:1179-1185) as transposed views
-                b_, n_, _ = qs.shape
-                sa_ = self.self_attn
-                outputs += (qs.view(b_, n_, sa_.num_heads, sa_.head_dim).transpose(1, 2),
-                            ks.view(b_, n_, sa_.num_heads, sa_.head_dim).transpose(1, 2))
+            if output_attention_states:
+                outputs += (_head_maps(qs, self.self_attn.num_heads), _head_maps(ks, self.self_attn.num_heads))
             if return_with_pos:
                 outputs += (None,)
             return outputs
@@ -1008,77 +1007,29 @@ class DeformableDetrDecoder(DeformableDetrPreTrainedModel):
         all_attention_queries = () if output_attention_states else None
         all_attention_keys = () if output_attention_states else None
         fast = ops.inference_fast_path(hidden_states) and encoder_hidden_states is not None
-        values = None
-        if fast:
-            # the value projections of ALL layers' cross-attention depend only on the encoder output: one batched
-            # GEMM + one bias / padding-mask pass instead of (GEMM + fill + select) per layer
-            nl = len(self.layers)
-            w_t, b_all = ops.cached_weights(
-                self, "decoder_value_proj",
-                [l.encoder_attn.value_proj.weight for l in self.layers] + [l.encoder_attn.value_proj.bias for l in self.layers],
-                lambda: (torch.stack([l.encoder_attn.value_proj.weight.t() for l in self.layers]).contiguous(),
-                         torch.stack([l.encoder_attn.value_proj.bias for l in self.layers]).contiguous()))
-            bsz_, seq_, dm_ = encoder_hidden_states.shape
-            if ops.proj_multi_fused_supported(encoder_hidden_states):
-                # one launch: a workgroup splits its 64 encoder rows once and multiplies them by all nl weights
-                w_xs = ops.cached_weights(
-                    self, "decoder_value_proj_xs", [l.encoder_attn.value_proj.weight for l in self.layers],
-                    lambda: ops.xs_split(torch.cat([l.encoder_attn.value_proj.weight for l in self.layers], 0),
-                                         weights=True))
-                values = ops.proj_multi_fused(encoder_hidden_states, w_xs, nl).view(nl, bsz_, seq_, dm_)
-            elif ops.gemm_split_supported(encoder_hidden_states, dm_, dm_):
-                values = torch.empty(nl, bsz_ * seq_, dm_, dtype=encoder_hidden_states.dtype,
-                                     device=encoder_hidden_states.device)
-                items = []
-                for i, l in enumerate(self.layers):
-                    vp = l.encoder_attn.value_proj
-                    wt = ops.cached_weights(vp, "gemm_split_bf16", [vp.weight],
-                                            lambda vp=vp: ops.gemm_split_weights(vp.weight))
-                    items.append(dict(x=encoder_hidden_states, wt=wt, N=dm_, out=values[i]))
-                for i0 in range(0, nl, 8):   # all layers' projections share one grid
-                    ops.linear_split_bf16_grouped(items[i0:i0 + 8])
-                values = values.view(nl, bsz_, seq_, dm_)
-            else:
-                x2 = encoder_hidden_states.reshape(1, bsz_ * seq_, dm_).expand(nl, -1, -1)
-                values = torch.bmm(x2, w_t).view(nl, bsz_, seq_, dm_)
-            lay0 = self.layers[0].encoder_attn
-            if (not output_attentions and (reference_points.shape[-1] == 2 or values.dtype == torch.float32)
-                    and ops.msda_fused_supported(lay0.n_heads, lay0.d_model // lay0.n_heads, lay0.n_levels,
-                                                 lay0.n_points)):
-                # the fused MSDA kernel applies the bias (times the sum of the valid corner weights) and skips padded
-                # tokens itself: no pass over the [Ld, S, 256] values at all
-                values_all = values
-                values = [(values[i], b_all[i]) for i in range(nl)]
-            else:
-                values = ops.bias_mask_rows_(values.view(nl, bsz_ * seq_, dm_), b_all,
-                                             encoder_attention_mask).view(nl, bsz_, seq_, dm_)
-        elif (encoder_hidden_states is not None and self.training
-              and ops.decoder_values_train_supported(encoder_hidden_states, encoder_attention_mask, self.layers)):
-            # training: the value projections of all layers' cross-attention as ONE autograd node (one grouped forward launch,
-            # one accumulating chain of data-gradient products; padded rows zeroed in the epilogues)
-            values = ops.decoder_values_train(encoder_hidden_states, encoder_attention_mask, self.layers)
-        hoisted_reference = None
-        use_cluster = (fast and isinstance(values, list) and self.bbox_embed is None and reference_points.shape[-1] == 2
+        values, raw_values = self._cross_attention_values(fast, encoder_hidden_states, encoder_attention_mask,
+                                                          reference_points, output_attentions)
+        use_cluster = (raw_values is not None and self.bbox_embed is None and reference_points.shape[-1] == 2
                        and decoder_fused.supported(self, hidden_states, position_embeddings, reference_points,
                                                    encoder_hidden_states, output_attentions))
-        if self.bbox_embed is None and reference_points.shape[-1] == 2 and not use_cluster:
-            # no refinement: same input for every layer (the cluster kernel multiplies by the valid ratios itself)
-            hoisted_reference = reference_points[:, :, None] * valid_ratios[:, None]
         if use_cluster:
             # ONE launch per layer (csrc/dec_layer.hip) instead of eight; a device whose dispatch does not keep a cluster's
             # workgroups on one XCD refuses (checked on the first run) and the per-operation loop below runs
             try:
                 states, q_all, k_all = decoder_fused.run(
-                    self, hidden_states, position_embeddings, reference_points, values_all, b_all,
+                    self, hidden_states, position_embeddings, reference_points, *raw_values,
                     encoder_attention_mask, spatial_shapes, level_start_index, first_with_pos=first_with_pos,
                     valid_ratios=valid_ratios, keep_bits=mask_bits)
             except decoder_fused.DecoderClusterError as exc:
                 ops.note_fallback("decoder_cluster", str(exc))
                 decoder_fused.ENABLED = False
-                hoisted_reference = reference_points[:, :, None] * valid_ratios[:, None]
             else:
                 return self._fused_outputs(states, q_all, k_all, hidden_states, reference_points, output_hidden_states,
                                            output_attention_states, return_dict)
+        hoisted_reference = None
+        if self.bbox_embed is None and reference_points.shape[-1] == 2:
+            # no refinement: same input for every layer (the cluster kernel multiplies by the valid ratios itself)
+            hoisted_reference = self._reference_input(reference_points, valid_ratios)
         with_pos = first_with_pos if fast else None
         # inference: every layer's final LayerNorm writes its states straight into the stacked [Ld, B, N, d] buffer the
         # heads read (viewed [B, Ld, N, d]) -- no torch.stack copy at the end
@@ -1096,15 +1047,8 @@ class DeformableDetrDecoder(DeformableDetrPreTrainedModel):
             layer_masks = torch.empty(len(self.layers), 3, rows, 256, dtype=torch.uint8,
                                       device=hidden_states.device).bernoulli_(1.0 - self.dropout)
         for idx, decoder_layer in enumerate(self.layers):
-            if hoisted_reference is not None:
-                reference_points_input = hoisted_reference
-            elif reference_points.shape[-1] == 4:
-                reference_points_input = (reference_points[:, :, None]
-                                          * torch.cat([valid_ratios, valid_ratios], -1)[:, None])
-            else:
-                if reference_points.shape[-1] != 2:
-                    raise ValueError("Reference points' last dimension must be of size 2")
-                reference_points_input = reference_points[:, :, None] * valid_ratios[:, None]
+            reference_points_input = (hoisted_reference if hoisted_reference is not None
+                                      else self._reference_input(reference_points, valid_ratios))
             if output_hidden_states:   # a pending LayerNorm's buffer: filled by the launch that consumes it
                 all_hidden_states += (hidden_states.out if isinstance(hidden_states, ops.DeferredLayerNorm)
                                       else hidden_states,)
@@ -1168,6 +1112,64 @@ class DeformableDetrDecoder(DeformableDetrPreTrainedModel):
             attention_queries=all_attention_queries, attention_keys=all_attention_keys)
 
 
+    @staticmethod
+    def _reference_input(reference_points, valid_ratios):
+        """A layer's reference points (boxes) in units of each level's valid area [B, N, L, 2 or 4] (dd:1854-1868)."""
+        if reference_points.shape[-1] == 4:
+            return reference_points[:, :, None] * torch.cat([valid_ratios, valid_ratios], -1)[:, None]
+        if reference_points.shape[-1] != 2:
+            raise ValueError("Reference points' last dimension must be of size 2")
+        return reference_points[:, :, None] * valid_ratios[:, None]
+
+    def _cross_attention_values(self, fast, encoder_hidden_states, encoder_attention_mask, reference_points,
+                                output_attentions):
+        """The value projections of ALL layers' cross-attention, which depend only on the encoder output: (each layer's
+        ``precomputed_value`` -- or None: every layer projects its own --, the stacked (W x [Ld, B, S, d], b [Ld, d]) where
+        the fused kernels add the bias and skip padded tokens themselves -- else None)."""
+        if not fast:
+            if (encoder_hidden_states is not None and self.training
+                    and ops.decoder_values_train_supported(encoder_hidden_states, encoder_attention_mask, self.layers)):
+                # training: the value projections of all layers' cross-attention as ONE autograd node (one grouped forward
+                # launch, one accumulating chain of data-gradient products; padded rows zeroed in the epilogues)
+                return ops.decoder_values_train(encoder_hidden_states, encoder_attention_mask, self.layers), None
+            return None, None
+        # inference: one batched GEMM + one bias / padding-mask pass instead of (GEMM + fill + select) per layer
+        nl = len(self.layers)
+        w_t, b_all = ops.cached_weights(
+            self, "decoder_value_proj",
+            [l.encoder_attn.value_proj.weight for l in self.layers] + [l.encoder_attn.value_proj.bias for l in self.layers],
+            lambda: (torch.stack([l.encoder_attn.value_proj.weight.t() for l in self.layers]).contiguous(),
+                     torch.stack([l.encoder_attn.value_proj.bias for l in self.layers]).contiguous()))
+        bsz_, seq_, dm_ = encoder_hidden_states.shape
+        if ops.proj_multi_fused_supported(encoder_hidden_states):
+            # one launch: a workgroup splits its 64 encoder rows once and multiplies them by all nl weights
+            w_xs = ops.cached_weights(
+                self, "decoder_value_proj_xs", [l.encoder_attn.value_proj.weight for l in self.layers],
+                lambda: ops.xs_split(torch.cat([l.encoder_attn.value_proj.weight for l in self.layers], 0), weights=True))
+            values = ops.proj_multi_fused(encoder_hidden_states, w_xs, nl).view(nl, bsz_, seq_, dm_)
+        elif ops.gemm_split_supported(encoder_hidden_states, dm_, dm_):
+            values = torch.empty(nl, bsz_ * seq_, dm_, dtype=encoder_hidden_states.dtype,
+                                 device=encoder_hidden_states.device)
+            items = []
+            for i, l in enumerate(self.layers):
+                vp = l.encoder_attn.value_proj
+                wt = ops.cached_weights(vp, "gemm_split_bf16", [vp.weight], lambda vp=vp: ops.gemm_split_weights(vp.weight))
+                items.append(dict(x=encoder_hidden_states, wt=wt, N=dm_, out=values[i]))
+            for i0 in range(0, nl, 8):   # all layers' projections share one grid
+                ops.linear_split_bf16_grouped(items[i0:i0 + 8])
+            values = values.view(nl, bsz_, seq_, dm_)
+        else:
+            x2 = encoder_hidden_states.reshape(1, bsz_ * seq_, dm_).expand(nl, -1, -1)
+            values = torch.bmm(x2, w_t).view(nl, bsz_, seq_, dm_)
+        lay0 = self.layers[0].encoder_attn
+        if (not output_attentions and (reference_points.shape[-1] == 2 or values.dtype == torch.float32)
+                and ops.msda_fused_supported(lay0.n_heads, lay0.d_model // lay0.n_heads, lay0.n_levels, lay0.n_points)):
+            # the fused MSDA kernel applies the bias (times the sum of the valid corner weights) and skips padded
+            # tokens itself: no pass over the [Ld, S, 256] values at all
+            return [(values[i], b_all[i]) for i in range(nl)], (values, b_all)
+        return ops.bias_mask_rows_(values.view(nl, bsz_ * seq_, dm_), b_all,
+                                   encoder_attention_mask).view(nl, bsz_, seq_, dm_), None
+
     def _fused_outputs(self, states, q_all, k_all, inputs_embeds, reference_points, output_hidden_states,
                        output_attention_states, return_dict):
         """Outputs of dd:1927-1968 from the stacked results of ``decoder_fused.run`` (states [Ld, B, N, d]; per-layer scaled
@@ -1182,10 +1184,8 @@ class DeformableDetrDecoder(DeformableDetrPreTrainedModel):
             all_hidden_states = (inputs_embeds,) + tuple(states[i] for i in range(nl))
         queries = keys = None
         if output_attention_states:
-            queries = tuple(q.view(B, N, M, d // M).transpose(1, 2) if q.is_contiguous()
-                            else q.reshape(B, N, M, d // M).transpose(1, 2) for q in q_all)
-            keys = tuple(k.view(B, N, M, d // M).transpose(1, 2) if k.is_contiguous()
-                         else k.reshape(B, N, M, d // M).transpose(1, 2) for k in k_all)
+            queries = tuple(_head_maps(q, M) for q in q_all)
+            keys = tuple(_head_maps(k, M) for k in k_all)
         if not return_dict:
             return tuple(v for v in [hidden_states, intermediate, intermediate_reference_points, all_hidden_states]
                          if v is not None)
@@ -1295,6 +1295,79 @@ class DeformableDetrModel(DeformableDetrPreTrainedModel):
         object_query = self.enc_output_norm(ops.module_linear(self.enc_output, object_query))
         return object_query, output_proposals
 
+    def _feature_maps(self, pixel_values, pixel_mask):
+        """The backbone's feature maps alone (the level-geometry kernels derive every level's mask from ``pixel_mask``)."""
+        conv_encoder = self.backbone.conv_encoder
+        if isinstance(conv_encoder, DeformableDetrTimmConvEncoder):
+            return conv_encoder.model(pixel_values)
+        # a user-supplied feature extractor: keep its (feature, mask) interface, drop its masks
+        return [fm for fm, _ in conv_encoder(pixel_values, pixel_mask)]
+
+    def _project_inputs(self, feature_maps):
+        """Every level's input projection [B, d, H, W] as the modules compose it."""
+        sources = [self.input_proj[level](fm) for level, fm in enumerate(feature_maps)]
+        for level in range(len(sources), self.config.num_feature_levels):  # dd:2228-2241
+            sources.append(self.input_proj[level](feature_maps[-1] if level == len(feature_maps) else sources[-1]))
+        return sources
+
+    def _project_inputs_inference(self, feature_maps, dtype):
+        """The input projections of all levels at inference, flattened and concatenated: (tokens [B, S, d],
+        [(H, W) of each level]), by the first of four routes that serves the maps' layout and the projection modules."""
+        n_extra = self.config.num_feature_levels - len(feature_maps)
+        channels_last = all(fm.dim() == 4 and fm.dtype == dtype and not fm.is_contiguous()
+                            and fm.is_contiguous(memory_format=torch.channels_last) for fm in feature_maps)
+        if (channels_last and n_extra <= 1 and self.config.d_model == 256
+                and self.input_proj[0][0].weight.dtype == dtype
+                and all(isinstance(p[1], nn.GroupNorm) and p[1].num_groups == 32 and p[0].bias is not None
+                        and p[0].groups == 1 for p in self.input_proj)
+                and all(tuple(self.input_proj[l][0].kernel_size) == (1, 1) and tuple(self.input_proj[l][0].stride) == (1, 1)
+                        and tuple(self.input_proj[l][0].padding) == (0, 0) for l in range(len(feature_maps)))):
+            # channels-last backbone: a feature map IS its [B*H*W, C] token matrix, the 1x1 projection a plain GEMM
+            # whose output is already `flatten(2).transpose(1, 2)`; GroupNorm + concatenation without a transpose
+            if (len(self.input_proj) == len(feature_maps) + n_extra
+                    and ops.input_proj_x6_supported(feature_maps, self.input_proj)):
+                # fp32 inference: every level's projection in ONE grouped K-split launch, the K ranges summed by the GroupNorm
+                # statistics pass (csrc/input_proj_x6.hip); EGTR_GEMM_SPLIT_BF16=0 keeps the vendor products below
+                return ops.input_proj_x6_groupnorm(feature_maps, self.input_proj)
+            toks, spatial_shapes_list = [], []
+            for level, fm in enumerate(feature_maps):
+                c = self.input_proj[level][0]
+                b_, c_, h_, w_ = fm.shape
+                toks.append(torch.mm(fm.permute(0, 2, 3, 1).reshape(-1, c_), c.weight.detach().view(c.weight.shape[0], c_).t())
+                            .view(b_, h_ * w_, -1))
+                spatial_shapes_list.append((h_, w_))
+            if n_extra == 1:  # dd:2228-2241: the extra level is a strided 3x3 convolution of the last feature map
+                c = self.input_proj[len(feature_maps)][0]
+                wcl = ops.cached_weights(c, "weight_channels_last", [c.weight],
+                                         lambda: c.weight.detach().contiguous(memory_format=torch.channels_last))
+                y = F.conv2d(feature_maps[-1], wcl, None, c.stride, c.padding)
+                toks.append(y.permute(0, 2, 3, 1).reshape(y.shape[0], y.shape[2] * y.shape[3], y.shape[1]))
+                spatial_shapes_list.append(tuple(y.shape[-2:]))
+            return ops.input_proj_groupnorm_tokens(toks, self.input_proj), spatial_shapes_list
+        if (n_extra <= 1 and self.config.d_model == 256 and feature_maps[0].dtype == dtype
+                and self.input_proj[0][0].weight.dtype == dtype
+                and all(isinstance(p[1], nn.GroupNorm) and p[0].bias is not None for p in self.input_proj)):
+            # input projections: bias-free convolutions, then conv bias + GroupNorm + flatten + transpose + cat
+            # of all levels in two HIP launches
+            convs = []
+            for level, fm in enumerate(feature_maps):
+                c = self.input_proj[level][0]
+                if (tuple(c.kernel_size) == (1, 1) and tuple(c.stride) == (1, 1) and tuple(c.padding) == (0, 0)
+                        and c.groups == 1):
+                    # a tuned GEMM on the NCHW tensor as it lies.  detach(): torch.matmul(2-D, 3-D) picks its
+                    # "fold" formulation when the 2-D operand requires grad, whose result is a transposed view that
+                    # then has to be copied back to NCHW (3 copies, 27 us per forward)
+                    convs.append(conv1x1_as_gemm(fm, c.weight.detach()))
+                else:
+                    convs.append(F.conv2d(fm, c.weight, None, c.stride, c.padding))
+            if n_extra == 1:  # dd:2228-2241: the extra level is a strided 3x3 convolution of the last feature map
+                c = self.input_proj[len(feature_maps)][0]
+                convs.append(F.conv2d(feature_maps[-1], c.weight, None, c.stride, c.padding))
+            return ops.input_proj_groupnorm_flatten(convs, self.input_proj), [tuple(cv.shape[-2:]) for cv in convs]
+        sources = self._project_inputs(feature_maps)
+        return (torch.cat([src.flatten(2).transpose(1, 2) for src in sources], 1),
+                [tuple(src.shape[-2:]) for src in sources])
+
     def forward(self, pixel_values, pixel_mask=None, decoder_attention_mask=None, encoder_outputs=None,
                 inputs_embeds=None, decoder_inputs_embeds=None, output_attentions=None, output_hidden_states=None,
                 output_attention_states=None, return_dict=None):
@@ -1321,72 +1394,8 @@ class DeformableDetrModel(DeformableDetrPreTrainedModel):
         if fused_geometry:
             # inference: masks, position embeddings (+ level_embed), valid ratios and the encoder reference points of
             # all levels come from ONE HIP kernel instead of ~100 tiny launches (dd:2195-2278, 1616-1648, 850-876)
-            conv_encoder = self.backbone.conv_encoder
-            if isinstance(conv_encoder, DeformableDetrTimmConvEncoder):
-                feature_maps = conv_encoder.model(pixel_values)
-            else:  # a user-supplied feature extractor: keep its (feature, mask) interface, drop its masks
-                feature_maps = [fm for fm, _ in conv_encoder(pixel_values, pixel_mask)]
-            n_extra = self.config.num_feature_levels - len(feature_maps)
-            channels_last = all(fm.dim() == 4 and fm.dtype == pixel_values.dtype and not fm.is_contiguous()
-                                and fm.is_contiguous(memory_format=torch.channels_last) for fm in feature_maps)
-            if (channels_last and n_extra <= 1 and self.config.d_model == 256
-                    and self.input_proj[0][0].weight.dtype == pixel_values.dtype
-                    and all(isinstance(p[1], nn.GroupNorm) and p[1].num_groups == 32 and p[0].bias is not None
-                            and p[0].groups == 1 for p in self.input_proj)
-                    and all(tuple(self.input_proj[l][0].kernel_size) == (1, 1) and tuple(self.input_proj[l][0].stride) == (1, 1)
-                            and tuple(self.input_proj[l][0].padding) == (0, 0) for l in range(len(feature_maps)))):
-                # channels-last backbone: a feature map IS its [B*H*W, C] token matrix, the 1x1 projection a plain GEMM
-                # whose output is already `flatten(2).transpose(1, 2)`; GroupNorm + concatenation without a transpose
-                toks, spatial_shapes_list = [], []
-                # fp32 inference: every level's projection in ONE grouped K-split launch, the K ranges summed by the GroupNorm
-                # statistics pass (csrc/input_proj_x6.hip); EGTR_GEMM_SPLIT_BF16=0 keeps the vendor products below
-                grouped = (len(self.input_proj) == len(feature_maps) + n_extra
-                           and ops.input_proj_x6_supported(feature_maps, self.input_proj))
-                if grouped:
-                    source_flatten, spatial_shapes_list = ops.input_proj_x6_groupnorm(feature_maps, self.input_proj)
-                for level, fm in enumerate(feature_maps if not grouped else ()):
-                    c = self.input_proj[level][0]
-                    b_, c_, h_, w_ = fm.shape
-                    toks.append(torch.mm(fm.permute(0, 2, 3, 1).reshape(-1, c_), c.weight.detach().view(c.weight.shape[0], c_).t())
-                                .view(b_, h_ * w_, -1))
-                    spatial_shapes_list.append((h_, w_))
-                if n_extra == 1 and not grouped:  # dd:2228-2241: the extra level is a strided 3x3 convolution of the last feature map
-                    c = self.input_proj[len(feature_maps)][0]
-                    wcl = ops.cached_weights(c, "weight_channels_last", [c.weight],
-                                             lambda: c.weight.detach().contiguous(memory_format=torch.channels_last))
-                    y = F.conv2d(feature_maps[-1], wcl, None, c.stride, c.padding)
-                    toks.append(y.permute(0, 2, 3, 1).reshape(y.shape[0], y.shape[2] * y.shape[3], y.shape[1]))
-                    spatial_shapes_list.append(tuple(y.shape[-2:]))
-                if not grouped:
-                    source_flatten = ops.input_proj_groupnorm_tokens(toks, self.input_proj)
-            elif (n_extra <= 1 and self.config.d_model == 256 and feature_maps[0].dtype == pixel_values.dtype
-                    and self.input_proj[0][0].weight.dtype == pixel_values.dtype
-                    and all(isinstance(p[1], nn.GroupNorm) and p[0].bias is not None for p in self.input_proj)):
-                # input projections: bias-free convolutions, then conv bias + GroupNorm + flatten + transpose + cat
-                # of all levels in two HIP launches
-                convs = []
-                for level, fm in enumerate(feature_maps):
-                    c = self.input_proj[level][0]
-                    if (tuple(c.kernel_size) == (1, 1) and tuple(c.stride) == (1, 1) and tuple(c.padding) == (0, 0)
-                            and c.groups == 1):
-                        # a tuned GEMM on the NCHW tensor as it lies.  detach(): torch.matmul(2-D, 3-D) picks its
-                        # "fold" formulation when the 2-D operand requires grad, whose result is a transposed view that
-                        # then has to be copied back to NCHW (3 copies, 27 us per forward)
-                        convs.append(conv1x1_as_gemm(fm, c.weight.detach()))
-                    else:
-                        convs.append(F.conv2d(fm, c.weight, None, c.stride, c.padding))
-                if n_extra == 1:  # dd:2228-2241: the extra level is a strided 3x3 convolution of the last feature map
-                    c = self.input_proj[len(feature_maps)][0]
-                    convs.append(F.conv2d(feature_maps[-1], c.weight, None, c.stride, c.padding))
-                spatial_shapes_list = [tuple(cv.shape[-2:]) for cv in convs]
-                source_flatten = ops.input_proj_groupnorm_flatten(convs, self.input_proj)
-            else:
-                sources = [self.input_proj[level](fm) for level, fm in enumerate(feature_maps)]
-                for level in range(len(sources), self.config.num_feature_levels):  # dd:2228-2241
-                    sources.append(self.input_proj[level](feature_maps[-1] if level == len(feature_maps)
-                                                          else sources[-1]))
-                spatial_shapes_list = [tuple(src.shape[-2:]) for src in sources]
-                source_flatten = torch.cat([src.flatten(2).transpose(1, 2) for src in sources], 1)
+            source_flatten, spatial_shapes_list = self._project_inputs_inference(
+                self._feature_maps(pixel_values, pixel_mask), pixel_values.dtype)
             mask_flatten, lvl_pos_embed_flatten, valid_ratios, encoder_reference_points, mask_bits = ops.level_geometry(
                 pixel_mask, spatial_shapes_list, self.level_embed, pos_mod.embedding_dim, pos_mod.temperature,
                 pos_mod.scale)
@@ -1397,40 +1406,24 @@ class DeformableDetrModel(DeformableDetrPreTrainedModel):
             # masks, sine position embeddings + level_embed, valid ratios, encoder reference points) comes from the two HIP
             # launches of the inference path, with the gradient of level_embed as four mask-weighted column sums
             # (ops.LevelGeometryTrainFunction) instead of ~80 tiny launches and four generic reductions per step
-            conv_encoder = self.backbone.conv_encoder
-            if isinstance(conv_encoder, DeformableDetrTimmConvEncoder):
-                feature_maps = conv_encoder.model(pixel_values)
-            else:  # a user-supplied feature extractor: keep its (feature, mask) interface, drop its masks
-                feature_maps = [fm for fm, _ in conv_encoder(pixel_values, pixel_mask)]
-            sources = [self.input_proj[level](fm) for level, fm in enumerate(feature_maps)]
-            for level in range(len(sources), self.config.num_feature_levels):  # dd:2228-2241
-                sources.append(self.input_proj[level](feature_maps[-1] if level == len(feature_maps) else sources[-1]))
+            sources = self._project_inputs(self._feature_maps(pixel_values, pixel_mask))
             spatial_shapes_list = [tuple(src.shape[-2:]) for src in sources]
             source_flatten = torch.cat([src.flatten(2).transpose(1, 2) for src in sources], 1)
             mask_flatten, lvl_pos_embed_flatten, valid_ratios, encoder_reference_points = ops.level_geometry_train(
                 pixel_mask, spatial_shapes_list, self.level_embed, pos_mod.embedding_dim, pos_mod.temperature, pos_mod.scale)
         else:
             features, position_embeddings_list = self.backbone(pixel_values, pixel_mask)
-            sources, masks = [], []
-            for level, (source, mask) in enumerate(features):
-                sources.append(self.input_proj[level](source))
+            masks = [mask for _, mask in features]
+            if any(mask is None for mask in masks):
+                raise ValueError("No attention mask was provided")
+            sources = self._project_inputs([source for source, _ in features])
+            for source in sources[len(features):]:  # dd:2228-2241: the extra levels' masks and position embeddings
+                mask = F.interpolate(pixel_mask[None].float(), size=source.shape[-2:]).to(torch.bool)[0]
                 masks.append(mask)
-                if mask is None:
-                    raise ValueError("No attention mask was provided")
-            if self.config.num_feature_levels > len(sources):  # dd:2228-2241
-                _len_sources = len(sources)
-                for level in range(_len_sources, self.config.num_feature_levels):
-                    source = self.input_proj[level](features[-1][0] if level == _len_sources else sources[-1])
-                    mask = F.interpolate(pixel_mask[None].float(), size=source.shape[-2:]).to(torch.bool)[0]
-                    pos_l = self.backbone.position_embedding(source, mask).to(source.dtype)
-                    sources.append(source)
-                    masks.append(mask)
-                    position_embeddings_list.append(pos_l)
-
+                position_embeddings_list.append(self.backbone.position_embedding(source, mask).to(source.dtype))
             source_flatten, mask_flatten, lvl_pos_embed_flatten, spatial_shapes_list = [], [], [], []
             for level, (source, mask, pos_embed) in enumerate(zip(sources, masks, position_embeddings_list)):
-                batch_size, num_channels, height, width = source.shape
-                spatial_shapes_list.append((height, width))
+                spatial_shapes_list.append(tuple(source.shape[-2:]))
                 source_flatten.append(source.flatten(2).transpose(1, 2))
                 mask_flatten.append(mask.flatten(1))
                 lvl_pos_embed_flatten.append(pos_embed.flatten(2).transpose(1, 2)

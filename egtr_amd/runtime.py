@@ -7,10 +7,27 @@ is absent on the GPU box; these helpers reproduce exactly the pieces that touch 
 """
 import collections
 import contextlib
+import gc
 import os
 
 import torch
 import torch.distributed as dist
+
+
+@contextlib.contextmanager
+def _collector_off():
+    """Around a stream capture: Python's cycle collector must not run while the stream captures.  A dead cycle that holds GPU
+    objects -- a dropped GraphedForward is one (model -> load_state_dict hook -> self -> its graphs and their pools) -- would be
+    torn down in the middle of the capture, where that is an illegal call and aborts the process.  torch.cuda.graph() collected
+    before every capture up to torch 2.9 and no longer does: collect first, then keep the collector off until the end."""
+    gc.collect()
+    was_enabled = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was_enabled:
+            gc.enable()
 
 
 class _GraphEntry:
@@ -190,7 +207,7 @@ class GraphedForward:
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
+        with _collector_off(), torch.cuda.graph(g):
             static_out = self._eager(*static_in)
         self.captures += 1
         self.graphed = True
@@ -376,8 +393,9 @@ class DataParallelTrainer:
             stash = [p.grad for p in params]
             for p in params:
                 p.grad = None
-            self._graphed = torch.cuda.make_graphed_callables(
-                _Body(), (pixel_values.detach().clone(), pixel_mask.detach().clone()), num_warmup_iters=3)
+            with _collector_off():
+                self._graphed = torch.cuda.make_graphed_callables(
+                    _Body(), (pixel_values.detach().clone(), pixel_mask.detach().clone()), num_warmup_iters=3)
             self._graph_key = key
             for p, g in zip(params, stash):  # drops what the warm-up / capture backward passes left behind
                 p.grad = g

@@ -1,0 +1,79 @@
+"""The launch sequence of the host model (egtr_amd/deformable_detr.py, egtr.py) is pinned: for each configuration below, the
+library entries that one forward -- or one train step -- goes through, in order, equal a table written here.
+
+The tables were taken with tools/route_trace.py from the PARENT of the commit that added this file (the commit itself only
+re-arranged the forward passes, and had to leave every sequence as it was).  They are not derived from the code under test: a
+pull request that changes a route on purpose updates its table by hand, and says so.  ATen operators are not pinned: their
+number belongs to torch's version, not to this project.
+
+Configurations (tools/route_trace.py CONFIGS; stub backbone and seeded weights of the ``small`` fixture, 24 queries, 2 encoder and
+3 decoder layers): T = one 448x448 image, 4 165 tokens -- just above SKINNY_MAX_ROWS = GEMM_SPLIT_MIN_ROWS = 4 096, where the
+split-GEMM, lazy-position, FFN, tail and multi-projection routes switch on --, T with each inference switch off in turn, and S =
+the fixture's padded batch of two (256 tokens per image) as an eval forward and as a train step."""
+import os
+import sys
+
+import pytest
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+import route_trace  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+PRE = ["egtr_input_proj_groupnorm_flatten_f32", "egtr_level_geometry_f32"]
+SPLIT, MSDA, LIN = "egtr_linear_split_bf16_grouped_pos_f32", "egtr_msda_forward_fused_vbias_f32", "egtr_linear_f32"
+GROUPED, GROUPED_LN = "egtr_linear_grouped_f32", "egtr_linear_grouped_ln_f32"
+LN, LN_POS, DROP_LN = "egtr_add_layernorm_f32", "egtr_add_layernorm_pos_f32", "egtr_dropout_add_layernorm_f32"
+LIN_BWD, LN_BWD, DROP_LN_BWD = "egtr_linear_backward_f32", "egtr_add_layernorm_backward_f32", "egtr_dropout_add_layernorm_backward_f32"
+COLSUM, WCOLSUM, WGRAD = "egtr_column_sum_f32", "egtr_weighted_column_sum_f32", "egtr_linear_split_bf16_wgrad_f32"
+MSDA_BWD = ["egtr_msda_backward_det_f32", "egtr_msda_geometry_backward_f32"]
+CLUSTER = [("egtr_decoder_layer_f32", 3)]
+HEADS = [GROUPED, (LIN, 2), "egtr_box_decode_argmax_f32", SPLIT, GROUPED, "egtr_rel_head_forward_bf16x6_f32"]
+T = PRE + 2 * [SPLIT, MSDA, "egtr_encoder_tail_x6_f32"] + ["egtr_proj_multi_x6_f32"] + CLUSTER + HEADS
+DECODER_LAYER = ["egtr_self_attn_forward_f32", LIN, GROUPED_LN, MSDA, LIN, GROUPED_LN, LIN]     # after its q / k / v projections
+ENCODER_TRAIN = [(LIN, 3), "egtr_msda_geometry_forward_f32", "egtr_msda_forward_f32", LIN, LN, (LIN, 2), LN,
+                 "egtr_any_nonfinite_f32", "egtr_clamp_if_flag_f32"]
+DECODER_TRAIN = [(LIN, 3), "egtr_self_attn_forward_f32", LIN, DROP_LN, (LIN, 3), "egtr_msda_geometry_forward_f32",
+                 "egtr_msda_forward_f32", LIN, DROP_LN, (LIN, 2), DROP_LN]
+DECODER_TRAIN_BWD = [DROP_LN_BWD, (LIN_BWD, 2), DROP_LN_BWD, LIN_BWD] + MSDA_BWD + [(LIN_BWD, 3), DROP_LN_BWD, LIN_BWD,
+                                                                                    "egtr_self_attn_backward_f32", (LIN_BWD, 3)]
+ENCODER_TRAIN_BWD = ["egtr_clamp_if_flag_f32", LN_BWD, (LIN_BWD, 2), LN_BWD, LIN_BWD] + MSDA_BWD + [(LIN_BWD, 3)]
+
+ROUTES = {
+    "T": T,
+    "T-no-FFN_FUSED": (PRE + 2 * [SPLIT, MSDA, "egtr_linear_split_bf16_f32", LN, ("egtr_linear_split_bf16_f32", 2), LN] + [SPLIT]
+                       + CLUSTER + HEADS),
+    "T-no-ENCODER_TAIL_FUSED": (PRE + 2 * [SPLIT, MSDA, "egtr_proj_ln_x6_f32", "egtr_ffn_x6_f32"] + ["egtr_proj_multi_x6_f32"]
+                                + CLUSTER + HEADS),
+    "T-no-LAZY_POS": T,             # the same entries: the position rows are an argument of the split GEMM, or added before it
+    "T-no-DEFER_LAYERNORM": T,      # the cluster decoder runs either way
+    "T-no-GEMM_SPLIT_BF16": (PRE + 2 * [MSDA, LN, LN_POS] + CLUSTER
+                             + [GROUPED, (LIN, 2), "egtr_box_decode_argmax_f32", (GROUPED, 2), "egtr_rel_head_forward_bf16x6_f32"]),
+    "T-no-DECODER_CLUSTER": (T[:T.index(CLUSTER[0])] + [GROUPED] + DECODER_LAYER + 2 * ([GROUPED_LN] + DECODER_LAYER) + [LN]
+                             + HEADS),
+    "S": PRE + 2 * [LIN, GROUPED, MSDA, LIN, LN, (LIN, 2), LN_POS] + CLUSTER + HEADS,
+    "S-train": (["egtr_level_geometry_f32"] + 2 * ENCODER_TRAIN + [LIN] + 3 * DECODER_TRAIN
+                + [(LIN, 4), "egtr_hungarian_match_f32", (LIN, 10), "egtr_rel_head_streams_f32",
+                   "egtr_rel_head_forward_bf16x6_save_f32", "egtr_detection_loss_f32", "egtr_relation_loss_det_f32",
+                   COLSUM, WGRAD, COLSUM, WCOLSUM, WGRAD, (COLSUM, 2), "egtr_rel_head_backward_pairs_f32", (LIN_BWD, 8), COLSUM,
+                   (LIN_BWD, 2), COLSUM]
+                + 3 * DECODER_TRAIN_BWD + [COLSUM] + 2 * ENCODER_TRAIN_BWD + [(WCOLSUM, 4)]),
+}
+
+
+def _flat(table):
+    return [name for item in table for name in ([item[0]] * item[1] if isinstance(item, tuple) else [item])]
+
+
+def test_the_pinned_configurations_are_the_ones_named_in_the_tool():
+    assert tuple(ROUTES) == route_trace.PINNED
+
+
+@pytest.mark.parametrize("name", list(ROUTES))
+def test_library_entry_sequence_equals_the_table(name):
+    lines, _ = route_trace.trace(name)
+    got = [line[4:] for line in lines if line.startswith("lib ")]
+    want = _flat(ROUTES[name])
+    first = next((i for i, (g, w) in enumerate(zip(got, want)) if g != w), min(len(got), len(want)))
+    assert got == want, f"{name}: differs at entry {first}: got {got[first:first + 3]}, table {want[first:first + 3]}"
+    assert lines[-1] == "fallbacks {}", lines[-1]
