@@ -153,6 +153,37 @@ def relation_losses(rel_logits, conn_logits, targets, indices, mcosts, nm_cost, 
     return torch.cat(rel_losses).mean(), torch.stack(conn_losses).mean()
 
 
+def _labels_boxes_card(lg, bx, idx, targets, num_boxes, focal_alpha, B, C):
+    """loss_labels, loss_boxes and loss_cardinality of ONE output set (egtr:611-712): the composition sgg_loss evaluates for
+    the main, the auxiliary and the encoder outputs.  B, C: batch size and class count of the MAIN logits."""
+    losses = {}
+    n_out = lg.shape[1]
+    bidx = torch.cat([torch.full_like(s, i) for i, (s, _) in enumerate(idx)])
+    sidx = torch.cat([s for s, _ in idx])
+    tc_o = torch.cat([t["class_labels"][j] for t, (_, j) in zip(targets, idx)])
+    tc = torch.full(lg.shape[:2], C, dtype=torch.int64)
+    tc[bidx, sidx] = tc_o
+    onehot = torch.zeros(B, n_out, C + 1, dtype=lg.dtype)
+    onehot.scatter_(2, tc.unsqueeze(-1), 1)
+    losses["loss_ce"] = sigmoid_focal_loss(lg, onehot[:, :, :-1], num_boxes, alpha=focal_alpha, gamma=2) * n_out  # egtr:647-656
+    src = bx[bidx, sidx]
+    tgt = torch.cat([t["boxes"][j] for t, (_, j) in zip(targets, idx)], dim=0)
+    losses["loss_bbox"] = F.l1_loss(src, tgt, reduction="none").sum() / num_boxes
+    giou = 1 - torch.diag(generalized_box_iou(center_to_corners(src), center_to_corners(tgt)))
+    losses["loss_giou"] = giou.sum() / num_boxes
+    with torch.no_grad():
+        tl = torch.as_tensor([len(t["class_labels"]) for t in targets]).float()
+        cp = (lg.argmax(-1) != lg.shape[-1] - 1).sum(1).float()
+        losses["cardinality_error"] = F.l1_loss(cp, tl)
+    return losses
+
+
+def labels_boxes_card(logits, boxes, indices, targets, num_boxes, focal_alpha):
+    """{"loss_ce", "loss_bbox", "loss_giou", "cardinality_error"} of one output set given its matches: what sgg_loss computes
+    for its main outputs, callable on its own (float64 inputs give a float64 evaluation)."""
+    return _labels_boxes_card(logits, boxes, indices, targets, num_boxes, focal_alpha, logits.shape[0], logits.shape[2])
+
+
 def sgg_loss(out, targets, cfg, training):
     """SceneGraphGenerationLoss.forward (egtr:953-1034) + the weighted sum of egtr:470-494.
 
@@ -169,25 +200,8 @@ def sgg_loss(out, targets, cfg, training):
     losses = {}
 
     def labels_boxes_card(lg, bx, idx, suffix="", targets=targets):
-        n_out = lg.shape[1]
-        bidx = torch.cat([torch.full_like(s, i) for i, (s, _) in enumerate(idx)])
-        sidx = torch.cat([s for s, _ in idx])
-        tc_o = torch.cat([t["class_labels"][j] for t, (_, j) in zip(targets, idx)])
-        tc = torch.full(lg.shape[:2], C, dtype=torch.int64)
-        tc[bidx, sidx] = tc_o
-        onehot = torch.zeros(B, n_out, C + 1, dtype=lg.dtype)
-        onehot.scatter_(2, tc.unsqueeze(-1), 1)
-        losses["loss_ce" + suffix] = sigmoid_focal_loss(lg, onehot[:, :, :-1], num_boxes,
-                                                        alpha=cfg["focal_alpha"], gamma=2) * n_out  # egtr:647-656
-        src = bx[bidx, sidx]
-        tgt = torch.cat([t["boxes"][j] for t, (_, j) in zip(targets, idx)], dim=0)
-        losses["loss_bbox" + suffix] = F.l1_loss(src, tgt, reduction="none").sum() / num_boxes
-        giou = 1 - torch.diag(generalized_box_iou(center_to_corners(src), center_to_corners(tgt)))
-        losses["loss_giou" + suffix] = giou.sum() / num_boxes
-        with torch.no_grad():
-            tl = torch.as_tensor([len(t["class_labels"]) for t in targets]).float()
-            cp = (lg.argmax(-1) != lg.shape[-1] - 1).sum(1).float()
-            losses["cardinality_error" + suffix] = F.l1_loss(cp, tl)
+        for k, v in _labels_boxes_card(lg, bx, idx, targets, num_boxes, cfg["focal_alpha"], B, C).items():
+            losses[k + suffix] = v
 
     labels_boxes_card(logits, boxes, indices)
 

@@ -72,45 +72,8 @@ def test_float64_backward_is_refused_by_name_under_the_mode():
 
 
 # ---- the tie rule of egtr_relation_loss_det_*: restated with numpy ---------------------------------------------------------
-def topk_lowest_index_first(logits, candidates, k):
-    """Boolean mask (shape of ``logits``) of the ``k`` candidates with the largest logit, ties broken by the LOWEST flat
-    (C-order) index: top-k by (logit descending, flat index ascending)."""
-    flat, cand = np.asarray(logits).reshape(-1), np.asarray(candidates).reshape(-1)
-    idx = np.nonzero(cand)[0]
-    order = idx[np.lexsort((idx, -flat[idx].astype(np.float64)))]   # last key is the primary one
-    sel = np.zeros(flat.shape, dtype=bool)
-    sel[order[:k]] = True
-    return sel.reshape(np.asarray(logits).shape)
-
-
-def relation_selection(pred_rel, dense, pred_idx, tgt_idx, k_neg, k_nm):
-    """One image of the relation loss (model/egtr.py:754-923, largest-score sampling) in query order, with the deterministic
-    tie rule.  pred_rel [N, N, R]; dense [N, N, R] 0 / 1 targets in TARGET order; pred_idx / tgt_idx: the matcher's pairs.
-    Returns (mult [N, N, R] int: how often an element enters the mean, target in query order, matched [N] bool,
-    per problem (k, tied candidates at the threshold, of which needed))."""
-    N, _, R = pred_rel.shape
-    T = len(pred_idx)
-    matched = np.zeros(N, dtype=bool)
-    matched[pred_idx] = True
-    tq = np.zeros(N, dtype=np.int64)
-    tq[pred_idx] = tgt_idx
-    tq[~matched] = T + np.arange(N - T)          # unmatched queries in ascending order take rows T, T + 1, ...
-    t = dense[tq][:, tq]                          # target in query order
-    blk = (matched[:, None] & matched[None, :])[:, :, None].repeat(R, 2)
-    n_true, n_false = int((t[blk] != 0).sum()), int((t[blk] != 1).sum())
-    n_nm = (N * N - T * T) * R
-    k = (min(n_true * k_neg, n_false), min(n_true * k_nm, n_nm)) if n_true > 0 else (0, 0)
-    mult = (blk & (t != 0)).astype(np.int64)
-    info = []
-    for prob, cand in enumerate((blk & (t != 1), ~blk)):
-        sel = topk_lowest_index_first(pred_rel, cand, k[prob])
-        mult += sel
-        if k[prob]:
-            thr = np.sort(pred_rel[cand])[::-1][k[prob] - 1]
-            info.append((k[prob], int((pred_rel[cand] == thr).sum()), k[prob] - int((pred_rel[cand] > thr).sum())))
-        else:
-            info.append((0, 0, 0))
-    return mult, t, matched, info
+# (tests/loss_restated.py; tests/test_gpu_deterministic.py imports the two names from here)
+from loss_restated import relation_selection, topk_lowest_index_first  # noqa: E402,F401
 
 
 def test_tie_rule_restatement():

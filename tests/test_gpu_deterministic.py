@@ -17,7 +17,7 @@ import helpers as Hh
 import weights as W
 from oracle import loss as OL
 from oracle import msda as OM
-from test_deterministic_cpu import relation_selection
+from test_deterministic_cpu import relation_selection  # noqa: F401  (the restatement's long-standing import path)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -196,22 +196,10 @@ def tie_case():
 
 
 def tie_expectation(c):
-    """float64 numpy: (grad_rel [B, N, N, R], loss_rel, per-image tie info) under the lowest-index-first rule."""
-    nm = float(OL.nonmatching_cost(2.0, 5.0, 2.0, 1e-14))
-    sig = lambda z: 1.0 / (1.0 + np.exp(-z))  # noqa: E731
-    mults, ys, infos = [], [], []
-    for b in range(c["B"]):
-        pi, ti = c["indices"][b][0].numpy(), c["indices"][b][1].numpy()
-        mult, t, matched, info = relation_selection(c["pred_rel"][b].numpy(), c["dense"][b].numpy(), pi, ti, K_TIE, K_TIE)
-        w = np.full(c["N"], 1.0 - sig(nm))
-        w[pi] = 1.0 - sig(c["costs"][b].double().numpy())
-        mults.append(mult)
-        ys.append(t.astype(np.float64) * (w[:, None] * w[None, :])[:, :, None])
-        infos.append(info)
-    mult, y, x = np.stack(mults), np.stack(ys), c["pred_rel"].double().numpy()
-    total = mult.sum()
-    bce = np.maximum(x, 0) - x * y + np.log1p(np.exp(-np.abs(x)))
-    return mult * (sig(x) - y) / total, float((mult * bce).sum() / total), infos, mult
+    """float64 numpy: (grad_rel [B, N, N, R], loss_rel, per-image tie info, mult) under the lowest-index-first rule."""
+    from loss_restated import relation_expectation
+    e = relation_expectation(c, K_TIE, K_TIE, order="key")
+    return e.grad, e.loss_rel, e.info, e.mult
 
 
 def test_loss_ties_are_taken_lowest_index_first():
