@@ -647,7 +647,10 @@ struct GnLevels {
 };
 
 // stats[(l * B + b) * G + g] = (mean, rstd) of (x + conv_bias) over the C/G channels x H_l W_l pixels of one group.
-// One pass: per-thread fp32 partial sums of <= ~100 elements, combined in double (E[x^2] - mean^2 in double).
+// One pass, every element accumulated in DOUBLE: v = x + conv_bias is formed in double (exact to 2^-53) and a thread adds the
+// v and v^2 of its cpg * ceil(hw / 1024) elements (80 for a 9 400-pixel level) to double sums, so E[v^2] - mean^2 loses
+// ~n 2^-53 mean^2, not the n 2^-24 mean^2 of fp32 partial sums: a group whose mean is 300 standard deviations away still gets
+// its variance to fp32 rounding (tests/test_gpu_input_proj_groupnorm.py, family "offset").
 __device__ __forceinline__ float gn_load(const float* p) { return *p; }
 __device__ __forceinline__ float gn_load(const unsigned short* p) { return bf2f(*p); }
 
@@ -657,9 +660,9 @@ __global__ __launch_bounds__(1024) void gn_stats_levels(GnLevels P, int C, int G
   const int g = blockIdx.x, b = blockIdx.y, l = blockIdx.z;
   const int cpg = C / G, hw = P.hw[l];
   const T* x = static_cast<const T*>(P.x[l]) + ((size_t)b * C + (size_t)g * cpg) * hw;  // the group's channels are contiguous in NCHW
-  float s1 = 0.f, s2 = 0.f;
+  double s1 = 0.0, s2 = 0.0;
   for (int c = 0; c < cpg; ++c) {
-    const float cb = P.conv_bias[l][g * cpg + c];
+    const double cb = (double)P.conv_bias[l][g * cpg + c];
     const T* xc = x + (size_t)c * hw;
     // 8 loads in flight per thread, accumulated in the original order (the loop was one dependent load -> add per
     // ~300 ns: 73 round trips for the 75 000 elements of a level-0 group)
@@ -673,14 +676,14 @@ __global__ __launch_bounds__(1024) void gn_stats_levels(GnLevels P, int C, int G
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
         if (i0 + 1024 * u < hw) {
-          const float t = v[u] + cb;
+          const double t = (double)v[u] + cb;
           s1 += t;
-          s2 += t * t;
+          s2 = fma(t, t, s2);
         }
       }
     }
   }
-  double d1 = (double)s1, d2 = (double)s2;
+  double d1 = s1, d2 = s2;
 #pragma unroll
   for (int o = 1; o < 64; o <<= 1) {
     d1 += __shfl_xor(d1, o);
@@ -698,7 +701,9 @@ __global__ __launch_bounds__(1024) void gn_stats_levels(GnLevels P, int C, int G
       t2 += s_red[1][w];
     }
     const double n = (double)cpg * hw, mean = t1 / n;
-    const double var = fmax(t2 / n - mean * mean, 0.0);  // biased, as nn.GroupNorm
+    // biased, as nn.GroupNorm.  The clamp is still reachable: a group of (nearly) equal values whose sums are not exact in
+    // double can come out at -n 2^-53 mean^2, which is nothing next to eps but must not reach the square root as a negative
+    const double var = fmax(t2 / n - mean * mean, 0.0);
     stats[((size_t)l * gridDim.y + b) * G + g] = make_float2((float)mean, (float)(1.0 / sqrt(var + (double)eps)));
   }
 }
@@ -902,8 +907,10 @@ __global__ __launch_bounds__(256) void gn_partial_tokens(GnTokLevels P, int L, i
   const int g = threadIdx.x & 31, ph = threadIdx.x >> 5;
   const T* x = static_cast<const T*>(P.x[l]) + (size_t)b * hw * 256;
   const float4 ba = *reinterpret_cast<const float4*>(P.conv_bias[l] + 8 * g), bb = *reinterpret_cast<const float4*>(P.conv_bias[l] + 8 * g + 4);
-  const float cb[8] = {ba.x, ba.y, ba.z, ba.w, bb.x, bb.y, bb.z, bb.w};
-  float s1 = 0.f, s2 = 0.f;
+  const double cb[8] = {ba.x, ba.y, ba.z, ba.w, bb.x, bb.y, bb.z, bb.w};
+  // every element is accumulated in double, as in gn_stats_levels: fp32 partial sums of a thread's <= 256 elements put the
+  // variance of a group with mean / std = 3 outside fp32 rounding already (E[v^2] - mean^2 cancels)
+  double s1 = 0.0, s2 = 0.0;
   bool summed = false;
   if constexpr (SPLIT) {
     const int ns = SL.S[l];
@@ -934,9 +941,9 @@ __global__ __launch_bounds__(256) void gn_partial_tokens(GnTokLevels P, int L, i
         dst[1] = make_float4(f[4], f[5], f[6], f[7]);
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
-          const float v = f[k] + cb[k];
+          const double v = (double)f[k] + cb[k];
           s1 += v;
-          s2 += v * v;
+          s2 = fma(v, v, s2);
         }
       }
     }
@@ -957,16 +964,16 @@ __global__ __launch_bounds__(256) void gn_partial_tokens(GnTokLevels P, int L, i
         if (t < hw) {
 #pragma unroll
           for (int k = 0; k < 8; ++k) {
-            const float v = f[u][k] + cb[k];
+            const double v = (double)f[u][k] + cb[k];
             s1 += v;
-            s2 += v * v;
+            s2 = fma(v, v, s2);
           }
         }
       }
     }
   }
-  s_red[0][g][ph] = (double)s1;
-  s_red[1][g][ph] = (double)s2;
+  s_red[0][g][ph] = s1;
+  s_red[1][g][ph] = s2;
   __syncthreads();
   if (threadIdx.x < 32) {
     double t1 = 0.0, t2 = 0.0;
@@ -1002,7 +1009,8 @@ __global__ __launch_bounds__(256) void gn_finalize_tokens(GnTokLevels P, int chu
     t2 += s_part[k][g].y;
   }
   const double n = 8.0 * P.hw[l], mean = t1 / n;
-  const double var = fmax(t2 / n - mean * mean, 0.0);  // biased, as nn.GroupNorm
+  // biased, as nn.GroupNorm; the clamp is still reachable (see gn_stats_levels: -n 2^-53 mean^2 on nearly equal values)
+  const double var = fmax(t2 / n - mean * mean, 0.0);
   stats[((size_t)l * B + b) * 32 + g] = make_float2((float)mean, (float)(1.0 / sqrt(var + (double)eps)));
 }
 

@@ -13,19 +13,12 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 import helpers as H
+from groupnorm_restated import sum_slabs as _sum_slabs     # fp32, slab order 0, 1, ...: gn_partial_tokens<float, true>'s
 from test_gpu_backbone_x6 import ADVERSARIAL, Case, _adversarial, _check_per_output, _check_six_terms, _check_teeth, _gen
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 FAMILIES = ["act", "wgt"]
-
-
-def _sum_slabs(slabs):
-    """fp32, slab order 0, 1, ...: the order of gn_partial_tokens<float, true>"""
-    y = slabs[0]
-    for s in range(1, slabs.shape[0]):
-        y = y + slabs[s]
-    return y
 
 
 def _plan(cases):
