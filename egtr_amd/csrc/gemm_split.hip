@@ -67,6 +67,65 @@ struct GemmProblems {
   GemmProblem p[kMaxProblems];
 };
 
+// The epilogue of a tile as a function, for the one-term kernel (gemm_bf16r_f32 below): bias, ReLU, row_keep, relu_ref, add1 / add2,
+// the store and colpart, in this order.  wm / wn: the wave's place in the workgroup's BM x 128 tile.  The six-term kernel keeps
+// the same statements in its own body: routed through this function its register allocation changed throughout, and its
+// instruction stream is to stay the parent's (the weight gradient keeps its own loop for the same reason).
+template <int NT>
+__device__ __forceinline__ void gemm_epilogue(const GemmProblem& G, const f32x16 (&acc)[NT], int M, int nb, int m0, int wm, int wn,
+                                              int li, int hf) {
+  const float* __restrict__ bias = G.bias;
+  float* __restrict__ C = G.C;
+  const int ldc = G.ldc;
+  const bool RELU = G.relu != 0;
+  // D[i = n][j = m]; accumulator r <-> column n = (r & 3) + 8 (r >> 2) + 4 hf of the 32-wide n tile, row m = lane & 31: one
+  // float4 (4 consecutive columns) per accumulator quad
+  const int row = m0 + wm * 32 + li;
+  const bool in_range = row < M;
+  const bool keep = in_range && (G.row_keep == nullptr || G.row_keep[row] != 0);
+  const float* __restrict__ relu_ref = G.relu_ref;
+  const float* add1 = G.add1;
+  const float* add2 = G.add2;
+  float* __restrict__ colpart = G.colpart;
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int col = nb * kBN + wn * (32 * NT) + nt * 32 + 8 * q + 4 * hf;
+      float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (bias != nullptr) bv = *reinterpret_cast<const float4*>(bias + col);
+      float4 v = make_float4(acc[nt][4 * q + 0] + bv.x, acc[nt][4 * q + 1] + bv.y, acc[nt][4 * q + 2] + bv.z,
+                             acc[nt][4 * q + 3] + bv.w);
+      if (RELU) v = make_float4(egtr_relu(v.x), egtr_relu(v.y), egtr_relu(v.z), egtr_relu(v.w));
+      if (!keep) v = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (relu_ref != nullptr && in_range) {
+        const float4 t = *reinterpret_cast<const float4*>(relu_ref + (size_t)row * G.ldref + col);
+        v = make_float4(t.x > 0.f ? v.x : 0.f, t.y > 0.f ? v.y : 0.f, t.z > 0.f ? v.z : 0.f, t.w > 0.f ? v.w : 0.f);
+      }
+      if (add1 != nullptr && in_range) {
+        const float4 t = *reinterpret_cast<const float4*>(add1 + (size_t)row * G.ldadd + col);
+        v = make_float4(v.x + t.x, v.y + t.y, v.z + t.z, v.w + t.w);
+      }
+      if (add2 != nullptr && in_range) {
+        const float4 t = *reinterpret_cast<const float4*>(add2 + (size_t)row * G.ldadd + col);
+        v = make_float4(v.x + t.x, v.y + t.y, v.z + t.z, v.w + t.w);
+      }
+      if (in_range) *reinterpret_cast<float4*>(C + (size_t)row * ldc + col) = v;
+      if (colpart != nullptr) {   // uniform per workgroup: sum over the wave's 32 rows (the 32 lanes that share hf)
+        float4 s = in_range ? v : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int o = 1; o < 32; o <<= 1) {
+          s.x += __shfl_xor(s.x, o);
+          s.y += __shfl_xor(s.y, o);
+          s.z += __shfl_xor(s.z, o);
+          s.w += __shfl_xor(s.w, o);
+        }
+        // (a 32-row block that starts at or beyond M does not exist in the [ceil(M / 32), N] buffer)
+        if (li == 0 && m0 + wm * 32 < M) *reinterpret_cast<float4*>(colpart + (size_t)((m0 >> 5) + wm) * G.N + col) = s;
+      }
+    }
+}
+
 // (A double-buffered form of this loop -- two LDS stage buffers, one barrier per stage, 120 KiB of LDS = one workgroup per CU --
 // and a ping-pong schedule on it were measured 7-15 % slower in round 5 and removed in round 6: DESIGN.md 4.12,
 // profiles/r05_gemm_double_buffer_ab.txt; the code is in the history, commit 46d9c2f and before.)
@@ -209,10 +268,143 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     }
 }
 
+// ---- the one-term counterpart: matmul precision "bf16" of the training routes (ops.set_matmul_precision) ----
+// Each operand is rounded ONCE to bf16, round to nearest even: the fp32 activations (after the on-load `+ pos`) by
+// v_cvt_pk_bf16_f32 on their way into LDS, the weights by the one-piece tiling launches below.  One MFMA per k-step instead of
+// six, fp32 accumulation, the same tiles, grouping and epilogue.  Inf and NaN survive the rounding (a non-finite activation makes
+// its output row non-finite and nothing else); a finite value beyond the largest bf16 (3.39e38) rounds to Inf.
+// The weight stream is [N/128][K/32][128 rows][32] bf16: 8 KiB blocks, consecutive in k for one n block, so that the stage depth
+// is the kernel's own choice.  A stage is BK = kR1StageK columns of k where K allows, else 32 (K % 32 == 0 is all the entry
+// asks, like the six-term one): with one piece an LDS stage of depth 32 is 20 KiB and its two barriers no longer hide behind six
+// MFMAs per k-step (DESIGN.md 4.12b has the measurements).  LDS rows are BK + 8 elements apart (80 / 144 / 272 bytes): the 16-byte
+// operand reads of 16 consecutive rows fall on 16 different bank quads.
+#ifndef EGTR_BF16R_STAGE_K
+#define EGTR_BF16R_STAGE_K 64
+#endif
+#ifndef EGTR_BF16R_STAGE_M
+#define EGTR_BF16R_STAGE_M 32
+#endif
+constexpr int kR1StageK = EGTR_BF16R_STAGE_K;   // forward / data gradient: 32, 64 or 128
+constexpr int kR1StageM = EGTR_BF16R_STAGE_M;   // weight gradient (rows of the reduction per stage): 32 or 64
+// Measured (tools/matmul_precision_bench.py on builds with other -DEGTR_BF16R_STAGE_K / _M, profiles/matmul_precision_stage_ablation.txt;
+// sum of the twelve training-size launches, six-term 1407-1445 us): K 32 / M 32: 649 us; K 64 / M 32: 613 us (taken); K 128 spills
+// 87 registers in the 128-row form and is slower than the six-term kernel; M 64 makes every weight gradient 1.8-2.6 x SLOWER than
+// M 32 (55 vs 30 us at 256 x 256) and its EXT form spills.  The macros stay for such builds; the masked weight gradient is 32 always.
+constexpr int kR1StageMExt = 32;
+static_assert(kR1StageK == 32 || kR1StageK == 64 || kR1StageK == 128, "stage depth");
+static_assert(kR1StageM == 32 || kR1StageM == 64, "stage depth");
+constexpr int kR1WBlockBytes = 2 * kBN * 32;
+
+// two fp32 -> one dword of two bf16, round to nearest even (v_cvt_pk_bf16_f32); a in the low half (the lower address)
+__device__ __forceinline__ unsigned cvt_pk_bf16_rne(float a, float b) {
+  typedef float f32x2 __attribute__((ext_vector_type(2)));
+  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+  const f32x2 v = {a, b};
+  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
+}
+// one stage out of LDS: BK / 16 k-steps x (1 + NT) 16-byte reads and one product per 32-column tile of the wave
+template <int NT, int BK>
+__device__ __forceinline__ void stage_product1(const __bf16* pa, const __bf16* pw, f32x16 (&acc)[NT]) {
+  constexpr int pitch = BK + 8;
+#pragma unroll
+  for (int ks = 0; ks < BK / 16; ++ks) {
+    const bf16x8 a = *reinterpret_cast<const bf16x8*>(pa + 16 * ks);
+#pragma unroll
+    for (int t = 0; t < NT; ++t) acc[t] = mfma(*reinterpret_cast<const bf16x8*>(pw + t * 32 * pitch + 16 * ks), a, acc[t]);
+  }
+}
+
+template <int BM, int BK>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) void gemm_bf16r_f32(GemmProblems P, int nprob, int M,
+                                                                                                  int K) {
+  const int mblocks = (M + BM - 1) / BM;
+  int tile = xcd_tile(blockIdx.x, gridDim.x), pi = 0;
+  for (; pi + 1 < nprob; ++pi) {
+    const int t = (P.p[pi].N / kBN) * mblocks;
+    if (tile < t) break;
+    tile -= t;
+  }
+  const GemmProblem& G = P.p[pi];
+  const int nblocks = G.N / kBN;
+  const int nb = tile % nblocks, m0 = (tile / nblocks) * BM;
+  const float* __restrict__ A = G.A;
+  const int lda = G.lda;
+  constexpr int WAVES_M = BM / 32, WAVES_N = 8 / WAVES_M, NT = 4 / WAVES_N;
+  constexpr int C4 = BK / 4;            // float4 per row of A and stage
+  constexpr int AQ = BM * C4 / 512;     // float4 of A per thread and stage
+  constexpr int WQ = BK / 32;           // weight blocks per stage = 16-byte chunks of W per thread and stage
+  constexpr int pitch = BK + 8;
+  __shared__ __attribute__((aligned(16))) __bf16 sbase[(BM + kBN) * pitch];
+  __bf16* sA = sbase;
+  __bf16* sW = sbase + BM * pitch;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave / WAVES_N, wn = wave % WAVES_N;
+  const int li = lane & 31, hf = lane >> 5;
+  const int nk = K / BK;
+
+  // A: BM x C4 float4 per stage, thread t takes idx = t + 512 q: row = idx / C4, c4 = idx % C4
+  // W: WQ blocks of 512 16-byte chunks [row 128][4 chunks of 8 bf16]; thread t takes chunk t of each block
+  const float* arow[AQ];
+  const float* prow[AQ];
+  const bool has_pos = G.pos != nullptr;   // uniform per workgroup
+#pragma unroll
+  for (int q = 0; q < AQ; ++q) {
+    const int idx = tid + 512 * q;
+    const int row = min(m0 + idx / C4, M - 1);
+    arow[q] = A + (size_t)row * lda + 4 * (idx % C4);
+    prow[q] = has_pos ? G.pos + (size_t)(row % G.pos_rows) * K + 4 * (idx % C4) : arow[q];
+  }
+  const char* wblk = reinterpret_cast<const char*>(G.Wt) + (size_t)nb * (K / 32) * kR1WBlockBytes + (size_t)tid * 16;
+
+  f32x4v ra[AQ], rp[AQ], rw[WQ];
+  auto issue = [&](int s) {
+#pragma unroll
+    for (int q = 0; q < AQ; ++q) ra[q] = gload(arow[q] + s * BK);
+    if (has_pos) {
+#pragma unroll
+      for (int q = 0; q < AQ; ++q) rp[q] = gload(prow[q] + s * BK);
+    }
+#pragma unroll
+    for (int q = 0; q < WQ; ++q) rw[q] = gload(wblk + (size_t)(s * WQ + q) * kR1WBlockBytes);
+  };
+  auto stash = [&]() {
+    vm_wait0(ra);
+    vm_wait0(rw);
+    if (has_pos) {
+#pragma unroll
+      for (int q = 0; q < AQ; ++q) {
+        vm_wait0(rp[q]);
+        ra[q] += rp[q];
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < AQ; ++q) {
+      const int idx = tid + 512 * q;
+      *reinterpret_cast<uint2*>(sA + (idx / C4) * pitch + 4 * (idx % C4)) =
+          make_uint2(cvt_pk_bf16_rne(ra[q].x, ra[q].y), cvt_pk_bf16_rne(ra[q].z, ra[q].w));
+    }
+#pragma unroll
+    for (int q = 0; q < WQ; ++q) *reinterpret_cast<f32x4v*>(sW + (tid >> 2) * pitch + 32 * q + 8 * (tid & 3)) = rw[q];
+  };
+
+  f32x16 acc[NT];
+#pragma unroll
+  for (int a = 0; a < NT; ++a)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[a][r] = 0.f;
+
+  const __bf16* pa = sA + (wm * 32 + li) * pitch + 8 * hf;
+  const __bf16* pw = sW + (wn * (32 * NT) + li) * pitch + 8 * hf;
+  staged_loop(nk, issue, [&]() { stage_product1<NT, BK>(pa, pw, acc); }, stash);
+
+  gemm_epilogue<NT>(G, acc, M, nb, m0, wm, wn, li, hf);
+}
+
 }  // namespace
 
 namespace {
-int launch_grouped(hipStream_t st, const GemmProblems& P, int nprob, int M, int K) {
+// pieces: 3 = the six-term kernel on the three-piece weight stream, 1 = the one-term kernel on the one-piece stream
+int launch_grouped(hipStream_t st, const GemmProblems& P, int nprob, int M, int K, int pieces = 3) {
   long long tiles128 = 0, tiles64 = 0;
   for (int i = 0; i < nprob; ++i) {
     tiles128 += (long long)(P.p[i].N / kBN) * ((M + 127) / 128);
@@ -227,6 +419,19 @@ int launch_grouped(hipStream_t st, const GemmProblems& P, int nprob, int M, int 
   // (value 256 -> 256 + offsets / weights 256 -> 384, M = 12 537) has 490 128-row tiles = 980 64-row tiles: one nearly full round
   // of the larger tiles beats 1.91 rounds of the smaller ones -- 42.9 -> 37.2 us per launch, 281.9 -> 284.7 images/s end to end
   // (three alternations on one box, abl/infer_ab.sh).
+  if (pieces == 1) {   // the same tile-height rule; the deep stage where K is a multiple of it
+    const bool deep = K % kR1StageK == 0;
+    const dim3 grid((unsigned)(tiles128 >= 480 ? tiles128 : tiles64));
+    if (tiles128 >= 480 && deep)
+      hipLaunchKernelGGL((gemm_bf16r_f32<128, kR1StageK>), grid, dim3(512), 0, st, P, nprob, M, K);
+    else if (tiles128 >= 480)
+      hipLaunchKernelGGL((gemm_bf16r_f32<128, 32>), grid, dim3(512), 0, st, P, nprob, M, K);
+    else if (deep)
+      hipLaunchKernelGGL((gemm_bf16r_f32<64, kR1StageK>), grid, dim3(512), 0, st, P, nprob, M, K);
+    else
+      hipLaunchKernelGGL((gemm_bf16r_f32<64, 32>), grid, dim3(512), 0, st, P, nprob, M, K);
+    return egtr_check_launch();
+  }
   if (tiles128 >= 480)
     hipLaunchKernelGGL(gemm_split_bf16_f32<128>, dim3((unsigned)tiles128), dim3(512), 0, st, P, nprob, M, K);
   else
@@ -360,6 +565,97 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
           make_float4(acc[nt][4 * q + 0], acc[nt][4 * q + 1], acc[nt][4 * q + 2], acc[nt][4 * q + 3]);
 }
 
+// The one-term counterpart (matmul precision "bf16"): both operands rounded once to bf16 (RNE, v_cvt_pk_bf16_f32; x after the
+// on-load `+ xpos`) on their way into LDS, one MFMA per k-step.  Same tiles, split-K chunks, workspace layout and fixed-order
+// reduction; a stage is BK = kR1StageM rows of the reduction: each thread transposes BK / 32 groups of 8 rows of its column.
+template <bool EXT, int BK>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) void wgrad_bf16r_f32(
+    const float* __restrict__ G, int ldg, const float* __restrict__ X, int ldx, float* __restrict__ partial, int M, int N,
+    int K, int rows_per_chunk, const float* __restrict__ xpos, int pos_rows, const unsigned char* __restrict__ row_keep) {
+  constexpr int BM = 128, R = BK / 32, pitch = BK + 8;
+  const int ktiles = K / kBN, tiles = (N / BM) * ktiles;
+  const int lb = xcd_tile(blockIdx.x, gridDim.x);
+  const int chunk = lb / tiles, t = lb - chunk * tiles;
+  const int n0 = (t / ktiles) * BM, k0 = (t % ktiles) * kBN;
+  const int mbeg = chunk * rows_per_chunk, mend = min(M, mbeg + rows_per_chunk);
+  const int nstage = (mend - mbeg + BK - 1) / BK;
+  __shared__ __attribute__((aligned(16))) __bf16 sG[BM * pitch];
+  __shared__ __attribute__((aligned(16))) __bf16 sX[kBN * pitch];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1;     // 4 x 2 waves: 32 rows (n) x 64 columns (k) each
+  const int li = lane & 31, hf = lane >> 5;
+  const int col = tid & 127, mq = tid >> 7;    // loader: column of the tile, rows 8 (mq + 4 h) .. + 7 of the stage, h < R
+  const float* gp = G + n0 + col;
+  const float* xp = X + k0 + col;
+  const float* pp = (EXT && xpos != nullptr) ? xpos + k0 + col : nullptr;
+
+  float rg[8 * R], rx[8 * R];
+  auto issue = [&](int s) {
+#pragma unroll
+    for (int h = 0; h < R; ++h) {
+      const int m = mbeg + s * BK + (mq + 4 * h) * 8;
+      if constexpr (EXT) {
+        float rp[8];
+        unsigned char rk[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {   // all loads of the group first (no test between them), then the arithmetic
+          const bool ok = m + e < mend;
+          const unsigned r = (unsigned)(ok ? m + e : mbeg);
+          rg[8 * h + e] = gp[(size_t)r * ldg];
+          rx[8 * h + e] = xp[(size_t)r * ldx];
+          rp[e] = pp != nullptr ? pp[(size_t)(r % (unsigned)pos_rows) * K] : 0.f;
+          rk[e] = row_keep != nullptr ? row_keep[r] : (unsigned char)1;
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const bool ok = m + e < mend;
+          rg[8 * h + e] = (ok && rk[e] != 0) ? rg[8 * h + e] : 0.f;
+          rx[8 * h + e] = ok ? rx[8 * h + e] + rp[e] : 0.f;
+        }
+      } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const bool ok = m + e < mend;
+          const size_t r = (size_t)(ok ? m + e : mbeg);
+          const float a = gp[r * ldg], b = xp[r * ldx];
+          rg[8 * h + e] = ok ? a : 0.f;
+          rx[8 * h + e] = ok ? b : 0.f;
+        }
+      }
+    }
+  };
+  // eight reduction rows of one column -> one 16-byte LDS row segment
+  auto stash_one = [&](const float (&v)[8 * R], __bf16* base) {
+#pragma unroll
+    for (int h = 0; h < R; ++h)
+      *reinterpret_cast<uint4*>(base + col * pitch + (mq + 4 * h) * 8) =
+          make_uint4(cvt_pk_bf16_rne(v[8 * h + 0], v[8 * h + 1]), cvt_pk_bf16_rne(v[8 * h + 2], v[8 * h + 3]),
+                     cvt_pk_bf16_rne(v[8 * h + 4], v[8 * h + 5]), cvt_pk_bf16_rne(v[8 * h + 6], v[8 * h + 7]));
+  };
+  auto stash = [&]() {
+    stash_one(rg, sG);
+    stash_one(rx, sX);
+  };
+
+  f32x16 acc[2];
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[a][r] = 0.f;
+
+  const __bf16* pa = sG + (wm * 32 + li) * pitch + 8 * hf;
+  const __bf16* pw = sX + (wn * 64 + li) * pitch + 8 * hf;
+  if (nstage > 0) staged_loop(nstage, issue, [&]() { stage_product1<2, BK>(pa, pw, acc); }, stash);
+  // D[i = k][j = n]: accumulator r <-> k = (r & 3) + 8 (r >> 2) + 4 hf of the 32-wide k tile, n = lane & 31
+  float* out = partial + ((size_t)chunk * N + n0 + wm * 32 + li) * K + k0 + wn * 64 + 4 * hf;
+#pragma unroll
+  for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      *reinterpret_cast<float4*>(out + nt * 32 + 8 * q) =
+          make_float4(acc[nt][4 * q + 0], acc[nt][4 * q + 1], acc[nt][4 * q + 2], acc[nt][4 * q + 3]);
+}
+
 // out[i] = sum over chunks of partial[c][i] (float4 columns; 16 columns x 16 chunk lanes per workgroup, fixed order)
 __global__ __launch_bounds__(256) void wgrad_reduce_f32(const float4* __restrict__ partial, int chunks, int n4,
                                                         float4* __restrict__ out) {
@@ -389,13 +685,13 @@ __global__ __launch_bounds__(256) void wgrad_reduce_f32(const float4* __restrict
 struct WgradPlan {
   int chunks, rows_per_chunk;
 };
-WgradPlan wgrad_plan(int M, int N, int K) {
+WgradPlan wgrad_plan(int M, int N, int K, int bk = kBK) {   // bk: rows of the reduction per stage
   const int tiles = (N / 128) * (K / 128);
   // two workgroups per CU; measured for 256 x 256 / 256 x 1024 over 50 148 rows with 256 / 384 / 512 / 768 / 1024 / 1536
   // workgroups: 53.6 / 56.4 / 53.2 / 59.8 / 64.4 / 69.8 us and 181.8 / 190.4 / 175.5 / 181.6 / 183.7 / 192.7 us
   int chunks = std::max(1, (512 + tiles - 1) / tiles);
-  chunks = std::min(chunks, (M + kBK - 1) / kBK);
-  const int rpc = ((M + chunks - 1) / chunks + kBK - 1) / kBK * kBK;
+  chunks = std::min(chunks, (M + bk - 1) / bk);
+  const int rpc = ((M + chunks - 1) / chunks + bk - 1) / bk * bk;
   return WgradPlan{(M + rpc - 1) / rpc, rpc};
 }
 
@@ -404,16 +700,22 @@ WgradPlan wgrad_plan(int M, int N, int K) {
 // stay exact in fp32); one thread per element, consecutive threads along k of one row -> 64-byte output segments.
 // Thread idx of a [N, K] weight takes element (k = idx & 31, n = (idx >> 5) & 127) of stage block idx >> 12: returns the slot
 // of its hi piece in the stream, (n, k) the element's place in the weight.
+template <int PIECES>
 __device__ __forceinline__ unsigned short* tiled_slot(unsigned short* out, int idx, int K, int& n, int& k) {
   const int kk = idx & 31, nn = (idx >> 5) & 127, blk = idx >> 12;
   const int ktiles = K / kBK;
   n = (blk / ktiles) * kBN + nn;
   k = (blk % ktiles) * kBK + kk;
-  return out + (size_t)blk * kWStageElems + nn * kBK + kk;
+  return out + (size_t)blk * (PIECES * kWPieceElems) + nn * kBK + kk;
 }
 // (xs::bf16_rne_bits, not xs::split3_rne: a non-finite weight keeps the NaN residuals inf - inf it always had here)
+template <int PIECES>
 __device__ __forceinline__ void store_split_rne(unsigned short* o, float x) {
   const unsigned hi = xs::bf16_rne_bits(x);
+  if constexpr (PIECES == 1) {   // the one-piece stream of the one-term kernels: the element rounded once
+    o[0] = (unsigned short)(hi >> 16);
+    return;
+  }
   const float r1 = x - __uint_as_float(hi);
   const unsigned mid = xs::bf16_rne_bits(r1);
   const unsigned lo = xs::bf16_rne_bits(r1 - __uint_as_float(mid));
@@ -423,12 +725,13 @@ __device__ __forceinline__ void store_split_rne(unsigned short* o, float x) {
 }
 // `pair`: the second half of the grid writes the tiling of W^T behind the first one (out + 3 N K), so that the forward
 // of a training step prepares the operand of its data-gradient product in the same launch.
+template <int PIECES>
 __global__ __launch_bounds__(256) void tile_weights_f32(const float* __restrict__ w, int ldw, int transposed, int N, int K,
                                                         unsigned short* __restrict__ out, int pair) {
   int idx = blockIdx.x * 256 + threadIdx.x;
   if (pair && idx >= N * K) {   // W^T [K, N] read in place
     idx -= N * K;
-    out += (size_t)3 * N * K;
+    out += (size_t)PIECES * N * K;
     transposed = 1;
     const int t = N;
     N = K;
@@ -436,8 +739,8 @@ __global__ __launch_bounds__(256) void tile_weights_f32(const float* __restrict_
   }
   if (idx >= N * K) return;
   int n, k;
-  unsigned short* o = tiled_slot(out, idx, K, n, k);
-  store_split_rne(o, transposed ? w[(size_t)k * ldw + n] : w[(size_t)n * ldw + k]);
+  unsigned short* o = tiled_slot<PIECES>(out, idx, K, n, k);
+  store_split_rne<PIECES>(o, transposed ? w[(size_t)k * ldw + n] : w[(size_t)n * ldw + k]);
 }
 
 // Several weights in ONE launch (a training step re-tiles every encoder weight after each optimizer step: 5 launches + 2
@@ -453,6 +756,7 @@ struct TileProblem {
 struct TileProblems {
   TileProblem p[kMaxTileProblems];
 };
+template <int PIECES>
 __global__ __launch_bounds__(256) void tile_weights_multi_f32(TileProblems P, int nprob) {
   int pi = 0;
   while (pi + 1 < nprob && (int)blockIdx.x >= P.p[pi + 1].first_block) ++pi;
@@ -463,24 +767,26 @@ __global__ __launch_bounds__(256) void tile_weights_multi_f32(TileProblems P, in
   const bool transposed = idx >= N * K;   // second half: the tiling of W^T [K, N] behind the first one
   if (transposed) {
     idx -= N * K;
-    out += (size_t)3 * N * K;
+    out += (size_t)PIECES * N * K;
     const int t = N;
     N = K;
     K = t;
   }
   if (idx >= N * K) return;
   int n, k;
-  unsigned short* o = tiled_slot(out, idx, K, n, k);
+  unsigned short* o = tiled_slot<PIECES>(out, idx, K, n, k);
   const int r = transposed ? k : n, c = transposed ? n : k;   // element (r, c) of the untransposed weight
-  store_split_rne(o, r < T.split ? T.w[(size_t)r * T.ldw + c] : T.w2[(size_t)(r - T.split) * T.ldw2 + c]);
+  store_split_rne<PIECES>(o, r < T.split ? T.w[(size_t)r * T.ldw + c] : T.w2[(size_t)(r - T.split) * T.ldw2 + c]);
 }
 
 }  // namespace
 
-extern "C" int egtr_gemm_split_tile_weights_multi_f32(egtr_stream_t stream, int num_weights, const float* const* w,
-                                                      const int* ldw, const float* const* w2, const int* ldw2,
-                                                      const int* split_rows, const int* N, const int* K,
-                                                      uint16_t* const* w_tiled_pair) {
+// The entries below exist twice: egtr_linear_split_bf16_* / egtr_gemm_split_* (three pieces, six terms) and egtr_linear_bf16r_* /
+// egtr_gemm_bf16r_* (one piece rounded to nearest, one term).  One implementation each, `pieces` = 3 or 1; the validation and
+// the status codes are the same.
+static int tile_multi_impl(int pieces, egtr_stream_t stream, int num_weights, const float* const* w, const int* ldw,
+                    const float* const* w2, const int* ldw2, const int* split_rows, const int* N, const int* K,
+                    uint16_t* const* w_tiled_pair) {
   if (!w || !ldw || !N || !K || !w_tiled_pair || num_weights <= 0 || num_weights > kMaxTileProblems) return EGTR_E_ARG;
   TileProblems P = {};
   long long blocks = 0;
@@ -496,8 +802,12 @@ extern "C" int egtr_gemm_split_tile_weights_multi_f32(egtr_stream_t stream, int 
     blocks += 2 * ((long long)N[i] * K[i] / 256);
   }
   if (blocks >= (1ll << 31)) return EGTR_E_UNSUPPORTED;
-  hipLaunchKernelGGL(tile_weights_multi_f32, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), P,
-                     num_weights);
+  if (pieces == 1)
+    hipLaunchKernelGGL(tile_weights_multi_f32<1>, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), P,
+                       num_weights);
+  else
+    hipLaunchKernelGGL(tile_weights_multi_f32<3>, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), P,
+                       num_weights);
   return egtr_check_launch();
 }
 
@@ -511,13 +821,11 @@ extern "C" int egtr_linear_split_bf16_f32(egtr_stream_t stream, const float* x, 
   return launch_grouped(static_cast<hipStream_t>(stream), P, 1, M, K);
 }
 
-extern "C" int egtr_linear_split_bf16_ex_f32(egtr_stream_t stream, int num_problems, const float* const* x, const int* ldx,
-                                             const uint16_t* const* w_tiled, const float* const* bias, float* const* y,
-                                             const int* ldy, const int* N, const int* relu, int M, int K,
-                                             const float* const* pos, const int* pos_rows,
-                                             const unsigned char* const* row_keep, const float* const* relu_ref,
-                                             const int* ldref, const float* const* add1, const float* const* add2,
-                                             const int* ldadd, float* const* colpart) {
+static int linear_ex_impl(int pieces, egtr_stream_t stream, int num_problems, const float* const* x, const int* ldx,
+                   const uint16_t* const* w_tiled, const float* const* bias, float* const* y, const int* ldy, const int* N,
+                   const int* relu, int M, int K, const float* const* pos, const int* pos_rows,
+                   const unsigned char* const* row_keep, const float* const* relu_ref, const int* ldref,
+                   const float* const* add1, const float* const* add2, const int* ldadd, float* const* colpart) {
   if (!x || !ldx || !w_tiled || !bias || !y || !ldy || !N || !relu) return EGTR_E_ARG;
   if (num_problems <= 0 || num_problems > kMaxProblems || M <= 0 || K <= 0) return EGTR_E_ARG;
   if ((pos != nullptr && pos_rows == nullptr) || (relu_ref != nullptr && ldref == nullptr) ||
@@ -543,7 +851,7 @@ extern "C" int egtr_linear_split_bf16_ex_f32(egtr_stream_t stream, int num_probl
                          row_keep != nullptr ? row_keep[i] : nullptr, rr, rr ? ldref[i] : 0, a1, a2,
                          (a1 || a2) ? ldadd[i] : 0, cp};
   }
-  return launch_grouped(static_cast<hipStream_t>(stream), P, num_problems, M, K);
+  return launch_grouped(static_cast<hipStream_t>(stream), P, num_problems, M, K, pieces);
 }
 
 extern "C" int egtr_linear_split_bf16_grouped_pos_f32(egtr_stream_t stream, int num_problems, const float* const* x,
@@ -551,45 +859,57 @@ extern "C" int egtr_linear_split_bf16_grouped_pos_f32(egtr_stream_t stream, int 
                                                       const float* const* bias, float* const* y, const int* ldy,
                                                       const int* N, const int* relu, int M, int K,
                                                       const float* const* pos, const int* pos_rows) {
-  return egtr_linear_split_bf16_ex_f32(stream, num_problems, x, ldx, w_tiled, bias, y, ldy, N, relu, M, K, pos, pos_rows,
-                                       nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+  return linear_ex_impl(3, stream, num_problems, x, ldx, w_tiled, bias, y, ldy, N, relu, M, K, pos, pos_rows, nullptr, nullptr,
+                        nullptr, nullptr, nullptr, nullptr, nullptr);
 }
 
-extern "C" int egtr_gemm_split_tile_weights_f32(egtr_stream_t stream, const float* w, int ldw, int transposed, int N, int K,
-                                                uint16_t* w_tiled) {
+static int tile_impl(int pieces, egtr_stream_t stream, const float* w, int ldw, int transposed, int N, int K, uint16_t* w_tiled) {
   if (!w || !w_tiled || N <= 0 || K <= 0 || ldw < (transposed ? N : K)) return EGTR_E_ARG;
   if (N % kBN != 0 || K % kBK != 0 || (long long)N * K > (1LL << 30)) return EGTR_E_UNSUPPORTED;
-  hipLaunchKernelGGL(tile_weights_f32, dim3(N * K / 256), dim3(256), 0, static_cast<hipStream_t>(stream), w, ldw,
-                     transposed, N, K, reinterpret_cast<unsigned short*>(w_tiled), 0);
+  if (pieces == 1)
+    hipLaunchKernelGGL(tile_weights_f32<1>, dim3(N * K / 256), dim3(256), 0, static_cast<hipStream_t>(stream), w, ldw,
+                       transposed, N, K, reinterpret_cast<unsigned short*>(w_tiled), 0);
+  else
+    hipLaunchKernelGGL(tile_weights_f32<3>, dim3(N * K / 256), dim3(256), 0, static_cast<hipStream_t>(stream), w, ldw,
+                       transposed, N, K, reinterpret_cast<unsigned short*>(w_tiled), 0);
   return egtr_check_launch();
 }
 
-extern "C" int egtr_gemm_split_tile_weights_pair_f32(egtr_stream_t stream, const float* w, int ldw, int N, int K,
-                                                     uint16_t* w_tiled_pair) {
+static int tile_pair_impl(int pieces, egtr_stream_t stream, const float* w, int ldw, int N, int K, uint16_t* w_tiled_pair) {
   if (!w || !w_tiled_pair || N <= 0 || K <= 0 || ldw < K) return EGTR_E_ARG;
   if (N % kBN != 0 || K % kBN != 0 || (long long)N * K > (1LL << 29)) return EGTR_E_UNSUPPORTED;
-  hipLaunchKernelGGL(tile_weights_f32, dim3(2 * (N * K / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), w, ldw, 0,
-                     N, K, reinterpret_cast<unsigned short*>(w_tiled_pair), 1);
+  if (pieces == 1)
+    hipLaunchKernelGGL(tile_weights_f32<1>, dim3(2 * (N * K / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), w, ldw, 0,
+                       N, K, reinterpret_cast<unsigned short*>(w_tiled_pair), 1);
+  else
+    hipLaunchKernelGGL(tile_weights_f32<3>, dim3(2 * (N * K / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), w, ldw, 0,
+                       N, K, reinterpret_cast<unsigned short*>(w_tiled_pair), 1);
   return egtr_check_launch();
 }
 
-extern "C" long long egtr_linear_split_bf16_wgrad_workspace_floats(int M, int N, int K) {
+static long long wgrad_workspace_impl(int pieces, int M, int N, int K) {
   if (M <= 0 || N <= 0 || K <= 0 || N % 128 || K % 128) return 0;
-  return (long long)wgrad_plan(M, N, K).chunks * N * K;
+  return (long long)wgrad_plan(M, N, K, pieces == 1 ? kR1StageMExt : kBK).chunks * N * K;   // (one term: the larger of its two plans)
 }
 
-extern "C" int egtr_linear_split_bf16_wgrad_ex_f32(egtr_stream_t stream, const float* g, int ldg, const float* x, int ldx,
-                                                   float* grad_weight, float* workspace, int M, int N, int K,
-                                                   const float* x_pos, int pos_rows, const unsigned char* row_keep) {
+static int wgrad_ex_impl(int pieces, egtr_stream_t stream, const float* g, int ldg, const float* x, int ldx, float* grad_weight,
+                  float* workspace, int M, int N, int K, const float* x_pos, int pos_rows, const unsigned char* row_keep) {
   if (!g || !x || !grad_weight || !workspace || M <= 0 || N <= 0 || K <= 0 || ldg < N || ldx < K) return EGTR_E_ARG;
   if (x_pos != nullptr && pos_rows <= 0) return EGTR_E_ARG;
   if (N % 128 || K % 128 || (reinterpret_cast<uintptr_t>(grad_weight) & 15) || (reinterpret_cast<uintptr_t>(workspace) & 15))
     return EGTR_E_UNSUPPORTED;
-  const WgradPlan pl = wgrad_plan(M, N, K);
+  const bool ext = x_pos != nullptr || row_keep != nullptr;
+  const WgradPlan pl = wgrad_plan(M, N, K, pieces != 1 ? kBK : ext ? kR1StageMExt : kR1StageM);
   const long long wgs = (long long)pl.chunks * (N / 128) * (K / 128);
   if (wgs >= (1ll << 31)) return EGTR_E_UNSUPPORTED;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (x_pos != nullptr || row_keep != nullptr)
+  if (pieces == 1 && ext)
+    hipLaunchKernelGGL((wgrad_bf16r_f32<true, kR1StageMExt>), dim3((unsigned)wgs), dim3(512), 0, st, g, ldg, x, ldx, workspace, M, N,
+                       K, pl.rows_per_chunk, x_pos, pos_rows, row_keep);
+  else if (pieces == 1)
+    hipLaunchKernelGGL((wgrad_bf16r_f32<false, kR1StageM>), dim3((unsigned)wgs), dim3(512), 0, st, g, ldg, x, ldx, workspace, M, N,
+                       K, pl.rows_per_chunk, x_pos, pos_rows, row_keep);
+  else if (ext)
     hipLaunchKernelGGL(wgrad_split_bf16_f32<true>, dim3((unsigned)wgs), dim3(512), 0, st, g, ldg, x, ldx, workspace, M, N, K,
                        pl.rows_per_chunk, x_pos, pos_rows, row_keep);
   else
@@ -603,7 +923,73 @@ extern "C" int egtr_linear_split_bf16_wgrad_ex_f32(egtr_stream_t stream, const f
   return egtr_check_launch();
 }
 
+extern "C" int egtr_gemm_split_tile_weights_multi_f32(egtr_stream_t stream, int num_weights, const float* const* w,
+                                                      const int* ldw, const float* const* w2, const int* ldw2,
+                                                      const int* split_rows, const int* N, const int* K,
+                                                      uint16_t* const* w_tiled_pair) {
+  return tile_multi_impl(3, stream, num_weights, w, ldw, w2, ldw2, split_rows, N, K, w_tiled_pair);
+}
+extern "C" int egtr_gemm_bf16r_tile_weights_multi_f32(egtr_stream_t stream, int num_weights, const float* const* w,
+                                                      const int* ldw, const float* const* w2, const int* ldw2,
+                                                      const int* split_rows, const int* N, const int* K,
+                                                      uint16_t* const* w_tiled_pair) {
+  return tile_multi_impl(1, stream, num_weights, w, ldw, w2, ldw2, split_rows, N, K, w_tiled_pair);
+}
+
+extern "C" int egtr_linear_split_bf16_ex_f32(egtr_stream_t stream, int num_problems, const float* const* x, const int* ldx,
+                                             const uint16_t* const* w_tiled, const float* const* bias, float* const* y,
+                                             const int* ldy, const int* N, const int* relu, int M, int K,
+                                             const float* const* pos, const int* pos_rows,
+                                             const unsigned char* const* row_keep, const float* const* relu_ref,
+                                             const int* ldref, const float* const* add1, const float* const* add2,
+                                             const int* ldadd, float* const* colpart) {
+  return linear_ex_impl(3, stream, num_problems, x, ldx, w_tiled, bias, y, ldy, N, relu, M, K, pos, pos_rows, row_keep, relu_ref,
+                        ldref, add1, add2, ldadd, colpart);
+}
+extern "C" int egtr_linear_bf16r_ex_f32(egtr_stream_t stream, int num_problems, const float* const* x, const int* ldx,
+                                        const uint16_t* const* w_tiled, const float* const* bias, float* const* y,
+                                        const int* ldy, const int* N, const int* relu, int M, int K, const float* const* pos,
+                                        const int* pos_rows, const unsigned char* const* row_keep,
+                                        const float* const* relu_ref, const int* ldref, const float* const* add1,
+                                        const float* const* add2, const int* ldadd, float* const* colpart) {
+  return linear_ex_impl(1, stream, num_problems, x, ldx, w_tiled, bias, y, ldy, N, relu, M, K, pos, pos_rows, row_keep, relu_ref,
+                        ldref, add1, add2, ldadd, colpart);
+}
+
+extern "C" int egtr_gemm_split_tile_weights_f32(egtr_stream_t stream, const float* w, int ldw, int transposed, int N, int K,
+                                                uint16_t* w_tiled) {
+  return tile_impl(3, stream, w, ldw, transposed, N, K, w_tiled);
+}
+extern "C" int egtr_gemm_bf16r_tile_weights_f32(egtr_stream_t stream, const float* w, int ldw, int transposed, int N, int K,
+                                                uint16_t* w_tiled) {
+  return tile_impl(1, stream, w, ldw, transposed, N, K, w_tiled);
+}
+extern "C" int egtr_gemm_split_tile_weights_pair_f32(egtr_stream_t stream, const float* w, int ldw, int N, int K,
+                                                     uint16_t* w_tiled_pair) {
+  return tile_pair_impl(3, stream, w, ldw, N, K, w_tiled_pair);
+}
+extern "C" int egtr_gemm_bf16r_tile_weights_pair_f32(egtr_stream_t stream, const float* w, int ldw, int N, int K,
+                                                     uint16_t* w_tiled_pair) {
+  return tile_pair_impl(1, stream, w, ldw, N, K, w_tiled_pair);
+}
+
+extern "C" long long egtr_linear_split_bf16_wgrad_workspace_floats(int M, int N, int K) {
+  return wgrad_workspace_impl(3, M, N, K);
+}
+extern "C" long long egtr_linear_bf16r_wgrad_workspace_floats(int M, int N, int K) { return wgrad_workspace_impl(1, M, N, K); }
+
+extern "C" int egtr_linear_split_bf16_wgrad_ex_f32(egtr_stream_t stream, const float* g, int ldg, const float* x, int ldx,
+                                                   float* grad_weight, float* workspace, int M, int N, int K,
+                                                   const float* x_pos, int pos_rows, const unsigned char* row_keep) {
+  return wgrad_ex_impl(3, stream, g, ldg, x, ldx, grad_weight, workspace, M, N, K, x_pos, pos_rows, row_keep);
+}
+extern "C" int egtr_linear_bf16r_wgrad_ex_f32(egtr_stream_t stream, const float* g, int ldg, const float* x, int ldx,
+                                              float* grad_weight, float* workspace, int M, int N, int K, const float* x_pos,
+                                              int pos_rows, const unsigned char* row_keep) {
+  return wgrad_ex_impl(1, stream, g, ldg, x, ldx, grad_weight, workspace, M, N, K, x_pos, pos_rows, row_keep);
+}
+
 extern "C" int egtr_linear_split_bf16_wgrad_f32(egtr_stream_t stream, const float* g, int ldg, const float* x, int ldx,
                                                 float* grad_weight, float* workspace, int M, int N, int K) {
-  return egtr_linear_split_bf16_wgrad_ex_f32(stream, g, ldg, x, ldx, grad_weight, workspace, M, N, K, nullptr, 1, nullptr);
+  return wgrad_ex_impl(3, stream, g, ldg, x, ldx, grad_weight, workspace, M, N, K, nullptr, 1, nullptr);
 }

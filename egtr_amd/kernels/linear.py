@@ -111,13 +111,36 @@ def _host_array(ctype, vals):
     return (ctype * len(vals))(*vals)
 
 
-def linear_split_ex(problems, M, K):
+# ``terms``: which arithmetic a split-GEMM binding launches.  6 (the default everywhere): the six-term split-bf16 product,
+# fp32 to the last bit, on the three-piece weight stream [N/128][K/32][3][128][32].  1: one product per element, each operand
+# rounded once to bf16 (round to nearest even), fp32 accumulation, on the one-piece stream [N/128][K/32][128][32] -- the
+# egtr_*_bf16r_* entries; ``egtr_amd.ops`` passes it from ``ops.matmul_precision()`` in its training Functions and nowhere else.
+def _pieces(terms):
+    if terms not in (1, 6):
+        raise ValueError(f"terms must be 6 (split-bf16, fp32 accuracy) or 1 (operands rounded to bf16), got {terms!r}")
+    return 3 if terms == 6 else 1
+
+
+def _stream_shape(N, K, terms):
+    return (N // 128, K // 32, 3, 128, 32) if _pieces(terms) == 3 else (N // 128, K // 32, 128, 32)
+
+
+def _entry(terms, six, one):
+    return six if _pieces(terms) == 3 else one
+
+
+def linear_split_ex(problems, M, K, terms=6):
     """Up to 8 token-sized linears with the same M and K in one launch of the split-bf16 GEMM with the training step's epilogue
     options (egtr_linear_split_bf16_ex_f32).  ``problems``: dicts with x [M, >=K] (unit inner stride), wt (tiled weight), N,
     and optionally b, relu, out ([M, N] view with unit inner stride), pos ([pos_rows, K]), row_keep ([M] uint8), relu_ref
-    ([M, N]), add1 / add2 ([M, N], may alias out), colpart ([ceil(M / 32), N]).  Returns the outputs.  No autograd."""
+    ([M, N]), add1 / add2 ([M, N], may alias out), colpart ([ceil(M / 32), N]).  Returns the outputs.  No autograd.  ``terms=1``: the one-term
+    arithmetic (egtr_linear_bf16r_ex_f32) on one-piece weight streams."""
     import ctypes
     n = len(problems)
+    for it in problems:
+        if tuple(it["wt"].shape) != _stream_shape(int(it["N"]), K, terms):
+            raise RuntimeError(f"linear_split_ex: wt must be {_stream_shape(int(it['N']), K, terms)} for terms={terms}, got "
+                               f"{tuple(it['wt'].shape)}")
     P, I = ctypes.c_void_p, ctypes.c_int
     outs = []
     for it in problems:
@@ -142,7 +165,8 @@ def linear_split_ex(problems, M, K):
             raise RuntimeError("linear_split_ex: add1 and add2 must share their row stride")
     ldadd = _host_array(I, [((it.get("add1") if it.get("add1") is not None else it.get("add2")).stride(0)
                              if (it.get("add1") is not None or it.get("add2") is not None) else 0) for it in problems])
-    _lib.launch("egtr_linear_split_bf16_ex_f32", n, _host_array(P, [it["x"].data_ptr() for it in problems]),
+    _lib.launch(_entry(terms, "egtr_linear_split_bf16_ex_f32", "egtr_linear_bf16r_ex_f32"), n,
+                _host_array(P, [it["x"].data_ptr() for it in problems]),
                 _host_array(I, [it["x"].stride(0) for it in problems]),
                 _host_array(P, [it["wt"].data_ptr() for it in problems]),
                 _host_array(P, [_lib.ptr(it.get("b")) for it in problems]),
@@ -154,14 +178,17 @@ def linear_split_ex(problems, M, K):
     return outs
 
 
-def _wgrad_ex(g, x, x_pos=None, row_keep=None):
-    """g [M, N]^T . (x [+ x_pos rows]) [M, K] -> [N, K] with optional row mask on g (egtr_linear_split_bf16_wgrad_ex_f32)."""
+def _wgrad_ex(g, x, x_pos=None, row_keep=None, terms=6):
+    """g [M, N]^T . (x [+ x_pos rows]) [M, K] -> [N, K] with optional row mask on g (egtr_linear_split_bf16_wgrad_ex_f32;
+    ``terms=1``: egtr_linear_bf16r_wgrad_ex_f32)."""
     lib = _lib.lib()
     M, N = g.shape
     K = x.shape[1]
-    ws = torch.empty(int(lib.egtr_linear_split_bf16_wgrad_workspace_floats(M, N, K)), dtype=torch.float32, device=g.device)
+    floats = getattr(lib, _entry(terms, "egtr_linear_split_bf16_wgrad_workspace_floats",
+                                 "egtr_linear_bf16r_wgrad_workspace_floats"))(M, N, K)
+    ws = torch.empty(int(floats), dtype=torch.float32, device=g.device)
     gw = torch.empty(N, K, dtype=torch.float32, device=g.device)
-    _lib.launch("egtr_linear_split_bf16_wgrad_ex_f32", g.data_ptr(), g.stride(0), x.data_ptr(), x.stride(0), gw.data_ptr(),
+    _lib.launch(_entry(terms, "egtr_linear_split_bf16_wgrad_ex_f32", "egtr_linear_bf16r_wgrad_ex_f32"), g.data_ptr(), g.stride(0), x.data_ptr(), x.stride(0), gw.data_ptr(),
                 ws.data_ptr(), M, N, K, _lib.ptr(x_pos), x_pos.shape[0] if x_pos is not None else 1, _lib.ptr(row_keep))
     return gw
 
@@ -291,40 +318,46 @@ def linear_grouped(items):
     return outs
 
 
-def gemm_split_weights(weight):
-    """W [N, K] fp32 -> the operand stream of gemm_split_bf16_f32: [N/128][K/32][3 pieces][128][32] bf16."""
+def gemm_split_weights(weight, terms=6):
+    """W [N, K] fp32 -> the operand stream of gemm_split_bf16_f32: [N/128][K/32][3 pieces][128][32] bf16.  ``terms=1``: the
+    one-piece stream of the one-term kernels, [N/128][K/32][128][32]: every element rounded once to bf16 (nearest even)."""
     N, K = weight.shape
+    if _pieces(terms) == 1:
+        return weight.detach().float().to(torch.bfloat16).view(N // 128, 128, K // 32, 32).permute(0, 2, 1, 3).contiguous()
     p = _split3_bf16(weight).view(3, N // 128, 128, K // 32, 32)
     return p.permute(1, 3, 0, 2, 4).contiguous()
 
 
-def gemm_split_tile(weight, transposed=False):
-    """``gemm_split_weights(weight)`` (``transposed``: of ``weight.t()``) in one launch (egtr_gemm_split_tile_weights_f32):
-    the training step re-tiles each weight after every optimizer step, for the forward (W) and the data gradient (W^T)."""
+def gemm_split_tile(weight, transposed=False, terms=6):
+    """``gemm_split_weights(weight, terms)`` (``transposed``: of ``weight.t()``) in one launch (egtr_gemm_split_tile_weights_f32,
+    egtr_gemm_bf16r_tile_weights_f32): the training step re-tiles each weight after every optimizer step, for the forward (W)
+    and the data gradient (W^T)."""
     w = weight.detach()
     if not w.is_cuda or w.dtype != torch.float32 or w.dim() != 2 or w.stride(1) != 1:
         raise RuntimeError("gemm_split_tile: weight must be a 2-d float32 CUDA/HIP tensor with unit inner stride")
     N, K = (w.shape[1], w.shape[0]) if transposed else (w.shape[0], w.shape[1])
-    out = torch.empty(N // 128, K // 32, 3, 128, 32, dtype=torch.bfloat16, device=w.device)
-    _lib.launch("egtr_gemm_split_tile_weights_f32", w.data_ptr(), w.stride(0), 1 if transposed else 0, N, K, out.data_ptr())
+    out = torch.empty(_stream_shape(N, K, terms), dtype=torch.bfloat16, device=w.device)
+    _lib.launch(_entry(terms, "egtr_gemm_split_tile_weights_f32", "egtr_gemm_bf16r_tile_weights_f32"), w.data_ptr(), w.stride(0),
+                1 if transposed else 0, N, K, out.data_ptr())
     return out
 
 
-def gemm_split_tile_pair(weight):
-    """(tiling of W, tiling of W^T) in one launch (egtr_gemm_split_tile_weights_pair_f32); N, K % 128 == 0."""
+def gemm_split_tile_pair(weight, terms=6):
+    """(tiling of W, tiling of W^T) in one launch (egtr_gemm_split_tile_weights_pair_f32 / egtr_gemm_bf16r_..); N, K % 128 == 0."""
     w = weight.detach()
     if not w.is_cuda or w.dtype != torch.float32 or w.dim() != 2 or w.stride(1) != 1:
         raise RuntimeError("gemm_split_tile_pair: weight must be a 2-d float32 CUDA/HIP tensor with unit inner stride")
     N, K = w.shape
-    out = torch.empty(2, 3 * N * K, dtype=torch.bfloat16, device=w.device)
-    _lib.launch("egtr_gemm_split_tile_weights_pair_f32", w.data_ptr(), w.stride(0), N, K, out.data_ptr())
-    return out[0].view(N // 128, K // 32, 3, 128, 32), out[1].view(K // 128, N // 32, 3, 128, 32)
+    out = torch.empty(2, _pieces(terms) * N * K, dtype=torch.bfloat16, device=w.device)
+    _lib.launch(_entry(terms, "egtr_gemm_split_tile_weights_pair_f32", "egtr_gemm_bf16r_tile_weights_pair_f32"), w.data_ptr(),
+                w.stride(0), N, K, out.data_ptr())
+    return out[0].view(_stream_shape(N, K, terms)), out[1].view(_stream_shape(K, N, terms))
 
 
-def gemm_split_tile_pairs(weights):
+def gemm_split_tile_pairs(weights, terms=6):
     """[(tiling of W, tiling of W^T)] for up to 8 weights in ONE launch (egtr_gemm_split_tile_weights_multi_f32).  An entry
     is a [N, K] tensor or a pair (w_a, w_b) of tensors with the same K: the row-wise concatenation [w_a; w_b] tiled as one
-    weight without materialising it.  N, K multiples of 128."""
+    weight without materialising it.  N, K multiples of 128.  ``terms=1``: egtr_gemm_bf16r_tile_weights_multi_f32."""
     import ctypes
     n = len(weights)
     P, I = ctypes.c_void_p, ctypes.c_int
@@ -339,24 +372,25 @@ def gemm_split_tile_pairs(weights):
         N, K = a.shape[0] + (b.shape[0] if b is not None else 0), a.shape[1]
         if b is not None and b.shape[1] != K:
             raise RuntimeError("gemm_split_tile_pairs: concatenated weights must share K")
-        out = torch.empty(2, 3 * N * K, dtype=torch.bfloat16, device=a.device)
+        out = torch.empty(2, _pieces(terms) * N * K, dtype=torch.bfloat16, device=a.device)
         w1.append(a.data_ptr()); ld1.append(a.stride(0)); split.append(a.shape[0])
         w2.append(_lib.ptr(b)); ld2.append(b.stride(0) if b is not None else 0)
         Ns.append(N); Ks.append(K); outs.append(out)
-    _lib.launch("egtr_gemm_split_tile_weights_multi_f32", n, (P * n)(*w1), (I * n)(*ld1), (P * n)(*w2), (I * n)(*ld2),
+    _lib.launch(_entry(terms, "egtr_gemm_split_tile_weights_multi_f32", "egtr_gemm_bf16r_tile_weights_multi_f32"), n, (P * n)(*w1), (I * n)(*ld1), (P * n)(*w2), (I * n)(*ld2),
                 (I * n)(*split), (I * n)(*Ns), (I * n)(*Ks), (P * n)(*[o.data_ptr() for o in outs]))
-    return [(o[0].view(N // 128, K // 32, 3, 128, 32), o[1].view(K // 128, N // 32, 3, 128, 32))
-            for o, N, K in zip(outs, Ns, Ks)]
+    return [(o[0].view(_stream_shape(N, K, terms)), o[1].view(_stream_shape(K, N, terms))) for o, N, K in zip(outs, Ns, Ks)]
 
 
-def linear_split_bf16_wgrad(g, x):
+def linear_split_bf16_wgrad(g, x, terms=6):
     """g [M, N]^T . x [M, K] -> [N, K] (the weight gradient of a token-sized linear layer) through
-    egtr_linear_split_bf16_wgrad_f32; unit inner strides, N, K % 128 == 0."""
+    egtr_linear_split_bf16_wgrad_f32 (``terms=1``: egtr_linear_bf16r_wgrad_ex_f32); unit inner strides, N, K % 128 == 0."""
     lib = _lib.lib()
     M, N = g.shape
     K = x.shape[1]
     if x.shape[0] != M or g.stride(1) != 1 or x.stride(1) != 1:
         raise RuntimeError("linear_split_bf16_wgrad: g [M, N] and x [M, K] with unit inner strides expected")
+    if _pieces(terms) == 1:
+        return _wgrad_ex(g, x, terms=1)
     ws = torch.empty(int(lib.egtr_linear_split_bf16_wgrad_workspace_floats(M, N, K)), dtype=torch.float32, device=g.device)
     gw = torch.empty(N, K, dtype=torch.float32, device=g.device)
     _lib.launch("egtr_linear_split_bf16_wgrad_f32", g.data_ptr(), g.stride(0), x.data_ptr(), x.stride(0), gw.data_ptr(),
@@ -364,15 +398,16 @@ def linear_split_bf16_wgrad(g, x):
     return gw
 
 
-def linear_split_bf16(x, w_tiled, bias, N, relu=False, out=None):
+def linear_split_bf16(x, w_tiled, bias, N, relu=False, out=None, terms=6):
     """act(x W^T + b) through egtr_linear_split_bf16_f32 (no autograd).  x [..., K] fp32 with unit inner stride and a
     uniform row stride (a column block of a wider buffer is fine); w_tiled from ``gemm_split_weights``; ``out``: optional
-    contiguous [rows, N] fp32 destination."""
+    contiguous [rows, N] fp32 destination.  ``terms=1``: the one-term arithmetic on the one-piece stream
+    (egtr_linear_bf16r_ex_f32 with one problem)."""
     K = x.shape[-1]
     x2 = _lib.row_view(x, K)
     _chk(w_tiled, "w_tiled", torch.bfloat16)
-    if tuple(w_tiled.shape) != (N // 128, K // 32, 3, 128, 32):
-        raise RuntimeError(f"w_tiled must be [{N // 128}, {K // 32}, 3, 128, 32], got {tuple(w_tiled.shape)}")
+    if tuple(w_tiled.shape) != _stream_shape(N, K, terms):
+        raise RuntimeError(f"w_tiled must be {list(_stream_shape(N, K, terms))} for terms={terms}, got {tuple(w_tiled.shape)}")
     b = _chk(bias.detach().contiguous(), "bias", torch.float32) if bias is not None else None
     if out is not None:
         y = _chk(out, "out", torch.float32)
@@ -380,8 +415,11 @@ def linear_split_bf16(x, w_tiled, bias, N, relu=False, out=None):
             raise RuntimeError(f"out must be [{x2.shape[0]}, {N}], got {tuple(y.shape)}")
     else:
         y = torch.empty(x2.shape[0], N, dtype=torch.float32, device=x.device)
-    _lib.launch("egtr_linear_split_bf16_f32", x2.data_ptr(), x2.stride(0), w_tiled.data_ptr(), _lib.ptr(b), y.data_ptr(), N,
-                x2.shape[0], K, N, 1 if relu else 0)
+    if _pieces(terms) == 1:
+        linear_split_ex([dict(x=x2, wt=w_tiled, N=N, b=b, relu=relu, out=y)], x2.shape[0], K, terms=1)
+    else:
+        _lib.launch("egtr_linear_split_bf16_f32", x2.data_ptr(), x2.stride(0), w_tiled.data_ptr(), _lib.ptr(b), y.data_ptr(), N,
+                    x2.shape[0], K, N, 1 if relu else 0)
     return y if out is not None else y.view(*x.shape[:-1], N)
 
 

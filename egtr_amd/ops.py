@@ -362,11 +362,12 @@ class TokenLinearFunction(Function):
         N, K = weight.shape
         ctx.split = GEMM_SPLIT_BF16 and x2.shape[0] >= GEMM_SPLIT_MIN_ROWS and weight.stride(1) == 1
         ctx.wt_t = None
+        ctx.terms = terms = _gemm_terms()   # read once: the backward multiplies the way the forward did
         if ctx.split and N % 128 == 0 and K % 128 == 0 and ctx.needs_input_grad[0]:
-            wt, ctx.wt_t = gemm_split_tile_pair(weight)   # W^T for the data gradient, same launch
-            y = linear_split_bf16(x2, wt, bias, N, relu=relu)
+            wt, ctx.wt_t = gemm_split_tile_pair(weight, terms=terms)   # W^T for the data gradient, same launch
+            y = linear_split_bf16(x2, wt, bias, N, relu=relu, terms=terms)
         elif ctx.split and N % 128 == 0 and K % 32 == 0:
-            y = linear_split_bf16(x2, gemm_split_tile(weight), bias, N, relu=relu)
+            y = linear_split_bf16(x2, gemm_split_tile(weight, terms=terms), bias, N, relu=relu, terms=terms)
         elif relu and hasattr(torch, "_addmm_activation"):
             y = torch._addmm_activation(bias, x2, weight.t(), use_gelu=False)
         else:
@@ -393,8 +394,8 @@ class TokenLinearFunction(Function):
         if ctx.needs_input_grad[0]:
             K = weight.shape[1]
             if ctx.split and K % 128 == 0 and N % 32 == 0:   # g W = "linear" with W^T
-                wt_t = ctx.wt_t if ctx.wt_t is not None else gemm_split_tile(weight, transposed=True)
-                gx = linear_split_bf16(g, wt_t, None, K)
+                wt_t = ctx.wt_t if ctx.wt_t is not None else gemm_split_tile(weight, transposed=True, terms=ctx.terms)
+                gx = linear_split_bf16(g, wt_t, None, K, terms=ctx.terms)
             else:
                 gx = g.mm(weight)
             gx = gx.view(ctx.in_shape)
@@ -402,7 +403,7 @@ class TokenLinearFunction(Function):
         if ctx.needs_input_grad[1]:
             K = weight.shape[1]
             if ctx.split and GEMM_SPLIT_WGRAD and N % 128 == 0 and K % 128 == 0 and x2.stride(1) == 1:
-                gw = linear_split_bf16_wgrad(g, x2)
+                gw = linear_split_bf16_wgrad(g, x2, terms=ctx.terms)
             else:
                 # the product autograd forms for addmm (x^T g, viewed transposed): the same vendor kernel as the plain path
                 gw = x2.t().mm(g).t()
@@ -455,16 +456,17 @@ class EncoderLayerTrainFunction(Function):
             rk = keep_rows.reshape(-1).contiguous()
             rk = rk.view(torch.uint8) if rk.dtype == torch.bool else rk.to(torch.uint8)
         bb = torch.cat([so_b.detach(), aw_b.detach()], 0)
+        ctx.terms = terms = _gemm_terms()   # read once: the tiled weights saved for the backward are of this kind only
         # every weight of the layer (and its transpose, for the data gradients) into the GEMM's operand stream: one launch;
         # sampling_offsets | attention_weights as ONE [384, 256] weight without a materialised concatenation
         (wt_v, wtT_v), (wt_b, wtT_b), (wt_o, wtT_o), (wt_1, wtT_1), (wt_2, wtT_2) = gemm_split_tile_pairs(
-            [vp_w, (so_w, aw_w), op_w, fc1_w, fc2_w])
+            [vp_w, (so_w, aw_w), op_w, fc1_w, fc2_w], terms=terms)
         F1 = fc1_w.shape[0]
         nb = so_w.shape[0] + aw_w.shape[0]
         n_off = so_w.shape[0]
         # value projection (padded rows zeroed in the epilogue) + offsets / logits projection of x + pos: one launch
         value, both = linear_split_ex([dict(x=x2, wt=wt_v, N=D, b=vp_b.detach(), row_keep=rk),
-                                       dict(x=x2, wt=wt_b, N=nb, b=bb, pos=pos2)], M, D)
+                                       dict(x=x2, wt=wt_b, N=nb, b=bb, pos=pos2)], M, D, terms=terms)
         Mh, L, P_ = 8, shapes.shape[0], n_off // (8 * shapes.shape[0] * 2)
         refc = _chk(ref.detach().contiguous(), "reference_points", torch.float32)
         shp = _chk(shapes.contiguous(), "spatial_shapes", torch.int64)
@@ -475,7 +477,7 @@ class EncoderLayerTrainFunction(Function):
                     refc.data_ptr(), refc.shape[-1], shp.data_ptr(), loc.data_ptr(), attn.data_ptr(), M, Mh, L, P_)
         value4 = value.view(B, S, Mh, D // Mh)
         att = _msda().ms_deform_attn_forward(value4, shp, lsi, loc, attn, 64).view(M, D)
-        a = linear_split_ex([dict(x=att, wt=wt_o, N=D, b=op_b.detach())], M, D)[0]
+        a = linear_split_ex([dict(x=att, wt=wt_o, N=D, b=op_b.detach())], M, D, terms=terms)[0]
         p = float(p_drop)
         scale = 1.0 / (1.0 - p) if p > 0.0 else 1.0
         m1 = m2 = None
@@ -487,8 +489,8 @@ class EncoderLayerTrainFunction(Function):
         flag = torch.zeros(1, dtype=torch.int32, device=dev)
         eps1, eps2 = float(ln_eps[0]), float(ln_eps[1])
         y1 = dropout_add_layernorm(a, x2, m1, scale, ln1_w.detach(), ln1_b.detach(), eps1)
-        h = linear_split_ex([dict(x=y1, wt=wt_1, N=F1, b=fc1_b.detach(), relu=True)], M, D)[0]
-        f = linear_split_ex([dict(x=h, wt=wt_2, N=D, b=fc2_b.detach())], M, F1)[0]
+        h = linear_split_ex([dict(x=y1, wt=wt_1, N=F1, b=fc1_b.detach(), relu=True)], M, D, terms=terms)[0]
+        f = linear_split_ex([dict(x=h, wt=wt_2, N=D, b=fc2_b.detach())], M, F1, terms=terms)[0]
         y2 = dropout_add_layernorm(f, y1, m2, scale, ln2_w.detach(), ln2_b.detach(), eps2, flag=flag)
         cv = torch.finfo(torch.float32).max - 1000
         _lib.launch("egtr_clamp_if_flag_f32", y2.data_ptr(), None, y2.numel(), flag.data_ptr(), cv, 0)
@@ -507,19 +509,20 @@ class EncoderLayerTrainFunction(Function):
         B, S, D, F1, nb, n_off, Mh, L, P_, scale, cv, eps1, eps2 = ctx.dims
         M = B * S
         dev = x2.device
+        terms = ctx.terms
         g = _rows256(g_y2)
         # LayerNorm2 + dropout backward (+ the clamp's gradient mask when the forward raised its flag)
         gs2, gf, gbb2 = dropout_add_layernorm_backward(f, y1, m2, scale, ln2_w.detach(), eps2, g, flag, y2, cv)
-        d_w2 = linear_split_bf16_wgrad(gf, h)
+        d_w2 = linear_split_bf16_wgrad(gf, h, terms=terms)
         colp = torch.empty((M + 31) // 32, F1, dtype=torch.float32, device=dev)
-        g_h = linear_split_ex([dict(x=gf, wt=wtT_2, N=F1, relu_ref=h, colpart=colp)], M, D)[0]   # ReLU mask + bias partials
+        g_h = linear_split_ex([dict(x=gf, wt=wtT_2, N=F1, relu_ref=h, colpart=colp)], M, D, terms=terms)[0]   # ReLU mask + bias partials
         d_b1 = column_sum(colp)
-        d_w1 = linear_split_bf16_wgrad(g_h, y1)
-        linear_split_ex([dict(x=g_h, wt=wtT_1, N=D, add1=gs2, out=gs2)], M, F1)                  # gs2 <- d loss / d y1
+        d_w1 = linear_split_bf16_wgrad(g_h, y1, terms=terms)
+        linear_split_ex([dict(x=g_h, wt=wtT_1, N=D, add1=gs2, out=gs2)], M, F1, terms=terms)   # gs2 <- d loss / d y1
         del g_h
         gs1, ga, gbb1 = dropout_add_layernorm_backward(a, x2, m1, scale, ln1_w.detach(), eps1, gs2)
-        d_wo = linear_split_bf16_wgrad(ga, att)
-        g_att = linear_split_ex([dict(x=ga, wt=wtT_o, N=D)], M, D)[0]
+        d_wo = linear_split_bf16_wgrad(ga, att, terms=terms)
+        g_att = linear_split_ex([dict(x=ga, wt=wtT_o, N=D)], M, D, terms=terms)[0]
         g_value, g_loc, g_attn = _msda().ms_deform_attn_backward(value.view(B, S, Mh, D // Mh), shp, lsi, loc, attn,
                                                                  g_att.view(B, S, D), 64)
         g_both = torch.empty(M, nb, dtype=torch.float32, device=dev)
@@ -528,12 +531,12 @@ class EncoderLayerTrainFunction(Function):
                     off.stride(0), refc.data_ptr(), refc.shape[-1], shp.data_ptr(), g_both.data_ptr(), nb,
                     g_both.data_ptr() + 4 * n_off, nb, None, M, Mh, L, P_)
         d_bb = column_sum(g_both)
-        d_wb = _wgrad_ex(g_both, x2, x_pos=pos2)
-        g_qin = linear_split_ex([dict(x=g_both, wt=wtT_b, N=D)], M, nb)[0]                       # = d loss / d pos as well
+        d_wb = _wgrad_ex(g_both, x2, x_pos=pos2, terms=terms)
+        g_qin = linear_split_ex([dict(x=g_both, wt=wtT_b, N=D)], M, nb, terms=terms)[0]   # = d loss / d pos as well
         gv2 = g_value.view(M, D)
         d_bv = column_sum(gv2) if rk is None else weighted_column_sum(gv2, rk.to(torch.float32))
-        d_wv = _wgrad_ex(gv2, x2, row_keep=rk)
-        linear_split_ex([dict(x=gv2, wt=wtT_v, N=D, row_keep=rk, add1=gs1, add2=g_qin, out=gs1)], M, D)   # gs1 <- d loss / d x
+        d_wv = _wgrad_ex(gv2, x2, row_keep=rk, terms=terms)
+        linear_split_ex([dict(x=gv2, wt=wtT_v, N=D, row_keep=rk, add1=gs1, add2=g_qin, out=gs1)], M, D, terms=terms)   # gs1 <- d loss / d x
         g_pos = g_qin.view(B, S, D)
         if tuple(ctx.pos_shape) != (B, S, D):
             g_pos = g_pos.sum_to_size(ctx.pos_shape)
@@ -562,13 +565,14 @@ class DecoderValueProjTrainFunction(Function):
         if keep_rows is not None:
             rk = keep_rows.reshape(-1).contiguous()
             rk = rk.view(torch.uint8) if rk.dtype == torch.bool else rk.to(torch.uint8)
+        ctx.terms = terms = _gemm_terms()
         tiles = []
         for i0 in range(0, nl, 8):
-            tiles += gemm_split_tile_pairs(list(ws[i0:i0 + 8]))
+            tiles += gemm_split_tile_pairs(list(ws[i0:i0 + 8]), terms=terms)
         outs = []
         for i0 in range(0, nl, 8):
             outs += linear_split_ex([dict(x=x2, wt=tiles[i][0], N=D, b=bs[i].detach(), row_keep=rk)
-                                     for i in range(i0, min(nl, i0 + 8))], M, D)
+                                     for i in range(i0, min(nl, i0 + 8))], M, D, terms=terms)
         ctx.save_for_backward(x2, rk, *[t[1] for t in tiles])
         ctx.set_materialize_grads(False)   # an unused layer's values: None, not a zero tensor to multiply out
         ctx.nl = nl
@@ -580,7 +584,7 @@ class DecoderValueProjTrainFunction(Function):
     def backward(ctx, *gs):
         x2, rk = ctx.saved_tensors[:2]
         wtT = ctx.saved_tensors[2:]
-        nl = ctx.nl
+        nl, terms = ctx.nl, ctx.terms
         M, D = x2.shape
         g_enc = None
         d_w, d_b = [], []
@@ -592,11 +596,11 @@ class DecoderValueProjTrainFunction(Function):
                 continue
             g = _rows256(gs[i])
             d_b.append(column_sum(g) if rkf is None else weighted_column_sum(g, rkf))
-            d_w.append(_wgrad_ex(g, x2, row_keep=rk))
+            d_w.append(_wgrad_ex(g, x2, row_keep=rk, terms=terms))
             if g_enc is None:
-                g_enc = linear_split_ex([dict(x=g, wt=wtT[i], N=D, row_keep=rk)], M, D)[0]
+                g_enc = linear_split_ex([dict(x=g, wt=wtT[i], N=D, row_keep=rk)], M, D, terms=terms)[0]
             else:
-                linear_split_ex([dict(x=g, wt=wtT[i], N=D, row_keep=rk, add1=g_enc, out=g_enc)], M, D)
+                linear_split_ex([dict(x=g, wt=wtT[i], N=D, row_keep=rk, add1=g_enc, out=g_enc)], M, D, terms=terms)
         return (g_enc.view(ctx.in_shape) if g_enc is not None else None, None, *d_w, *d_b)
 
 
@@ -876,9 +880,13 @@ def decoder_layer_train(layer, x, pos, ref, value, spatial_shapes, level_start_i
 #   EGTR_DETERMINISTIC=1        ops.DETERMINISTIC           (opt-IN) training: fp32 atomics / first-come tie tickets  ->  the order-free
 #                                                           routes (fixed-point MSDA grad_value, indexed loss ties, gate means
 #                                                           reduced in a fixed order); see set_deterministic() below
+#   EGTR_MATMUL_PRECISION=bf16  ops.MATMUL_PRECISION        (opt-IN) training token GEMMs: six-term split-bf16, fp32 to the last bit  ->
+#                                                           ONE product per element, operands rounded once to bf16 (nearest even),
+#                                                           fp32 accumulation; see set_matmul_precision() below
 # Not route switches: EGTR_HIP_LIBRARY (another build of the library), EGTR_STRICT_FAST_PATH (below), EGTR_TRUST_CHECKPOINT_PICKLE.
 ENV_ROUTE_SWITCHES = ("EGTR_DECODER_CLUSTER", "EGTR_GEMM_SPLIT_BF16", "EGTR_REL_HEAD_SPLIT_BF16", "EGTR_FFN_FUSED",
-                      "EGTR_BACKBONE_NHWC", "EGTR_ENCODER_TRAIN_FUSED", "EGTR_TOKEN_LINEAR", "EGTR_DETERMINISTIC")
+                      "EGTR_BACKBONE_NHWC", "EGTR_ENCODER_TRAIN_FUSED", "EGTR_TOKEN_LINEAR", "EGTR_DETERMINISTIC",
+                      "EGTR_MATMUL_PRECISION")
 
 # ---- deterministic mode ------------------------------------------------------------------------------
 # Opt-in: the same inputs on the same device with the same build give the same bits from the library's own kernels and this
@@ -919,6 +927,65 @@ class deterministic:
     def __exit__(self, *exc):
         set_deterministic(self.prev)
         return False
+
+
+# ---- matmul precision of the training token GEMMs ----------------------------------------------------------
+# Opt-in, the counterpart of torch.set_float32_matmul_precision("medium") / Lightning's precision="bf16" for this package's own
+# kernels: under "bf16" the token-sized products of the autograd training routes -- TokenLinearFunction (forward, data gradient,
+# weight gradient), every product of EncoderLayerTrainFunction and DecoderValueProjTrainFunction -- round each operand ONCE to
+# bf16 (round to nearest even; `x + pos` is added in fp32 first) and issue one matrix instruction per k-step instead of six
+# (csrc/gemm_split.hip, the egtr_*_bf16r_* entries).  Accumulation, the tensors in memory, master weights, gradients and the
+# optimizer stay fp32; bf16 has fp32's exponent range, so there is no loss scaling.  Consulted AT CALL TIME in a Function's
+# forward and kept on its ctx for the backward (a route switch, not a fall-off: nothing is counted in FALLBACKS).
+# Not covered: every inference route (module_linear, ffn_fused, the grouped projections, the relation head, the backbone) keeps
+# its bits -- a user who wants bf16 inference has the bf16 model; the relation head's training kernels (rel_head_fwd_x6 and its
+# aten::mm backward), MSDA, LayerNorm, the losses and the matcher; shapes the split kernels do not serve still take the vendor
+# GEMM in fp32.  torch's own float32_matmul_precision is neither read nor set.
+_MATMUL_PRECISIONS = ("fp32", "bf16")
+
+
+def _checked_matmul_precision(p):
+    if p not in _MATMUL_PRECISIONS:
+        raise ValueError(f"matmul precision must be one of {_MATMUL_PRECISIONS}, got {p!r}")
+    return p
+
+
+MATMUL_PRECISION = _checked_matmul_precision(os.environ.get("EGTR_MATMUL_PRECISION", "fp32"))
+
+
+def set_matmul_precision(p):
+    """"fp32" (the six-term split-bf16 products) or "bf16" (operands rounded once) for the training token GEMMs; process-wide,
+    returns the previous setting."""
+    global MATMUL_PRECISION
+    prev = MATMUL_PRECISION
+    MATMUL_PRECISION = _checked_matmul_precision(p)
+    return prev
+
+
+def matmul_precision():
+    """The current setting: "fp32" or "bf16"."""
+    return MATMUL_PRECISION
+
+
+class matmul_precision_mode:
+    """``with ops.matmul_precision_mode("bf16"):`` -- the setting for a block; restores the previous one, on an exception too."""
+
+    def __init__(self, p):
+        self.p = _checked_matmul_precision(p)
+
+    def __enter__(self):
+        self.prev = set_matmul_precision(self.p)
+        return self
+
+    def __exit__(self, *exc):
+        set_matmul_precision(self.prev)
+        return False
+
+
+def _gemm_terms():
+    """Products per element of a training token GEMM under the current setting (the ``terms`` of the kernels.linear bindings)."""
+    return 1 if MATMUL_PRECISION == "bf16" else 6
+
 
 # ---- leaving a HIP fast path is never silent ------------------------------------------------------------------------------
 # Every route from a hand-written kernel to an ATen composition (unsupported shape, misaligned operand, a device that

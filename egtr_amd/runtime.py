@@ -324,7 +324,7 @@ class DataParallelTrainer:
     clip-grad-norm 0.1 and AdamW.  ``num_boxes`` stays per-rank (model/egtr.py:976-980)."""
 
     def __init__(self, model, optimizer=None, accumulate=2, clip=0.1, bucket_cap_mb=25, graph=False, force_ddp=False,
-                 grad_compression=None, deterministic=False):
+                 grad_compression=None, deterministic=False, matmul_precision=None):
         """graph=True (single process, GPU, fixed image size): the static-shape part of the step -- backbone, encoder,
         decoder, detection + relation heads, forward AND backward -- is captured once into two HIP graphs
         (torch.cuda.make_graphed_callables over ``model.forward_tensors``) and replayed; the Hungarian matcher and the
@@ -342,7 +342,15 @@ class DataParallelTrainer:
         from the library's own kernels -- and ``torch.backends.cudnn.deterministic`` is set, which REQUESTS deterministic MIOpen
         algorithms; MIOpen's compliance is requested, not promised, and vendor GEMMs / ATen operations without a deterministic
         form are outside the guarantee.  Works with ``graph=True``: the mode is part of the key of the captured
-        step, so a step captured under one setting is never replayed under the other."""
+        step, so a step captured under one setting is never replayed under the other.
+
+        ``matmul_precision``: None (follow ``ops.matmul_precision()``, i.e. EGTR_MATMUL_PRECISION or the last
+        ``ops.set_matmul_precision``), "fp32" or "bf16": every step runs inside ``ops.matmul_precision_mode(..)``.  "bf16": the
+        token-sized products of the encoder layers and of the decoder's value projections round each operand once to bf16
+        (fp32 accumulation; weights, gradients and the optimizer stay fp32; no loss scaling) -- DESIGN.md 4.12b.  Part of the
+        captured step's key like the deterministic mode, and it combines freely with it: the two touch different kernels."""
+        from . import ops
+        self.matmul_precision = None if matmul_precision is None else ops._checked_matmul_precision(matmul_precision)
         self.deterministic = bool(deterministic)
         if self.deterministic:
             torch.backends.cudnn.deterministic = True
@@ -375,7 +383,8 @@ class DataParallelTrainer:
 
     def _graphed_body(self, pixel_values, pixel_mask):
         from . import ops
-        key = (tuple(pixel_values.shape), pixel_values.dtype, tuple(pixel_mask.shape), pixel_mask.dtype, ops.is_deterministic())
+        key = (tuple(pixel_values.shape), pixel_values.dtype, tuple(pixel_mask.shape), pixel_mask.dtype, ops.is_deterministic(),
+               ops.matmul_precision())
         if self._graphed is None or key != self._graph_key:
             raw = self.raw
 
@@ -446,7 +455,8 @@ class DataParallelTrainer:
         ctx = contextlib.nullcontext() if (boundary or not wrapped) else self.model.no_sync()
         from . import ops
         mode = ops.deterministic(True) if self.deterministic else contextlib.nullcontext()
-        with ctx, mode:
+        prec = ops.matmul_precision_mode(self.matmul_precision) if self.matmul_precision is not None else contextlib.nullcontext()
+        with ctx, mode, prec:
             loss, loss_dict = self.common_step(batch)
             (loss / self.accumulate).backward()
         if boundary:

@@ -912,6 +912,32 @@ int egtr_linear_split_bf16_wgrad_ex_f32(egtr_stream_t stream, const float* g, in
                                         float* grad_weight, float* workspace, int M, int N, int K, const float* x_pos,
                                         int pos_rows, const unsigned char* row_keep);
 
+/* ---- the one-term ("bf16r") counterparts of the entries above: matmul precision "bf16" of the training routes ----------
+ * Same arguments, same validation and status codes, same epilogue options in the same order, same grouping and strides; the
+ * arithmetic is ONE product per element: each operand rounded once to bf16, round to nearest even (x after the on-load
+ * `+ pos` / `+ x_pos`: RNE(fl32(x + pos))), every bf16 x bf16 product exact in fp32, fp32 accumulation.  Tensors stay fp32.
+ * Inf and NaN survive the rounding (a non-finite element of x makes its output row -- weight gradient: its column --
+ * non-finite and nothing else); a finite value beyond the largest bf16 (about 3.39e38) rounds to Inf.
+ * w_tiled is the ONE-piece stream [N/128][K/32][128 rows][32] raw bfloat16 bits (ops.gemm_split_weights(w, terms=1)), written
+ * by the three tiling entries; the pair forms hold [tiling of W (N K) | tiling of W^T (N K)].  K % 32 == 0, N % 128 == 0 and
+ * the alignment rules of the six-term entries, else EGTR_E_UNSUPPORTED.  The weight gradient keeps the split-K chunks through
+ * `workspace` (egtr_linear_bf16r_wgrad_workspace_floats(M, N, K) floats) and the fixed summation order. */
+int egtr_linear_bf16r_ex_f32(egtr_stream_t stream, int num_problems, const float* const* x, const int* ldx,
+                             const uint16_t* const* w_tiled, const float* const* bias, float* const* y, const int* ldy,
+                             const int* N, const int* relu, int M, int K, const float* const* pos, const int* pos_rows,
+                             const unsigned char* const* row_keep, const float* const* relu_ref, const int* ldref,
+                             const float* const* add1, const float* const* add2, const int* ldadd, float* const* colpart);
+long long egtr_linear_bf16r_wgrad_workspace_floats(int M, int N, int K);
+int egtr_linear_bf16r_wgrad_ex_f32(egtr_stream_t stream, const float* g, int ldg, const float* x, int ldx, float* grad_weight,
+                                   float* workspace, int M, int N, int K, const float* x_pos, int pos_rows,
+                                   const unsigned char* row_keep);
+int egtr_gemm_bf16r_tile_weights_f32(egtr_stream_t stream, const float* w, int ldw, int transposed, int N, int K,
+                                     uint16_t* w_tiled);
+int egtr_gemm_bf16r_tile_weights_pair_f32(egtr_stream_t stream, const float* w, int ldw, int N, int K, uint16_t* w_tiled_pair);
+int egtr_gemm_bf16r_tile_weights_multi_f32(egtr_stream_t stream, int num_weights, const float* const* w, const int* ldw,
+                                           const float* const* w2, const int* ldw2, const int* split_rows, const int* N,
+                                           const int* K, uint16_t* const* w_tiled_pair);
+
 /* ---- the "XS" operand format of the row-panel kernels (csrc/xs_format.h, csrc/xs_split.hip) --------------------------
  * XS(X) of a logical fp32 matrix X[rows][K] (K % 16 == 0): the exact three-way bf16 split x = hi + mid + lo, stored as
  * 1 KiB fragments of 32 rows x 16 k of ONE piece; fragment (rb = row / 32, ks = k / 16, piece p) at byte
