@@ -16,7 +16,7 @@ LIB_PATH = os.environ.get("EGTR_HIP_LIBRARY") or os.path.join(_HERE, "libegtr_hi
 
 _P = ctypes.c_void_p
 _I = ctypes.c_int
-ABI_VERSION = 5   # include/egtr_hip.h: EGTR_ABI_VERSION of the header these signatures were written against
+ABI_VERSION = 6   # include/egtr_hip.h: EGTR_ABI_VERSION of the header these signatures were written against
 
 # name -> argtypes (restype is always int status unless listed in _RESTYPES)
 SIGNATURES = {
@@ -127,21 +127,13 @@ SIGNATURES = {
     "egtr_rel_head_forward_bf16p": [_P] * 16 + [_I] * 6 + [_P] * 3,
     "egtr_rel_head_pack_tables_bf16": [_P, _P, _I, _I, _I, _P],
     "egtr_linear_split_bf16_f32": [_P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I],
-    "egtr_linear_split_bf16_wgrad_f32": [_P, _P, _I, _P, _I, _P, _P, _I, _I, _I],
-    "egtr_linear_split_bf16_wgrad_workspace_floats": [_I, _I, _I],
-    "egtr_gemm_split_tile_weights_f32": [_P, _P, _I, _I, _I, _I, _P],
-    "egtr_gemm_split_tile_weights_pair_f32": [_P, _P, _I, _I, _I, _P],
-    "egtr_gemm_split_tile_weights_multi_f32": [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P],
-    "egtr_linear_split_bf16_grouped_pos_f32": [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P],
-    "egtr_linear_split_bf16_ex_f32": [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P],
-    "egtr_linear_split_bf16_wgrad_ex_f32": [_P, _P, _I, _P, _I, _P, _P, _I, _I, _I, _P, _I, _P],
-    # the one-term ("bf16r") counterparts: same argument lists as the six-term entries above
-    "egtr_linear_bf16r_ex_f32": [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P],
-    "egtr_linear_bf16r_wgrad_workspace_floats": [_I, _I, _I],
-    "egtr_linear_bf16r_wgrad_ex_f32": [_P, _P, _I, _P, _I, _P, _P, _I, _I, _I, _P, _I, _P],
-    "egtr_gemm_bf16r_tile_weights_f32": [_P, _P, _I, _I, _I, _I, _P],
-    "egtr_gemm_bf16r_tile_weights_pair_f32": [_P, _P, _I, _I, _I, _P],
-    "egtr_gemm_bf16r_tile_weights_multi_f32": [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P],
+    # the split GEMM: the trailing int is `terms` (6 = six exact cross terms, 1 = operands rounded once to bf16)
+    "egtr_linear_split_bf16_wgrad_workspace_floats": [_I, _I, _I, _I],
+    "egtr_gemm_split_tile_weights_f32": [_P, _P, _I, _I, _I, _I, _P, _I],
+    "egtr_gemm_split_tile_weights_pair_f32": [_P, _P, _I, _I, _I, _P, _I],
+    "egtr_gemm_split_tile_weights_multi_f32": [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I],
+    "egtr_linear_split_bf16_ex_f32": [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I],
+    "egtr_linear_split_bf16_wgrad_ex_f32": [_P, _P, _I, _P, _I, _P, _P, _I, _I, _I, _P, _I, _P, _I],
     "egtr_dropout_add_layernorm_f32": [_P, _P, _P, _P, ctypes.c_float, _P, _P, _P, _I, _I, ctypes.c_float, _P],
     "egtr_dropout_add_layernorm_backward_workspace_floats": [_I],
     "egtr_dropout_add_layernorm_backward_f32": [_P, _P, _P, _P, ctypes.c_float, _P, _P, _P, _P, ctypes.c_float, _P, _P, _P,
@@ -188,7 +180,6 @@ _RESTYPES = {"egtr_status_string": ctypes.c_char_p, "egtr_last_hip_error": ctype
              "egtr_column_sum_workspace_floats": ctypes.c_longlong,
              "egtr_add_layernorm_backward_workspace_floats": ctypes.c_longlong,
              "egtr_linear_split_bf16_wgrad_workspace_floats": ctypes.c_longlong,
-             "egtr_linear_bf16r_wgrad_workspace_floats": ctypes.c_longlong,
              "egtr_dropout_add_layernorm_backward_workspace_floats": ctypes.c_longlong,
              "egtr_xs_bytes": ctypes.c_longlong, "egtr_sgg_eval_width": ctypes.c_longlong,
              "egtr_oi_eval_width": ctypes.c_longlong, "egtr_matched_topk_workspace_bytes": ctypes.c_longlong, "egtr_oi_select_workspace_bytes": ctypes.c_longlong}

@@ -781,12 +781,17 @@ __global__ __launch_bounds__(256) void tile_weights_multi_f32(TileProblems P, in
 
 }  // namespace
 
-// The entries below exist twice: egtr_linear_split_bf16_* / egtr_gemm_split_* (three pieces, six terms) and egtr_linear_bf16r_* /
-// egtr_gemm_bf16r_* (one piece rounded to nearest, one term).  One implementation each, `pieces` = 3 or 1; the validation and
-// the status codes are the same.
-static int tile_multi_impl(int pieces, egtr_stream_t stream, int num_weights, const float* const* w, const int* ldw,
-                    const float* const* w2, const int* ldw2, const int* split_rows, const int* N, const int* K,
-                    uint16_t* const* w_tiled_pair) {
+// `terms`, the trailing argument of every entry below but the scalar forward: which arithmetic runs.  6: the six exact cross
+// terms on the three-piece weight stream; 1: one product per element, operands rounded once to bf16, on the one-piece stream.
+// Anything else is an argument error (0 pieces), answered before any HIP call.
+static int pieces_of(int terms) { return terms == 6 ? 3 : terms == 1 ? 1 : 0; }
+
+extern "C" int egtr_gemm_split_tile_weights_multi_f32(egtr_stream_t stream, int num_weights, const float* const* w,
+                                                      const int* ldw, const float* const* w2, const int* ldw2,
+                                                      const int* split_rows, const int* N, const int* K,
+                                                      uint16_t* const* w_tiled_pair, int terms) {
+  const int pieces = pieces_of(terms);
+  if (!pieces) return EGTR_E_ARG;
   if (!w || !ldw || !N || !K || !w_tiled_pair || num_weights <= 0 || num_weights > kMaxTileProblems) return EGTR_E_ARG;
   TileProblems P = {};
   long long blocks = 0;
@@ -811,6 +816,7 @@ static int tile_multi_impl(int pieces, egtr_stream_t stream, int num_weights, co
   return egtr_check_launch();
 }
 
+// The single-problem, scalar-argument form of inference (six terms): no host arrays to build on a host-bound forward.
 extern "C" int egtr_linear_split_bf16_f32(egtr_stream_t stream, const float* x, int ldx, const uint16_t* w_tiled,
                                           const float* bias, float* y, int ldy, int M, int K, int N, int relu) {
   if (!x || !w_tiled || !y) return EGTR_E_ARG;
@@ -821,11 +827,15 @@ extern "C" int egtr_linear_split_bf16_f32(egtr_stream_t stream, const float* x, 
   return launch_grouped(static_cast<hipStream_t>(stream), P, 1, M, K);
 }
 
-static int linear_ex_impl(int pieces, egtr_stream_t stream, int num_problems, const float* const* x, const int* ldx,
-                   const uint16_t* const* w_tiled, const float* const* bias, float* const* y, const int* ldy, const int* N,
-                   const int* relu, int M, int K, const float* const* pos, const int* pos_rows,
-                   const unsigned char* const* row_keep, const float* const* relu_ref, const int* ldref,
-                   const float* const* add1, const float* const* add2, const int* ldadd, float* const* colpart) {
+extern "C" int egtr_linear_split_bf16_ex_f32(egtr_stream_t stream, int num_problems, const float* const* x, const int* ldx,
+                                             const uint16_t* const* w_tiled, const float* const* bias, float* const* y,
+                                             const int* ldy, const int* N, const int* relu, int M, int K,
+                                             const float* const* pos, const int* pos_rows,
+                                             const unsigned char* const* row_keep, const float* const* relu_ref,
+                                             const int* ldref, const float* const* add1, const float* const* add2,
+                                             const int* ldadd, float* const* colpart, int terms) {
+  const int pieces = pieces_of(terms);
+  if (!pieces) return EGTR_E_ARG;
   if (!x || !ldx || !w_tiled || !bias || !y || !ldy || !N || !relu) return EGTR_E_ARG;
   if (num_problems <= 0 || num_problems > kMaxProblems || M <= 0 || K <= 0) return EGTR_E_ARG;
   if ((pos != nullptr && pos_rows == nullptr) || (relu_ref != nullptr && ldref == nullptr) ||
@@ -854,16 +864,10 @@ static int linear_ex_impl(int pieces, egtr_stream_t stream, int num_problems, co
   return launch_grouped(static_cast<hipStream_t>(stream), P, num_problems, M, K, pieces);
 }
 
-extern "C" int egtr_linear_split_bf16_grouped_pos_f32(egtr_stream_t stream, int num_problems, const float* const* x,
-                                                      const int* ldx, const uint16_t* const* w_tiled,
-                                                      const float* const* bias, float* const* y, const int* ldy,
-                                                      const int* N, const int* relu, int M, int K,
-                                                      const float* const* pos, const int* pos_rows) {
-  return linear_ex_impl(3, stream, num_problems, x, ldx, w_tiled, bias, y, ldy, N, relu, M, K, pos, pos_rows, nullptr, nullptr,
-                        nullptr, nullptr, nullptr, nullptr, nullptr);
-}
-
-static int tile_impl(int pieces, egtr_stream_t stream, const float* w, int ldw, int transposed, int N, int K, uint16_t* w_tiled) {
+extern "C" int egtr_gemm_split_tile_weights_f32(egtr_stream_t stream, const float* w, int ldw, int transposed, int N, int K,
+                                                uint16_t* w_tiled, int terms) {
+  const int pieces = pieces_of(terms);
+  if (!pieces) return EGTR_E_ARG;
   if (!w || !w_tiled || N <= 0 || K <= 0 || ldw < (transposed ? N : K)) return EGTR_E_ARG;
   if (N % kBN != 0 || K % kBK != 0 || (long long)N * K > (1LL << 30)) return EGTR_E_UNSUPPORTED;
   if (pieces == 1)
@@ -875,7 +879,10 @@ static int tile_impl(int pieces, egtr_stream_t stream, const float* w, int ldw, 
   return egtr_check_launch();
 }
 
-static int tile_pair_impl(int pieces, egtr_stream_t stream, const float* w, int ldw, int N, int K, uint16_t* w_tiled_pair) {
+extern "C" int egtr_gemm_split_tile_weights_pair_f32(egtr_stream_t stream, const float* w, int ldw, int N, int K,
+                                                     uint16_t* w_tiled_pair, int terms) {
+  const int pieces = pieces_of(terms);
+  if (!pieces) return EGTR_E_ARG;
   if (!w || !w_tiled_pair || N <= 0 || K <= 0 || ldw < K) return EGTR_E_ARG;
   if (N % kBN != 0 || K % kBN != 0 || (long long)N * K > (1LL << 29)) return EGTR_E_UNSUPPORTED;
   if (pieces == 1)
@@ -887,13 +894,18 @@ static int tile_pair_impl(int pieces, egtr_stream_t stream, const float* w, int 
   return egtr_check_launch();
 }
 
-static long long wgrad_workspace_impl(int pieces, int M, int N, int K) {
-  if (M <= 0 || N <= 0 || K <= 0 || N % 128 || K % 128) return 0;
+extern "C" long long egtr_linear_split_bf16_wgrad_workspace_floats(int M, int N, int K, int terms) {
+  const int pieces = pieces_of(terms);
+  if (!pieces || M <= 0 || N <= 0 || K <= 0 || N % 128 || K % 128) return 0;
   return (long long)wgrad_plan(M, N, K, pieces == 1 ? kR1StageMExt : kBK).chunks * N * K;   // (one term: the larger of its two plans)
 }
 
-static int wgrad_ex_impl(int pieces, egtr_stream_t stream, const float* g, int ldg, const float* x, int ldx, float* grad_weight,
-                  float* workspace, int M, int N, int K, const float* x_pos, int pos_rows, const unsigned char* row_keep) {
+extern "C" int egtr_linear_split_bf16_wgrad_ex_f32(egtr_stream_t stream, const float* g, int ldg, const float* x, int ldx,
+                                                   float* grad_weight, float* workspace, int M, int N, int K,
+                                                   const float* x_pos, int pos_rows, const unsigned char* row_keep,
+                                                   int terms) {
+  const int pieces = pieces_of(terms);
+  if (!pieces) return EGTR_E_ARG;
   if (!g || !x || !grad_weight || !workspace || M <= 0 || N <= 0 || K <= 0 || ldg < N || ldx < K) return EGTR_E_ARG;
   if (x_pos != nullptr && pos_rows <= 0) return EGTR_E_ARG;
   if (N % 128 || K % 128 || (reinterpret_cast<uintptr_t>(grad_weight) & 15) || (reinterpret_cast<uintptr_t>(workspace) & 15))
@@ -921,75 +933,4 @@ static int wgrad_ex_impl(int pieces, egtr_stream_t stream, const float* g, int l
   hipLaunchKernelGGL(wgrad_reduce_f32, dim3((n4 + 15) / 16), dim3(256), 0, st, reinterpret_cast<const float4*>(workspace),
                      pl.chunks, n4, reinterpret_cast<float4*>(grad_weight));
   return egtr_check_launch();
-}
-
-extern "C" int egtr_gemm_split_tile_weights_multi_f32(egtr_stream_t stream, int num_weights, const float* const* w,
-                                                      const int* ldw, const float* const* w2, const int* ldw2,
-                                                      const int* split_rows, const int* N, const int* K,
-                                                      uint16_t* const* w_tiled_pair) {
-  return tile_multi_impl(3, stream, num_weights, w, ldw, w2, ldw2, split_rows, N, K, w_tiled_pair);
-}
-extern "C" int egtr_gemm_bf16r_tile_weights_multi_f32(egtr_stream_t stream, int num_weights, const float* const* w,
-                                                      const int* ldw, const float* const* w2, const int* ldw2,
-                                                      const int* split_rows, const int* N, const int* K,
-                                                      uint16_t* const* w_tiled_pair) {
-  return tile_multi_impl(1, stream, num_weights, w, ldw, w2, ldw2, split_rows, N, K, w_tiled_pair);
-}
-
-extern "C" int egtr_linear_split_bf16_ex_f32(egtr_stream_t stream, int num_problems, const float* const* x, const int* ldx,
-                                             const uint16_t* const* w_tiled, const float* const* bias, float* const* y,
-                                             const int* ldy, const int* N, const int* relu, int M, int K,
-                                             const float* const* pos, const int* pos_rows,
-                                             const unsigned char* const* row_keep, const float* const* relu_ref,
-                                             const int* ldref, const float* const* add1, const float* const* add2,
-                                             const int* ldadd, float* const* colpart) {
-  return linear_ex_impl(3, stream, num_problems, x, ldx, w_tiled, bias, y, ldy, N, relu, M, K, pos, pos_rows, row_keep, relu_ref,
-                        ldref, add1, add2, ldadd, colpart);
-}
-extern "C" int egtr_linear_bf16r_ex_f32(egtr_stream_t stream, int num_problems, const float* const* x, const int* ldx,
-                                        const uint16_t* const* w_tiled, const float* const* bias, float* const* y,
-                                        const int* ldy, const int* N, const int* relu, int M, int K, const float* const* pos,
-                                        const int* pos_rows, const unsigned char* const* row_keep,
-                                        const float* const* relu_ref, const int* ldref, const float* const* add1,
-                                        const float* const* add2, const int* ldadd, float* const* colpart) {
-  return linear_ex_impl(1, stream, num_problems, x, ldx, w_tiled, bias, y, ldy, N, relu, M, K, pos, pos_rows, row_keep, relu_ref,
-                        ldref, add1, add2, ldadd, colpart);
-}
-
-extern "C" int egtr_gemm_split_tile_weights_f32(egtr_stream_t stream, const float* w, int ldw, int transposed, int N, int K,
-                                                uint16_t* w_tiled) {
-  return tile_impl(3, stream, w, ldw, transposed, N, K, w_tiled);
-}
-extern "C" int egtr_gemm_bf16r_tile_weights_f32(egtr_stream_t stream, const float* w, int ldw, int transposed, int N, int K,
-                                                uint16_t* w_tiled) {
-  return tile_impl(1, stream, w, ldw, transposed, N, K, w_tiled);
-}
-extern "C" int egtr_gemm_split_tile_weights_pair_f32(egtr_stream_t stream, const float* w, int ldw, int N, int K,
-                                                     uint16_t* w_tiled_pair) {
-  return tile_pair_impl(3, stream, w, ldw, N, K, w_tiled_pair);
-}
-extern "C" int egtr_gemm_bf16r_tile_weights_pair_f32(egtr_stream_t stream, const float* w, int ldw, int N, int K,
-                                                     uint16_t* w_tiled_pair) {
-  return tile_pair_impl(1, stream, w, ldw, N, K, w_tiled_pair);
-}
-
-extern "C" long long egtr_linear_split_bf16_wgrad_workspace_floats(int M, int N, int K) {
-  return wgrad_workspace_impl(3, M, N, K);
-}
-extern "C" long long egtr_linear_bf16r_wgrad_workspace_floats(int M, int N, int K) { return wgrad_workspace_impl(1, M, N, K); }
-
-extern "C" int egtr_linear_split_bf16_wgrad_ex_f32(egtr_stream_t stream, const float* g, int ldg, const float* x, int ldx,
-                                                   float* grad_weight, float* workspace, int M, int N, int K,
-                                                   const float* x_pos, int pos_rows, const unsigned char* row_keep) {
-  return wgrad_ex_impl(3, stream, g, ldg, x, ldx, grad_weight, workspace, M, N, K, x_pos, pos_rows, row_keep);
-}
-extern "C" int egtr_linear_bf16r_wgrad_ex_f32(egtr_stream_t stream, const float* g, int ldg, const float* x, int ldx,
-                                              float* grad_weight, float* workspace, int M, int N, int K, const float* x_pos,
-                                              int pos_rows, const unsigned char* row_keep) {
-  return wgrad_ex_impl(1, stream, g, ldg, x, ldx, grad_weight, workspace, M, N, K, x_pos, pos_rows, row_keep);
-}
-
-extern "C" int egtr_linear_split_bf16_wgrad_f32(egtr_stream_t stream, const float* g, int ldg, const float* x, int ldx,
-                                                float* grad_weight, float* workspace, int M, int N, int K) {
-  return wgrad_ex_impl(3, stream, g, ldg, x, ldx, grad_weight, workspace, M, N, K, nullptr, 1, nullptr);
 }

@@ -236,7 +236,7 @@ def input_proj_x6_weights(w):
     N = w.shape[0]
     wm = w.permute(0, 2, 3, 1).reshape(N, -1).contiguous()
     out = torch.empty(N // 128, wm.shape[1] // 32, 3, 128, 32, dtype=torch.bfloat16, device=w.device)
-    _lib.launch("egtr_gemm_split_tile_weights_f32", wm.data_ptr(), wm.stride(0), 0, N, wm.shape[1], out.data_ptr())
+    _lib.launch("egtr_gemm_split_tile_weights_f32", wm.data_ptr(), wm.stride(0), 0, N, wm.shape[1], out.data_ptr(), 6)
     return out
 
 

@@ -106,15 +106,11 @@ def weighted_column_sum(g, row_weight):
     return out
 
 
-def _host_array(ctype, vals):
-    import ctypes
-    return (ctype * len(vals))(*vals)
-
-
-# ``terms``: which arithmetic a split-GEMM binding launches.  6 (the default everywhere): the six-term split-bf16 product,
-# fp32 to the last bit, on the three-piece weight stream [N/128][K/32][3][128][32].  1: one product per element, each operand
-# rounded once to bf16 (round to nearest even), fp32 accumulation, on the one-piece stream [N/128][K/32][128][32] -- the
-# egtr_*_bf16r_* entries; ``egtr_amd.ops`` passes it from ``ops.matmul_precision()`` in its training Functions and nowhere else.
+# ``terms``: which arithmetic a split-GEMM binding launches; it travels as the trailing argument of the C entries.  6 (the
+# default everywhere): the six-term split-bf16 product, fp32 to the last bit, on the three-piece weight stream
+# [N/128][K/32][3][128][32].  1: one product per element, each operand rounded once to bf16 (round to nearest even), fp32
+# accumulation, on the one-piece stream [N/128][K/32][128][32]; ``egtr_amd.ops`` passes it from ``ops.matmul_precision()`` in
+# its training Functions and nowhere else.
 def _pieces(terms):
     if terms not in (1, 6):
         raise ValueError(f"terms must be 6 (split-bf16, fp32 accuracy) or 1 (operands rounded to bf16), got {terms!r}")
@@ -125,71 +121,105 @@ def _stream_shape(N, K, terms):
     return (N // 128, K // 32, 3, 128, 32) if _pieces(terms) == 3 else (N // 128, K // 32, 128, 32)
 
 
-def _entry(terms, six, one):
-    return six if _pieces(terms) == 3 else one
+_EPILOGUE = frozenset(("row_keep", "relu_ref", "add1", "add2", "colpart"))
+
+
+def _split_launch(who, problems, M, K, terms, x_as_given=False):
+    """ONE launch of egtr_linear_split_bf16_ex_f32 for 1..16 problems (kMaxProblems of csrc/gemm_split.hip) of M rows and
+    reduction length K, after the checks every split-GEMM binding shares.  A problem is a dict: x [..., K] (viewed as rows; copied
+    when the kernel's stride / alignment rules ask for it), wt (tiled weight of ``terms``), N, and optionally b, relu, out (float32
+    [M, N] view, unit inner stride, row stride % 4 == 0, 16-byte aligned base: rows of a larger buffer are fine), pos
+    ([pos_rows, K], pos_rows divides M), row_keep, relu_ref, add1, add2, colpart.  ``x_as_given``: x is the [M, >= K] matrix
+    itself (a column block of a wider buffer has more than K columns, which no row view expresses) and is never copied.
+    Returns the outputs."""
+    import ctypes
+    n = len(problems)
+    if not 0 < n <= 16:
+        raise RuntimeError(f"{who}: 1..16 problems in one launch, got {n}")
+    # One pass: a problem becomes its row of the ten host arrays.  The eager inference forward is host-bound and makes three
+    # such launches per image, one of them with 14 problems, so nothing below looks at a problem twice.
+    rows, ys, keep = [], [], []
+    epi = None      # the training step's epilogue operands, key -> per-problem tensors; built once a problem names one
+    for i, it in enumerate(problems):
+        x2 = it["x"] if x_as_given else _lib.row_view(it["x"], K)
+        N, wt = int(it["N"]), it["wt"]
+        if not x2.is_cuda or x2.dtype != torch.float32 or x2.dim() != 2 or x2.stride(1) != 1:
+            raise RuntimeError(f"{who}: x must be a float32 CUDA/HIP tensor with unit inner stride")
+        if x2.shape[0] != M:
+            raise RuntimeError(f"{who}: all inputs must have the same number of rows")
+        _chk(wt, "wt", torch.bfloat16)
+        if tuple(wt.shape) != _stream_shape(N, K, terms):
+            raise RuntimeError(f"{who}: wt must be {list(_stream_shape(N, K, terms))} for terms={terms}, got {tuple(wt.shape)}")
+        b = it.get("b")
+        if b is not None:
+            b = _chk(b.detach().contiguous(), "bias", torch.float32)
+        y = it.get("out")
+        if y is None:
+            y = torch.empty(M, N, dtype=torch.float32, device=x2.device)
+        elif not (y.is_cuda and y.dtype == torch.float32 and y.dim() == 2 and tuple(y.shape) == (M, N)
+                  and y.stride(1) == 1 and y.stride(0) % 4 == 0 and y.data_ptr() % 16 == 0):
+            raise RuntimeError(f"{who}: out must be a float32 [rows, N] view with unit inner stride, a row stride that is a "
+                               "multiple of 4 and a 16-byte aligned base")
+        pos = it.get("pos")
+        if pos is not None:
+            pos = _chk(pos.reshape(-1, K).contiguous(), "pos", torch.float32)
+            if M % pos.shape[0]:
+                raise RuntimeError(f"{who}: pos must tile the rows")
+        if not _EPILOGUE.isdisjoint(it):
+            if epi is None:
+                epi = {key: [None] * n for key in _EPILOGUE}
+            for key in _EPILOGUE:
+                epi[key][i] = it.get(key)
+        # x, ldx, w_tiled, bias, y, ldy, N, relu, pos, pos_rows: the order of the C entry's arrays
+        rows.append((x2.data_ptr(), x2.stride(0), wt.data_ptr(), _lib.ptr(b), y.data_ptr(), y.stride(0), N,
+                     1 if it.get("relu") else 0, _lib.ptr(pos), pos.shape[0] if pos is not None else 1))
+        ys.append(y)
+        keep.append((x2, b, pos))      # (possibly copies: alive until the launch is queued)
+    PA, IA = ctypes.c_void_p * n, ctypes.c_int * n
+    px, ldx, pw, pb, py, ldy, Ns, relu, ppos, prows = zip(*rows)
+    tail = (None,) * 7      # an option no problem uses travels as a NULL array
+    if epi is not None:
+        rr, a1, a2 = epi["relu_ref"], epi["add1"], epi["add2"]
+        for key, ts in (("relu_ref", rr), ("add1", a1), ("add2", a2)):
+            for t in ts:
+                if t is not None and (t.stride(-1) != 1 or t.dtype != torch.float32 or not t.is_cuda):
+                    raise RuntimeError(f"{who}: {key} must be a float32 device tensor with unit inner stride")
+        if any(p is not None and q is not None and p.stride(0) != q.stride(0) for p, q in zip(a1, a2)):
+            raise RuntimeError(f"{who}: add1 and add2 must share their row stride")
+
+        def ptrs(ts):
+            return PA(*[_lib.ptr(t) for t in ts]) if any(t is not None for t in ts) else None
+
+        def lds(ts):
+            return IA(*[(t.stride(0) if t is not None else 0) for t in ts])
+
+        tail = (ptrs(epi["row_keep"]), ptrs(rr), lds(rr), ptrs(a1), ptrs(a2),
+                lds([p if p is not None else q for p, q in zip(a1, a2)]), ptrs(epi["colpart"]))
+    _lib.launch("egtr_linear_split_bf16_ex_f32", n, PA(*px), IA(*ldx), PA(*pw), PA(*pb), PA(*py), IA(*ldy), IA(*Ns), IA(*relu),
+                M, K, PA(*ppos), IA(*prows), *tail, terms)
+    return ys
 
 
 def linear_split_ex(problems, M, K, terms=6):
-    """Up to 8 token-sized linears with the same M and K in one launch of the split-bf16 GEMM with the training step's epilogue
+    """Up to 16 token-sized linears with the same M and K in one launch of the split-bf16 GEMM with the training step's epilogue
     options (egtr_linear_split_bf16_ex_f32).  ``problems``: dicts with x [M, >=K] (unit inner stride), wt (tiled weight), N,
-    and optionally b, relu, out ([M, N] view with unit inner stride), pos ([pos_rows, K]), row_keep ([M] uint8), relu_ref
-    ([M, N]), add1 / add2 ([M, N], may alias out), colpart ([ceil(M / 32), N]).  Returns the outputs.  No autograd.  ``terms=1``: the one-term
-    arithmetic (egtr_linear_bf16r_ex_f32) on one-piece weight streams."""
-    import ctypes
-    n = len(problems)
-    for it in problems:
-        if tuple(it["wt"].shape) != _stream_shape(int(it["N"]), K, terms):
-            raise RuntimeError(f"linear_split_ex: wt must be {_stream_shape(int(it['N']), K, terms)} for terms={terms}, got "
-                               f"{tuple(it['wt'].shape)}")
-    P, I = ctypes.c_void_p, ctypes.c_int
-    outs = []
-    for it in problems:
-        y = it.get("out")
-        if y is None:
-            y = torch.empty(M, int(it["N"]), dtype=torch.float32, device=it["x"].device)
-        outs.append(y)
-
-    def ptrs(key):
-        vals = [_lib.ptr(it.get(key)) for it in problems]
-        return _host_array(P, vals) if any(v is not None for v in vals) else None
-
-    def ld(key):
-        return _host_array(I, [(it[key].stride(0) if it.get(key) is not None else 0) for it in problems])
-
-    for it in problems:
-        for key in ("x", "relu_ref", "add1", "add2"):
-            t = it.get(key)
-            if t is not None and (t.stride(-1) != 1 or t.dtype != torch.float32 or not t.is_cuda):
-                raise RuntimeError(f"linear_split_ex: {key} must be a float32 device tensor with unit inner stride")
-        if it.get("add1") is not None and it.get("add2") is not None and it["add1"].stride(0) != it["add2"].stride(0):
-            raise RuntimeError("linear_split_ex: add1 and add2 must share their row stride")
-    ldadd = _host_array(I, [((it.get("add1") if it.get("add1") is not None else it.get("add2")).stride(0)
-                             if (it.get("add1") is not None or it.get("add2") is not None) else 0) for it in problems])
-    _lib.launch(_entry(terms, "egtr_linear_split_bf16_ex_f32", "egtr_linear_bf16r_ex_f32"), n,
-                _host_array(P, [it["x"].data_ptr() for it in problems]),
-                _host_array(I, [it["x"].stride(0) for it in problems]),
-                _host_array(P, [it["wt"].data_ptr() for it in problems]),
-                _host_array(P, [_lib.ptr(it.get("b")) for it in problems]),
-                _host_array(P, [y.data_ptr() for y in outs]), _host_array(I, [y.stride(0) for y in outs]),
-                _host_array(I, [int(it["N"]) for it in problems]),
-                _host_array(I, [1 if it.get("relu") else 0 for it in problems]), int(M), int(K), ptrs("pos"),
-                _host_array(I, [(it["pos"].shape[0] if it.get("pos") is not None else 1) for it in problems]), ptrs("row_keep"),
-                ptrs("relu_ref"), ld("relu_ref"), ptrs("add1"), ptrs("add2"), ldadd, ptrs("colpart"))
-    return outs
+    and optionally b, relu, out ([M, N] view with unit inner stride), pos ([pos_rows, K], pos_rows divides M), row_keep ([M]
+    uint8), relu_ref
+    ([M, N]), add1 / add2 ([M, N], may alias out), colpart ([ceil(M / 32), N]).  Returns the outputs.  No autograd.
+    ``terms=1``: the one-term arithmetic on one-piece weight streams."""
+    return _split_launch("linear_split_ex", problems, int(M), int(K), terms, x_as_given=True)
 
 
 def _wgrad_ex(g, x, x_pos=None, row_keep=None, terms=6):
-    """g [M, N]^T . (x [+ x_pos rows]) [M, K] -> [N, K] with optional row mask on g (egtr_linear_split_bf16_wgrad_ex_f32;
-    ``terms=1``: egtr_linear_bf16r_wgrad_ex_f32)."""
+    """g [M, N]^T . (x [+ x_pos rows]) [M, K] -> [N, K] with optional row mask on g (egtr_linear_split_bf16_wgrad_ex_f32)."""
     lib = _lib.lib()
     M, N = g.shape
     K = x.shape[1]
-    floats = getattr(lib, _entry(terms, "egtr_linear_split_bf16_wgrad_workspace_floats",
-                                 "egtr_linear_bf16r_wgrad_workspace_floats"))(M, N, K)
-    ws = torch.empty(int(floats), dtype=torch.float32, device=g.device)
+    _pieces(terms)
+    ws = torch.empty(int(lib.egtr_linear_split_bf16_wgrad_workspace_floats(M, N, K, terms)), dtype=torch.float32, device=g.device)
     gw = torch.empty(N, K, dtype=torch.float32, device=g.device)
-    _lib.launch(_entry(terms, "egtr_linear_split_bf16_wgrad_ex_f32", "egtr_linear_bf16r_wgrad_ex_f32"), g.data_ptr(), g.stride(0), x.data_ptr(), x.stride(0), gw.data_ptr(),
-                ws.data_ptr(), M, N, K, _lib.ptr(x_pos), x_pos.shape[0] if x_pos is not None else 1, _lib.ptr(row_keep))
+    _lib.launch("egtr_linear_split_bf16_wgrad_ex_f32", g.data_ptr(), g.stride(0), x.data_ptr(), x.stride(0), gw.data_ptr(),
+                ws.data_ptr(), M, N, K, _lib.ptr(x_pos), x_pos.shape[0] if x_pos is not None else 1, _lib.ptr(row_keep), terms)
     return gw
 
 
@@ -329,35 +359,32 @@ def gemm_split_weights(weight, terms=6):
 
 
 def gemm_split_tile(weight, transposed=False, terms=6):
-    """``gemm_split_weights(weight, terms)`` (``transposed``: of ``weight.t()``) in one launch (egtr_gemm_split_tile_weights_f32,
-    egtr_gemm_bf16r_tile_weights_f32): the training step re-tiles each weight after every optimizer step, for the forward (W)
-    and the data gradient (W^T)."""
+    """``gemm_split_weights(weight, terms)`` (``transposed``: of ``weight.t()``) in one launch (egtr_gemm_split_tile_weights_f32):
+    the training step re-tiles each weight after every optimizer step, for the forward (W) and the data gradient (W^T)."""
     w = weight.detach()
     if not w.is_cuda or w.dtype != torch.float32 or w.dim() != 2 or w.stride(1) != 1:
         raise RuntimeError("gemm_split_tile: weight must be a 2-d float32 CUDA/HIP tensor with unit inner stride")
     N, K = (w.shape[1], w.shape[0]) if transposed else (w.shape[0], w.shape[1])
     out = torch.empty(_stream_shape(N, K, terms), dtype=torch.bfloat16, device=w.device)
-    _lib.launch(_entry(terms, "egtr_gemm_split_tile_weights_f32", "egtr_gemm_bf16r_tile_weights_f32"), w.data_ptr(), w.stride(0),
-                1 if transposed else 0, N, K, out.data_ptr())
+    _lib.launch("egtr_gemm_split_tile_weights_f32", w.data_ptr(), w.stride(0), 1 if transposed else 0, N, K, out.data_ptr(), terms)
     return out
 
 
 def gemm_split_tile_pair(weight, terms=6):
-    """(tiling of W, tiling of W^T) in one launch (egtr_gemm_split_tile_weights_pair_f32 / egtr_gemm_bf16r_..); N, K % 128 == 0."""
+    """(tiling of W, tiling of W^T) in one launch (egtr_gemm_split_tile_weights_pair_f32); N, K % 128 == 0."""
     w = weight.detach()
     if not w.is_cuda or w.dtype != torch.float32 or w.dim() != 2 or w.stride(1) != 1:
         raise RuntimeError("gemm_split_tile_pair: weight must be a 2-d float32 CUDA/HIP tensor with unit inner stride")
     N, K = w.shape
     out = torch.empty(2, _pieces(terms) * N * K, dtype=torch.bfloat16, device=w.device)
-    _lib.launch(_entry(terms, "egtr_gemm_split_tile_weights_pair_f32", "egtr_gemm_bf16r_tile_weights_pair_f32"), w.data_ptr(),
-                w.stride(0), N, K, out.data_ptr())
+    _lib.launch("egtr_gemm_split_tile_weights_pair_f32", w.data_ptr(), w.stride(0), N, K, out.data_ptr(), terms)
     return out[0].view(_stream_shape(N, K, terms)), out[1].view(_stream_shape(K, N, terms))
 
 
 def gemm_split_tile_pairs(weights, terms=6):
     """[(tiling of W, tiling of W^T)] for up to 8 weights in ONE launch (egtr_gemm_split_tile_weights_multi_f32).  An entry
     is a [N, K] tensor or a pair (w_a, w_b) of tensors with the same K: the row-wise concatenation [w_a; w_b] tiled as one
-    weight without materialising it.  N, K multiples of 128.  ``terms=1``: egtr_gemm_bf16r_tile_weights_multi_f32."""
+    weight without materialising it.  N, K multiples of 128."""
     import ctypes
     n = len(weights)
     P, I = ctypes.c_void_p, ctypes.c_int
@@ -376,33 +403,24 @@ def gemm_split_tile_pairs(weights, terms=6):
         w1.append(a.data_ptr()); ld1.append(a.stride(0)); split.append(a.shape[0])
         w2.append(_lib.ptr(b)); ld2.append(b.stride(0) if b is not None else 0)
         Ns.append(N); Ks.append(K); outs.append(out)
-    _lib.launch(_entry(terms, "egtr_gemm_split_tile_weights_multi_f32", "egtr_gemm_bf16r_tile_weights_multi_f32"), n, (P * n)(*w1), (I * n)(*ld1), (P * n)(*w2), (I * n)(*ld2),
-                (I * n)(*split), (I * n)(*Ns), (I * n)(*Ks), (P * n)(*[o.data_ptr() for o in outs]))
+    _lib.launch("egtr_gemm_split_tile_weights_multi_f32", n, (P * n)(*w1), (I * n)(*ld1), (P * n)(*w2), (I * n)(*ld2),
+                (I * n)(*split), (I * n)(*Ns), (I * n)(*Ks), (P * n)(*[o.data_ptr() for o in outs]), terms)
     return [(o[0].view(_stream_shape(N, K, terms)), o[1].view(_stream_shape(K, N, terms))) for o, N, K in zip(outs, Ns, Ks)]
 
 
 def linear_split_bf16_wgrad(g, x, terms=6):
     """g [M, N]^T . x [M, K] -> [N, K] (the weight gradient of a token-sized linear layer) through
-    egtr_linear_split_bf16_wgrad_f32 (``terms=1``: egtr_linear_bf16r_wgrad_ex_f32); unit inner strides, N, K % 128 == 0."""
-    lib = _lib.lib()
-    M, N = g.shape
-    K = x.shape[1]
-    if x.shape[0] != M or g.stride(1) != 1 or x.stride(1) != 1:
+    egtr_linear_split_bf16_wgrad_ex_f32 without its options; unit inner strides, N, K % 128 == 0."""
+    if x.shape[0] != g.shape[0] or g.stride(1) != 1 or x.stride(1) != 1:
         raise RuntimeError("linear_split_bf16_wgrad: g [M, N] and x [M, K] with unit inner strides expected")
-    if _pieces(terms) == 1:
-        return _wgrad_ex(g, x, terms=1)
-    ws = torch.empty(int(lib.egtr_linear_split_bf16_wgrad_workspace_floats(M, N, K)), dtype=torch.float32, device=g.device)
-    gw = torch.empty(N, K, dtype=torch.float32, device=g.device)
-    _lib.launch("egtr_linear_split_bf16_wgrad_f32", g.data_ptr(), g.stride(0), x.data_ptr(), x.stride(0), gw.data_ptr(),
-                ws.data_ptr(), M, N, K)
-    return gw
+    return _wgrad_ex(g, x, terms=terms)
 
 
 def linear_split_bf16(x, w_tiled, bias, N, relu=False, out=None, terms=6):
     """act(x W^T + b) through egtr_linear_split_bf16_f32 (no autograd).  x [..., K] fp32 with unit inner stride and a
     uniform row stride (a column block of a wider buffer is fine); w_tiled from ``gemm_split_weights``; ``out``: optional
     contiguous [rows, N] fp32 destination.  ``terms=1``: the one-term arithmetic on the one-piece stream
-    (egtr_linear_bf16r_ex_f32 with one problem)."""
+    (egtr_linear_split_bf16_ex_f32 with one problem)."""
     K = x.shape[-1]
     x2 = _lib.row_view(x, K)
     _chk(w_tiled, "w_tiled", torch.bfloat16)
@@ -416,7 +434,7 @@ def linear_split_bf16(x, w_tiled, bias, N, relu=False, out=None, terms=6):
     else:
         y = torch.empty(x2.shape[0], N, dtype=torch.float32, device=x.device)
     if _pieces(terms) == 1:
-        linear_split_ex([dict(x=x2, wt=w_tiled, N=N, b=b, relu=relu, out=y)], x2.shape[0], K, terms=1)
+        _split_launch("linear_split_bf16", [dict(x=x2, wt=w_tiled, N=N, b=b, relu=relu, out=y)], x2.shape[0], K, 1)
     else:
         _lib.launch("egtr_linear_split_bf16_f32", x2.data_ptr(), x2.stride(0), w_tiled.data_ptr(), _lib.ptr(b), y.data_ptr(), N,
                     x2.shape[0], K, N, 1 if relu else 0)
@@ -424,52 +442,12 @@ def linear_split_bf16(x, w_tiled, bias, N, relu=False, out=None, terms=6):
 
 
 def linear_split_bf16_grouped(items):
-    """Several token-sized linears with the same row count and K in ONE launch (egtr_linear_split_bf16_grouped_pos_f32).
-    ``items``: dicts with x [..., K], wt (from ``gemm_split_weights``), N, optional b, relu, out ([rows, N] contiguous),
-    pos ([pos_rows, K], added to x's rows (row % pos_rows) on the way into the kernel).  Returns the outputs ([rows, N]).
-    Inference only."""
-    import ctypes
-    n = len(items)
-    K = items[0]["x"].shape[-1]
-    xs, outs, keep, poss = [], [], [], []
-    for it in items:
-        x2 = _lib.row_view(it["x"], K)
-        if not x2.is_cuda or x2.dtype != torch.float32:
-            raise RuntimeError("linear_split_bf16_grouped: x must be a float32 CUDA/HIP tensor")
-        N = int(it["N"])
-        _chk(it["wt"], "wt", torch.bfloat16)
-        if tuple(it["wt"].shape) != (N // 128, K // 32, 3, 128, 32):
-            raise RuntimeError(f"wt must be [{N // 128}, {K // 32}, 3, 128, 32], got {tuple(it['wt'].shape)}")
-        y = it.get("out")
-        if y is None:
-            y = torch.empty(x2.shape[0], N, dtype=torch.float32, device=x2.device)
-        elif not (y.is_cuda and y.dtype == torch.float32 and y.dim() == 2 and tuple(y.shape) == (x2.shape[0], N)
-                  and y.stride(1) == 1 and y.stride(0) % 4 == 0 and y.data_ptr() % 16 == 0):
-            # (rows of a larger buffer are fine: the kernel takes the row stride)
-            raise RuntimeError("linear_split_bf16_grouped: out must be a float32 [rows, N] view with unit inner stride, a "
-                               "row stride that is a multiple of 4 and a 16-byte aligned base")
-        b = it.get("b")
-        if b is not None:
-            b = _chk(b.detach().contiguous(), "bias", torch.float32)
-        pos = it.get("pos")
-        if pos is not None:
-            pos = _chk(pos.reshape(-1, K).contiguous(), "pos", torch.float32)
-            if x2.shape[0] % pos.shape[0]:
-                raise RuntimeError("linear_split_bf16_grouped: pos must tile the rows")
-        poss.append(pos)
-        keep.append((x2, b))
-        xs.append(x2)
-        outs.append(y)
-    M = xs[0].shape[0]
-    if any(x2.shape[0] != M for x2 in xs):
-        raise RuntimeError("linear_split_bf16_grouped: all inputs must have the same number of rows")
-    PA, IA = ctypes.c_void_p * n, ctypes.c_int * n
-    _lib.launch("egtr_linear_split_bf16_grouped_pos_f32", n, PA(*[x2.data_ptr() for x2 in xs]),
-                IA(*[x2.stride(0) for x2 in xs]), PA(*[it["wt"].data_ptr() for it in items]),
-                PA(*[_lib.ptr(b) for _, b in keep]), PA(*[y.data_ptr() for y in outs]), IA(*[y.stride(0) for y in outs]),
-                IA(*[int(it["N"]) for it in items]), IA(*[1 if it.get("relu") else 0 for it in items]), M, K,
-                PA(*[_lib.ptr(p) for p in poss]), IA(*[(p.shape[0] if p is not None else 1) for p in poss]))
-    return outs
+    """Several token-sized linears with the same row count and K in ONE launch (egtr_linear_split_bf16_ex_f32, six terms).
+    ``items``: dicts with x [..., K], wt (from ``gemm_split_weights``), N, optional b, relu, out ([rows, N] view with unit inner
+    stride: rows of a larger buffer are fine), pos ([pos_rows, K], added to x's rows (row % pos_rows) on the way into the
+    kernel).  Returns the outputs ([rows, N]).  Inference only."""
+    x0 = items[0]["x"]
+    return _split_launch("linear_split_bf16_grouped", items, x0.numel() // x0.shape[-1], x0.shape[-1], 6)
 
 
 def ffn_fused(x, fc1, fc2, ln=None, pos=None):

@@ -25,7 +25,7 @@ from .kernels.elementwise import *  # noqa: F401,F403
 from .kernels.elementwise import _DIM_T  # noqa: F401
 from .kernels.heads import *  # noqa: F401,F403
 from .kernels.linear import *  # noqa: F401,F403
-from .kernels.linear import _c16, _host_array, _skinny_bwd, _skinny_fwd, _split3_bf16, _wgrad_ex  # noqa: F401
+from .kernels.linear import _c16, _skinny_bwd, _skinny_fwd, _split3_bf16, _wgrad_ex  # noqa: F401
 from .kernels.protocols import *  # noqa: F401,F403
 from .kernels.statistics import *  # noqa: F401,F403
 from .kernels.vrd import *  # noqa: F401,F403
@@ -426,6 +426,14 @@ def _rows256(t):
     return t2
 
 
+def _keep_bytes(keep_rows):
+    """[..] bool / integer row mask (non-zero = valid token) -> the flat uint8 ``row_keep`` operand of the split GEMMs; None stays None."""
+    if keep_rows is None:
+        return None
+    rk = keep_rows.reshape(-1).contiguous()
+    return rk.view(torch.uint8) if rk.dtype == torch.bool else rk.to(torch.uint8)
+
+
 class EncoderLayerTrainFunction(Function):
     """One Deformable-DETR encoder layer in TRAINING as a single autograd node (reference: DeformableDetrEncoderLayer.forward
     in train mode, model/deformable_detr.py:1283-1358, with DeformableDetrMultiscaleDeformableAttention.forward, :1026-1104):
@@ -451,10 +459,7 @@ class EncoderLayerTrainFunction(Function):
         dev = x.device
         x2 = _rows256(x.detach())
         pos2 = _rows256(pos.detach())
-        rk = None
-        if keep_rows is not None:
-            rk = keep_rows.reshape(-1).contiguous()
-            rk = rk.view(torch.uint8) if rk.dtype == torch.bool else rk.to(torch.uint8)
+        rk = _keep_bytes(keep_rows)
         bb = torch.cat([so_b.detach(), aw_b.detach()], 0)
         ctx.terms = terms = _gemm_terms()   # read once: the tiled weights saved for the backward are of this kind only
         # every weight of the layer (and its transpose, for the data gradients) into the GEMM's operand stream: one launch;
@@ -561,10 +566,7 @@ class DecoderValueProjTrainFunction(Function):
         B, S, D = enc.shape
         M = B * S
         x2 = _rows256(enc.detach())
-        rk = None
-        if keep_rows is not None:
-            rk = keep_rows.reshape(-1).contiguous()
-            rk = rk.view(torch.uint8) if rk.dtype == torch.bool else rk.to(torch.uint8)
+        rk = _keep_bytes(keep_rows)
         ctx.terms = terms = _gemm_terms()
         tiles = []
         for i0 in range(0, nl, 8):
@@ -934,7 +936,7 @@ class deterministic:
 # kernels: under "bf16" the token-sized products of the autograd training routes -- TokenLinearFunction (forward, data gradient,
 # weight gradient), every product of EncoderLayerTrainFunction and DecoderValueProjTrainFunction -- round each operand ONCE to
 # bf16 (round to nearest even; `x + pos` is added in fp32 first) and issue one matrix instruction per k-step instead of six
-# (csrc/gemm_split.hip, the egtr_*_bf16r_* entries).  Accumulation, the tensors in memory, master weights, gradients and the
+# (csrc/gemm_split.hip, `terms` = 1 of its entries).  Accumulation, the tensors in memory, master weights, gradients and the
 # optimizer stay fp32; bf16 has fp32's exponent range, so there is no loss scaling.  Consulted AT CALL TIME in a Function's
 # forward and kept on its ctx for the backward (a route switch, not a fall-off: nothing is counted in FALLBACKS).
 # Not covered: every inference route (module_linear, ffn_fused, the grouped projections, the relation head, the backbone) keeps

@@ -46,7 +46,7 @@ enum {
 
 /* Bumped whenever an entry point is added / removed or the meaning of an argument changes; egtr_amd/_lib.py refuses a
  * library whose number differs from the one it was written against. */
-#define EGTR_ABI_VERSION 5
+#define EGTR_ABI_VERSION 6
 int egtr_abi_version(void);
 const char* egtr_status_string(int status);
 /* last HIP error string seen by this thread (for EGTR_E_LAUNCH) */
@@ -841,56 +841,56 @@ int egtr_rel_head_forward_bf16p(egtr_stream_t stream, const float* gate_q, const
 int egtr_linear_bf16(egtr_stream_t stream, const uint16_t* x, int ldx, const uint16_t* weight, const uint16_t* bias,
                      uint16_t* y, int ldy, int M, int N, int K, int relu, float alpha);
 
-/* Token-sized nn.Linear, y[M, N] (row stride ldy) = act(x[M, K] (row stride ldx) . W[N, K]^T + bias): fp32 in, fp32 out,
- * fp32-level accuracy, evaluated on the bf16 matrix cores from exact three-way bf16 splits of both operands (six cross
- * terms, fp32 accumulation; csrc/gemm_split.hip).  Replaces the vendor fp32 GEMM behind the reference's encoder
- * nn.Linear layers (model/deformable_detr.py:1049, 1053-1058, 1102, 1337-1343) in inference.  w_tiled: W pre-split and
- * pre-tiled, raw bfloat16 bits, [N/128][K/32][3 pieces hi, mid, lo][128 rows][32]
- * (egtr_amd/ops.py::gemm_split_weights).  K % 32 == 0, N % 128 == 0, x 16-byte aligned with ldx % 4 == 0, else
- * EGTR_E_UNSUPPORTED.  bias may be NULL; relu != 0 applies max(., 0). */
+/* ---- token-sized nn.Linear on the bf16 matrix cores (csrc/gemm_split.hip): seven entries ---------------------------------
+ * y[M, N] (row stride ldy) = act(x[M, K] (row stride ldx) . W[N, K]^T + bias): fp32 in, fp32 out.  Replaces the vendor fp32
+ * GEMM behind the reference's encoder nn.Linear layers (model/deformable_detr.py:1049, 1053-1058, 1102, 1337-1343).
+ *
+ * `terms`, the trailing argument of every entry but the first, selects the arithmetic:
+ *   6  fp32-level accuracy from exact three-way bf16 splits of both operands (six cross terms, fp32 accumulation).  w_tiled
+ *      is W pre-split and pre-tiled, raw bfloat16 bits, [N/128][K/32][3 pieces hi, mid, lo][128 rows][32]
+ *      (egtr_amd/ops.py::gemm_split_weights); the pair forms hold [tiling of W (3 N K) | tiling of W^T (3 N K)].
+ *   1  matmul precision "bf16" of the training routes: ONE product per element, each operand rounded once to bf16, round to
+ *      nearest even (x after the on-load `+ pos` / `+ x_pos`: RNE(fl32(x + pos))), every bf16 x bf16 product exact in fp32,
+ *      fp32 accumulation.  Tensors stay fp32.  Inf and NaN survive the rounding (a non-finite element of x makes its output
+ *      row -- weight gradient: its column -- non-finite and nothing else); a finite value beyond the largest bf16 (about
+ *      3.39e38) rounds to Inf.  w_tiled is the ONE-piece stream [N/128][K/32][128 rows][32]
+ *      (ops.gemm_split_weights(w, terms=1)); the pair forms hold [tiling of W (N K) | tiling of W^T (N K)].
+ * Any other value: EGTR_E_ARG (the workspace query: 0) before anything else is looked at.  Validation, status codes,
+ * epilogue options and their order, grouping, strides and the weight gradient's fixed summation order do not depend on
+ * `terms`.  K % 32 == 0, N % 128 == 0, x 16-byte aligned with ldx % 4 == 0, else EGTR_E_UNSUPPORTED. */
+
+/* One product, six terms, scalar arguments: the form of the inference forward (no host arrays to build).  bias may be NULL;
+ * relu != 0 applies max(., 0). */
 int egtr_linear_split_bf16_f32(egtr_stream_t stream, const float* x, int ldx, const uint16_t* w_tiled,
                                const float* bias, float* y, int ldy, int M, int K, int N, int relu);
 
-/* The w_tiled stream of the two entries around this one from W [N, K] fp32 (row stride ldw), or, with transposed != 0,
- * from the [K, N] array w holding W^T (element (n, k) at w[k * ldw + n]: the data-gradient product g . W of the training
- * backward is "linear" with weight W^T).  Pieces rounded to nearest even, bit-identical to ops.gemm_split_weights.
- * One launch -- the training step re-tiles every weight after each optimizer step. */
+/* The w_tiled stream from W [N, K] fp32 (row stride ldw), or, with transposed != 0, from the [K, N] array w holding W^T
+ * (element (n, k) at w[k * ldw + n]: the data-gradient product g . W of the training backward is "linear" with weight W^T).
+ * Pieces rounded to nearest even, bit-identical to ops.gemm_split_weights.  One launch -- the training step re-tiles every
+ * weight after each optimizer step. */
 int egtr_gemm_split_tile_weights_f32(egtr_stream_t stream, const float* w, int ldw, int transposed, int N, int K,
-                                     uint16_t* w_tiled);
-/* Both streams of W [N, K] in one launch: w_tiled_pair = [tiling of W (3 N K) | tiling of W^T (3 N K)] (N, K % 128 == 0). */
+                                     uint16_t* w_tiled, int terms);
+/* Both streams of W [N, K] in one launch: w_tiled_pair = [tiling of W | tiling of W^T] (N, K % 128 == 0). */
 int egtr_gemm_split_tile_weights_pair_f32(egtr_stream_t stream, const float* w, int ldw, int N, int K,
-                                          uint16_t* w_tiled_pair);
+                                          uint16_t* w_tiled_pair, int terms);
 /* The pair tilings of up to 8 weights in ONE launch (a training step re-tiles every encoder weight after each optimizer
  * step).  Weight i is [N[i], K[i]] (both multiples of 128): its first split_rows[i] rows are read from w[i] (row stride
  * ldw[i]) and the remaining rows from w2[i] (row stride ldw2[i]) -- two nn.Linear weights applied to the same input, e.g.
  * sampling_offsets | attention_weights (model/deformable_detr.py:1053-1058), tiled as ONE weight without a materialised
- * concatenation; w2 == NULL or w2[i] == NULL: a single source.  w_tiled_pair[i]: 6 N K bf16, as the pair entry writes them.
+ * concatenation; w2 == NULL or w2[i] == NULL: a single source.  w_tiled_pair[i]: as the pair entry writes them.
  * All arrays are HOST arrays. */
 int egtr_gemm_split_tile_weights_multi_f32(egtr_stream_t stream, int num_weights, const float* const* w, const int* ldw,
                                            const float* const* w2, const int* ldw2, const int* split_rows, const int* N,
-                                           const int* K, uint16_t* const* w_tiled_pair);
+                                           const int* K, uint16_t* const* w_tiled_pair, int terms);
 
-/* Weight gradient of such a layer in training: grad_weight [N, K] (contiguous) = g[M, N]^T . x[M, K] (row strides ldg,
- * ldx), same split arithmetic; the M rows are cut into chunks whose 128 x 128 partial products go through `workspace`
- * (egtr_linear_split_bf16_wgrad_workspace_floats(M, N, K) floats) and are summed in a fixed order (bit-reproducible).
- * Replaces the vendor GEMM autograd calls for model/deformable_detr.py's encoder nn.Linear layers (K = rows of the token
- * sequence: 66 TFLOP/s in the vendor library for N = K = 256).  N, K % 128 == 0, else EGTR_E_UNSUPPORTED. */
-long long egtr_linear_split_bf16_wgrad_workspace_floats(int M, int N, int K);
-int egtr_linear_split_bf16_wgrad_f32(egtr_stream_t stream, const float* g, int ldg, const float* x, int ldx,
-                                     float* grad_weight, float* workspace, int M, int N, int K);
-
-/* Up to 8 such products with the same M and K in ONE launch (their tiles share the grid): the value projection and the
- * offsets / attention-weights projection of an encoder layer, the six value projections of the decoder.  All arrays are
- * HOST arrays of num_problems entries (pointers inside are device pointers; bias[i] may be NULL).
- * A problem may add a [pos_rows[g], K] table to the rows of x_g on the way in (row % pos_rows): `hidden_states + position_embeddings` (model/deformable_detr.py:1041) as the input of the sampling-offset /
- * attention-weight projection without a materialised sum.  pos == NULL or pos[g] == NULL: none. */
-int egtr_linear_split_bf16_grouped_pos_f32(egtr_stream_t stream, int num_problems, const float* const* x, const int* ldx,
-                                           const uint16_t* const* w_tiled, const float* const* bias, float* const* y,
-                                           const int* ldy, const int* N, const int* relu, int M, int K,
-                                           const float* const* pos, const int* pos_rows);
-
-/* The same with the epilogue options of the TRAINING step (every array may be NULL = none, every entry NULL = none), applied
- * in this order to v = act(x_g W_g^T + bias_g):
+/* Up to 16 products with the same M and K in ONE launch (their tiles share the grid): the value projection and the
+ * offsets / attention-weights projection of an encoder layer, the six value projections of the decoder, the relation head's
+ * slot products.  All arrays are HOST arrays of num_problems entries (pointers inside are device pointers; bias[i] may be
+ * NULL).  A problem may add a [pos_rows[g], K] table to the rows of x_g on the way in (row % pos_rows): `hidden_states +
+ * position_embeddings` (model/deformable_detr.py:1041) as the input of the sampling-offset / attention-weight projection
+ * without a materialised sum.  pos == NULL or pos[g] == NULL: none.
+ * The epilogue options of the TRAINING step (every array may be NULL = none, every entry NULL = none) are applied in this
+ * order to v = act(x_g W_g^T + bias_g):
  *   row_keep[g] [M] bytes      rows with 0 yield zeros (value rows of padded tokens, model/deformable_detr.py:1052; in the
  *                              backward: their gradients);
  *   relu_ref[g] [M, ldref[g]]  v = relu_ref > 0 ? v : 0 -- the ReLU backward of the layer whose output relu_ref is, fused into
@@ -904,39 +904,19 @@ int egtr_linear_split_bf16_ex_f32(egtr_stream_t stream, int num_problems, const 
                                   const int* ldy, const int* N, const int* relu, int M, int K, const float* const* pos,
                                   const int* pos_rows, const unsigned char* const* row_keep, const float* const* relu_ref,
                                   const int* ldref, const float* const* add1, const float* const* add2, const int* ldadd,
-                                  float* const* colpart);
-/* egtr_linear_split_bf16_wgrad_f32 for a layer whose input was `x + pos` formed on load (x_pos [pos_rows, K], row m uses
- * x_pos[m % pos_rows]; NULL = none) and / or whose gradient rows are masked (row_keep [M] bytes, 0 = the row counts as zero;
- * NULL = none). */
+                                  float* const* colpart, int terms);
+
+/* Weight gradient of such a layer in training: grad_weight [N, K] (contiguous) = g[M, N]^T . x[M, K] (row strides ldg,
+ * ldx), same arithmetic; the M rows are cut into chunks whose 128 x 128 partial products go through `workspace`
+ * (egtr_linear_split_bf16_wgrad_workspace_floats(M, N, K, terms) floats) and are summed in a fixed order (bit-reproducible).
+ * Replaces the vendor GEMM autograd calls for model/deformable_detr.py's encoder nn.Linear layers (K = rows of the token
+ * sequence: 66 TFLOP/s in the vendor library for N = K = 256).  N, K % 128 == 0, else EGTR_E_UNSUPPORTED.
+ * The layer's input may have been `x + pos` formed on load (x_pos [pos_rows, K], row m uses x_pos[m % pos_rows]; NULL =
+ * none) and its gradient rows may be masked (row_keep [M] bytes, 0 = the row counts as zero; NULL = none). */
+long long egtr_linear_split_bf16_wgrad_workspace_floats(int M, int N, int K, int terms);
 int egtr_linear_split_bf16_wgrad_ex_f32(egtr_stream_t stream, const float* g, int ldg, const float* x, int ldx,
                                         float* grad_weight, float* workspace, int M, int N, int K, const float* x_pos,
-                                        int pos_rows, const unsigned char* row_keep);
-
-/* ---- the one-term ("bf16r") counterparts of the entries above: matmul precision "bf16" of the training routes ----------
- * Same arguments, same validation and status codes, same epilogue options in the same order, same grouping and strides; the
- * arithmetic is ONE product per element: each operand rounded once to bf16, round to nearest even (x after the on-load
- * `+ pos` / `+ x_pos`: RNE(fl32(x + pos))), every bf16 x bf16 product exact in fp32, fp32 accumulation.  Tensors stay fp32.
- * Inf and NaN survive the rounding (a non-finite element of x makes its output row -- weight gradient: its column --
- * non-finite and nothing else); a finite value beyond the largest bf16 (about 3.39e38) rounds to Inf.
- * w_tiled is the ONE-piece stream [N/128][K/32][128 rows][32] raw bfloat16 bits (ops.gemm_split_weights(w, terms=1)), written
- * by the three tiling entries; the pair forms hold [tiling of W (N K) | tiling of W^T (N K)].  K % 32 == 0, N % 128 == 0 and
- * the alignment rules of the six-term entries, else EGTR_E_UNSUPPORTED.  The weight gradient keeps the split-K chunks through
- * `workspace` (egtr_linear_bf16r_wgrad_workspace_floats(M, N, K) floats) and the fixed summation order. */
-int egtr_linear_bf16r_ex_f32(egtr_stream_t stream, int num_problems, const float* const* x, const int* ldx,
-                             const uint16_t* const* w_tiled, const float* const* bias, float* const* y, const int* ldy,
-                             const int* N, const int* relu, int M, int K, const float* const* pos, const int* pos_rows,
-                             const unsigned char* const* row_keep, const float* const* relu_ref, const int* ldref,
-                             const float* const* add1, const float* const* add2, const int* ldadd, float* const* colpart);
-long long egtr_linear_bf16r_wgrad_workspace_floats(int M, int N, int K);
-int egtr_linear_bf16r_wgrad_ex_f32(egtr_stream_t stream, const float* g, int ldg, const float* x, int ldx, float* grad_weight,
-                                   float* workspace, int M, int N, int K, const float* x_pos, int pos_rows,
-                                   const unsigned char* row_keep);
-int egtr_gemm_bf16r_tile_weights_f32(egtr_stream_t stream, const float* w, int ldw, int transposed, int N, int K,
-                                     uint16_t* w_tiled);
-int egtr_gemm_bf16r_tile_weights_pair_f32(egtr_stream_t stream, const float* w, int ldw, int N, int K, uint16_t* w_tiled_pair);
-int egtr_gemm_bf16r_tile_weights_multi_f32(egtr_stream_t stream, int num_weights, const float* const* w, const int* ldw,
-                                           const float* const* w2, const int* ldw2, const int* split_rows, const int* N,
-                                           const int* K, uint16_t* const* w_tiled_pair);
+                                        int pos_rows, const unsigned char* row_keep, int terms);
 
 /* ---- the "XS" operand format of the row-panel kernels (csrc/xs_format.h, csrc/xs_split.hip) --------------------------
  * XS(X) of a logical fp32 matrix X[rows][K] (K % 16 == 0): the exact three-way bf16 split x = hi + mid + lo, stored as

@@ -47,7 +47,7 @@ def test_library_exports_every_declared_symbol(lib_path):
     for n in _declared():
         assert hasattr(h, n), f"{n} declared in include/egtr_hip.h but not exported"
     h.egtr_abi_version.restype = ctypes.c_int
-    assert h.egtr_abi_version() == 5
+    assert h.egtr_abi_version() == 6
     h.egtr_status_string.restype = ctypes.c_char_p
     assert b"ok" == h.egtr_status_string(0)
 
@@ -62,6 +62,80 @@ def test_ctypes_binding_covers_the_header(lib_path):
     assert not set(_lib.SIGNATURES) & set(hip_test_abi.SIGNATURES)
     _lib.lib()  # resolves every symbol with its argtypes
     hip_test_abi._handle()
+
+
+_SCALARS = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "long long": ctypes.c_longlong}
+
+
+def _prototypes(header):
+    """name -> (restype, argtypes) for every prototype of include/<header>: pointers and egtr_stream_t are c_void_p (a returned
+    ``const char*`` is c_char_p), int / float / double / long long their ctypes types.  Anything else raises."""
+    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", header)).read(), flags=re.S)
+    src = re.sub(r"^\s*#.*$", "", src, flags=re.M)      # preprocessor lines
+
+    def ctype(decl, returned=False):
+        words = [w for w in decl.replace("*", " * ").split() if w != "const"]
+        if "*" in words:
+            return ctypes.c_char_p if returned and words[0] == "char" else ctypes.c_void_p
+        if not returned:
+            assert len(words) >= 2 and re.fullmatch(r"[A-Za-z_]\w*", words[-1]), f"{header}: unnamed parameter {decl!r}"
+            words = words[:-1]
+        if words == ["egtr_stream_t"]:
+            return ctypes.c_void_p
+        assert " ".join(words) in _SCALARS, f"{header}: no ctypes type for {decl!r}"
+        return _SCALARS[" ".join(words)]
+
+    out = {}
+    for ret, name, args in re.findall(r"([A-Za-z_][\w\s\*]*?)\b(egtr_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", src):
+        assert name not in out, f"{header}: {name} declared twice"
+        args = [a.strip() for a in args.split(",")] if args.strip() not in ("", "void") else []
+        out[name] = (ctype(ret.strip(), returned=True), [ctype(a) for a in args])
+    return out
+
+
+def test_ctypes_tables_equal_the_headers_prototypes(lib_path):
+    """argtypes and restype of every bound entry, as the tables state them and as the loaded functions carry them, equal what
+    the headers declare: a c_int for a long long or a float would load and then corrupt a call."""
+    from egtr_amd import _lib
+    import hip_test_abi
+    for header, table, handle in (("egtr_hip.h", _lib.SIGNATURES, _lib.lib()),
+                                  ("egtr_hip_test.h", hip_test_abi.SIGNATURES, hip_test_abi._handle())):
+        protos = _prototypes(header)
+        assert sorted(protos) == _declared((header,)), f"{header}: a prototype the parser could not read"
+        assert sorted(table) == sorted(protos)
+        for name, (restype, argtypes) in protos.items():
+            fn = getattr(handle, name)
+            assert list(table[name]) == argtypes, f"{name}: table {table[name]}, header {argtypes}"
+            assert list(fn.argtypes) == argtypes and fn.restype is restype, f"{name}: bound as {fn.restype} {fn.argtypes}"
+            if table is _lib.SIGNATURES:
+                assert _lib._RESTYPES.get(name, ctypes.c_int) is restype, f"{name}: _RESTYPES vs header {restype}"
+    assert not set(_lib._RESTYPES) - set(_lib.SIGNATURES)
+
+
+@pytest.mark.parametrize("terms", [0, 3, 7, 6, 1])
+def test_split_gemm_entries_validate_terms_without_a_gpu(lib_path, terms):
+    """``terms`` other than 6 / 1 is EGTR_E_ARG (the workspace query: 0) with otherwise plausible non-NULL arguments; 6 / 1 with a
+    NULL operand is EGTR_E_ARG as before.  Both answers come before any HIP call."""
+    from egtr_amd import _lib
+    h = _lib.lib()
+    good = terms in (6, 1)
+    # for a bad `terms` every operand is plausible, so that `terms` is the ONLY reason for EGTR_E_ARG: `p` a 16-byte aligned host
+    # address, `pa` a one-entry host array holding it (the pointer-array arguments: their entries are looked at too), `ia` a
+    # one-entry int array of 128 (row strides, N, K, pos_rows, split_rows: 128 x 128 problems).  For a valid `terms`: all NULL.
+    raw = ctypes.create_string_buffer(64 + 16)
+    addr = (ctypes.addressof(raw) + 15) & ~15
+    ptrs, ints = (ctypes.c_void_p * 1)(addr), (ctypes.c_int * 1)(128)
+    p, pa, ia = (None, None, None) if good else (addr, ctypes.addressof(ptrs), ctypes.addressof(ints))
+    E_ARG = -1
+    assert h.egtr_linear_split_bf16_ex_f32(None, 1, pa, ia, pa, pa, pa, ia, ia, ia, 128, 128, pa, ia, pa, pa, ia, pa, pa, ia, pa,
+                                           terms) == E_ARG
+    assert h.egtr_linear_split_bf16_wgrad_ex_f32(None, p, 128, p, 128, p, p, 128, 128, 128, p, 1, p, terms) == E_ARG
+    assert h.egtr_gemm_split_tile_weights_f32(None, p, 128, 0, 128, 128, p, terms) == E_ARG
+    assert h.egtr_gemm_split_tile_weights_pair_f32(None, p, 128, 128, 128, p, terms) == E_ARG
+    assert h.egtr_gemm_split_tile_weights_multi_f32(None, 1, pa, ia, pa, ia, ia, ia, ia, pa, terms) == E_ARG
+    floats = h.egtr_linear_split_bf16_wgrad_workspace_floats(128, 128, 128, terms)
+    assert (floats > 0) if good else (floats == 0)
+    assert h.egtr_linear_split_bf16_wgrad_workspace_floats(128, 128, 100, terms) == 0
 
 
 def test_null_arguments_are_rejected_without_a_gpu(lib_path):

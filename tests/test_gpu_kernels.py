@@ -1600,7 +1600,7 @@ def test_msda_geometry_function_matches_reference_composition(B, Lq, ref_dim, re
 
 @pytest.mark.parametrize("M,N,K", [(50148, 256, 256), (12537, 384, 256), (4100, 128, 1024), (33, 128, 128), (777, 256, 128)])
 def test_linear_split_bf16_wgrad_is_fp32_accurate(M, N, K):
-    """egtr_linear_split_bf16_wgrad_f32 (g^T x over the token rows, split-K with a fixed-order reduction) against float64:
+    """egtr_linear_split_bf16_wgrad_ex_f32 without its options (g^T x over the token rows, split-K with a fixed-order reduction) against float64:
     within 2.5x of the vendor fp32 GEMM's own error (+ floor), strided operands, ragged last chunk, bit-reproducible."""
     from egtr_amd import ops
     rng = W.rng_inputs(3600 + M)
@@ -1665,7 +1665,7 @@ def test_linear_grouped_layernorm_prologue(B, N):
 
 
 def test_linear_split_bf16_grouped_adds_position_rows_on_load():
-    """egtr_linear_split_bf16_grouped_pos_f32: a problem with ``pos`` multiplies (x + pos[row % pos_rows]) -- bit-identical
+    """egtr_linear_split_bf16_ex_f32 (linear_split_bf16_grouped): a problem with ``pos`` multiplies (x + pos[row % pos_rows]) -- bit-identical
     to handing it the materialised sum; the other problem of the launch is untouched."""
     from egtr_amd import ops
     rng = W.rng_inputs(654)

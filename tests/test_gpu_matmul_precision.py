@@ -495,7 +495,7 @@ def test_decoder_value_projection_node_under_the_mode_measured_against_the_round
 def test_trainer_runs_two_steps_under_the_mode(monkeypatch):
     """DataParallelTrainer(matmul_precision="bf16") on the tiny model of tests/test_gpu_robustness.py with the 320 x 416 images
     of tests/_ddp2_worker.py (2 x 2765 tokens: above the 4096 rows from which the training nodes serve the encoder): losses
-    finite, parameters updated, the one-term entries launched, the global setting "fp32" again, ops.FALLBACKS as it was."""
+    finite, parameters updated, the split-GEMM entries launched with ``terms == 1``, the global setting "fp32" again, ops.FALLBACKS as it was."""
     from egtr_amd import _lib, ops
     from egtr_amd.runtime import DataParallelTrainer, configure_optimizers
     from test_gpu_robustness import _tiny_train_setup
@@ -506,8 +506,12 @@ def test_trainer_runs_two_steps_under_the_mode(monkeypatch):
     launched = {}
     real = _lib.launch
 
-    def counting(name, *args, **kw):
-        launched[name] = launched.get(name, 0) + 1
+    with_terms = {"egtr_linear_split_bf16_ex_f32", "egtr_linear_split_bf16_wgrad_ex_f32", "egtr_gemm_split_tile_weights_f32",
+                  "egtr_gemm_split_tile_weights_pair_f32", "egtr_gemm_split_tile_weights_multi_f32"}
+
+    def counting(name, *args, **kw):     # the split-GEMM entries are keyed on (entry, terms): `terms` is their last argument
+        key = (name, args[-1]) if name in with_terms else name
+        launched[key] = launched.get(key, 0) + 1
         return real(name, *args, **kw)
 
     fallbacks = dict(ops.FALLBACKS)
@@ -523,7 +527,8 @@ def test_trainer_runs_two_steps_under_the_mode(monkeypatch):
     moved = [n for n, p in model.named_parameters() if p.requires_grad and not torch.equal(p.detach(), before[n])]
     assert any("encoder" in n and "fc1.weight" in n for n in moved) and len(moved) > 50
     assert all(torch.isfinite(p).all().item() for p in model.parameters())
-    assert launched.get("egtr_linear_bf16r_ex_f32", 0) > 0 and launched.get("egtr_linear_bf16r_wgrad_ex_f32", 0) > 0
-    assert launched.get("egtr_gemm_bf16r_tile_weights_multi_f32", 0) > 0
-    assert "egtr_linear_split_bf16_ex_f32" not in launched          # every product of the training nodes took the one-term route
+    assert launched.get(("egtr_linear_split_bf16_ex_f32", 1), 0) > 0
+    assert launched.get(("egtr_linear_split_bf16_wgrad_ex_f32", 1), 0) > 0
+    assert launched.get(("egtr_gemm_split_tile_weights_multi_f32", 1), 0) > 0
+    assert ("egtr_linear_split_bf16_ex_f32", 6) not in launched     # every product of the training nodes took the one-term route
     assert ops.FALLBACKS == fallbacks

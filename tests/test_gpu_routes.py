@@ -21,11 +21,11 @@ import route_trace  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 PRE = ["egtr_input_proj_groupnorm_flatten_f32", "egtr_level_geometry_f32"]
-SPLIT, MSDA, LIN = "egtr_linear_split_bf16_grouped_pos_f32", "egtr_msda_forward_fused_vbias_f32", "egtr_linear_f32"
+SPLIT, MSDA, LIN = "egtr_linear_split_bf16_ex_f32", "egtr_msda_forward_fused_vbias_f32", "egtr_linear_f32"
 GROUPED, GROUPED_LN = "egtr_linear_grouped_f32", "egtr_linear_grouped_ln_f32"
 LN, LN_POS, DROP_LN = "egtr_add_layernorm_f32", "egtr_add_layernorm_pos_f32", "egtr_dropout_add_layernorm_f32"
 LIN_BWD, LN_BWD, DROP_LN_BWD = "egtr_linear_backward_f32", "egtr_add_layernorm_backward_f32", "egtr_dropout_add_layernorm_backward_f32"
-COLSUM, WCOLSUM, WGRAD = "egtr_column_sum_f32", "egtr_weighted_column_sum_f32", "egtr_linear_split_bf16_wgrad_f32"
+COLSUM, WCOLSUM, WGRAD = "egtr_column_sum_f32", "egtr_weighted_column_sum_f32", "egtr_linear_split_bf16_wgrad_ex_f32"
 MSDA_BWD = ["egtr_msda_backward_det_f32", "egtr_msda_geometry_backward_f32"]
 CLUSTER = [("egtr_decoder_layer_f32", 3)]
 HEADS = [GROUPED, (LIN, 2), "egtr_box_decode_argmax_f32", SPLIT, GROUPED, "egtr_rel_head_forward_bf16x6_f32"]

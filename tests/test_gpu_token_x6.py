@@ -184,7 +184,7 @@ def _wgrad_plan(M, N, K):
     chunks = min(max(1, -(-512 // tiles)), -(-M // 32))
     rpc = -(-(-(-M // chunks)) // 32) * 32
     chunks = -(-M // rpc)
-    assert int(_lib.lib().egtr_linear_split_bf16_wgrad_workspace_floats(M, N, K)) == chunks * N * K
+    assert int(_lib.lib().egtr_linear_split_bf16_wgrad_workspace_floats(M, N, K, 6)) == chunks * N * K
     last = M - (chunks - 1) * rpc
     return chunks, rpc, -(-last // 32), (last - 1) % 32 + 1
 

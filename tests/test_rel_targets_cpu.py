@@ -191,4 +191,4 @@ def test_new_entries_resolve_and_reject_null_arguments():
     assert h.egtr_pack_relations_u64(None, None, None, 2, 3, 7, 5, None) == -1
     assert h.egtr_relation_loss_bits_f32(None, None, None, None, None, None, None, None, 2, 7, 5, 1.0, 80, 80, None, None,
                                          None, None) == -1
-    assert h.egtr_abi_version() == 5
+    assert h.egtr_abi_version() == 6
