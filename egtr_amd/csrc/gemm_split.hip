@@ -295,13 +295,7 @@ static_assert(kR1StageK == 32 || kR1StageK == 64 || kR1StageK == 128, "stage dep
 static_assert(kR1StageM == 32 || kR1StageM == 64, "stage depth");
 constexpr int kR1WBlockBytes = 2 * kBN * 32;
 
-// two fp32 -> one dword of two bf16, round to nearest even (v_cvt_pk_bf16_f32); a in the low half (the lower address)
-__device__ __forceinline__ unsigned cvt_pk_bf16_rne(float a, float b) {
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
-  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-  const f32x2 v = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
+using xs::cvt_pk_bf16_rne;   // two fp32 -> one dword of two bf16, round to nearest even (xs_format.h; rel_head.hip shares it)
 // one stage out of LDS: BK / 16 k-steps x (1 + NT) 16-byte reads and one product per 32-column tile of the wave
 template <int NT, int BK>
 __device__ __forceinline__ void stage_product1(const __bf16* pa, const __bf16* pw, f32x16 (&acc)[NT]) {

@@ -662,9 +662,36 @@ struct PrefetchX6 {
   }
 };
 
+// The one-piece form (TERMS = 1 below): one KiB and one product per step, the same counted waits
+template <int PRE>
+struct PrefetchX1 {
+  template <int I>
+  static __device__ __forceinline__ void issue(f32x4v (&wq)[PRE][1], unsigned voff, const char* wtile) {
+    wq[I][0] = gload_b128_s(voff, wtile + I * 1024);
+    if constexpr (I + 1 < PRE) issue<I + 1>(wq, voff, wtile);
+  }
+  template <int S>
+  static __device__ __forceinline__ void run(f32x4v (&wq)[PRE][1], unsigned voff, const char* wtile,
+                                             const __bf16* hrow, f32x16& acc) {
+    constexpr int newer = (15 - S) < (PRE - 1) ? (15 - S) : (PRE - 1);  // own loads issued after this step's
+    vm_wait<newer>(wq[S % PRE][0]);
+    const bf16x8 w = __builtin_bit_cast(bf16x8, wq[S % PRE][0]);
+    const bf16x8 h = *reinterpret_cast<const bf16x8*>(hrow + 16 * S);
+    acc = mfma_bf16(w, h, acc);
+    if constexpr (S + PRE < 16) wq[S % PRE][0] = gload_b128_s(voff, wtile + (S + PRE) * 1024);
+    if constexpr (S + 1 < 16) run<S + 1>(wq, voff, wtile, hrow, acc);
+  }
+};
+
 // SAVE (training forward): the post-ReLU activations of layers 1 and 2 go to h1_save / h2_save [2 (mlp)][B N N][256] as in
 // rel_head_fwd_f32 -- the backward's GEMMs read them (ops.RelationHeadFunction).
-template <int T, int OT, bool SAVE = false>
+// TERMS = 1 (matmul precision "bf16" of the training forward, ops.set_matmul_precision / DESIGN.md 4.12b): layers 2 and 3 multiply
+// operands rounded ONCE to bf16, round to nearest even -- the post-ReLU activations by v_cvt_pk_bf16_f32 (xs::cvt_pk_bf16_rne, as
+// in gemm_bf16r_f32), the weights by the one-piece streams w2x [8 nt][16 t][64 lane][8] / w3x [8 nt][2 kb][OT][64 lane][8]
+// (egtr_rel_head_streams_bf16r_f32) -- one product per k-step, fp32 accumulation.  Layer 1, the connectivity output layer, the
+// biases, the frequency bias, gate_mean and the saves (the fp32 values BEFORE the rounding) are those of TERMS = 6; so is every
+// barrier and wait.
+template <int T, int OT, bool SAVE = false, int TERMS = 6>
 __global__ __launch_bounds__(64 * kRhWaves) __attribute__((amdgpu_waves_per_eu(2, 2))) void rel_head_fwd_x6(
     const float* __restrict__ gate_q, const float* __restrict__ gate_k, const float* __restrict__ uq,
     const float* __restrict__ uk, const float* __restrict__ b1, const unsigned short* __restrict__ w2xr,
@@ -674,10 +701,12 @@ __global__ __launch_bounds__(64 * kRhWaves) __attribute__((amdgpu_waves_per_eu(2
     int N, int R, int C1, float* __restrict__ rel_logits, float* __restrict__ conn_logits,
     float* __restrict__ gate_mean, int apply_sigmoid, float* __restrict__ h1_save, float* __restrict__ h2_save) {
   // apply_sigmoid: write sigmoid(logit) (egtr.py:450-454, the model's pred_rel / pred_connectivity) instead of the logit
-  // one buffer, two lives: the three h1 pieces (read by every layer-2 step), then the output tiles
+  // one buffer, two lives: the three h1 pieces (TERMS = 1: the one) (read by every layer-2 step), then the output tiles
+  static_assert(TERMS == 6 || TERMS == 1, "six exact cross terms or one product of rounded operands");
+  constexpr int kPieces = TERMS == 6 ? 3 : 1;
   constexpr int kStride = 32 * OT + 1;
-  static_assert(kRhWaves * 32 * kStride * 4 <= 3 * 32 * kHp * 2, "output tiles fit in the h1 buffer");
-  __shared__ __attribute__((aligned(16))) __bf16 s_h[3 * 32 * kHp];
+  static_assert(kRhWaves * 32 * kStride * 4 <= kPieces * 32 * kHp * 2, "output tiles fit in the h1 buffer");
+  __shared__ __attribute__((aligned(16))) __bf16 s_h[kPieces * 32 * kHp];
   float* const s_out = reinterpret_cast<float*>(s_h);
   __shared__ int s_tb[32];
   __shared__ long long s_pp[32];
@@ -770,12 +799,18 @@ __global__ __launch_bounds__(64 * kRhWaves) __attribute__((amdgpu_waves_per_eu(2
           reinterpret_cast<float4*>(h1_save + ((size_t)mlp * total +
                                                (size_t)(((long long)b * N + i0 + ii) * N + j0 + jj)) * kHd)[lane] =
               make_float4(egtr_relu(a01.x), egtr_relu(a01.y), egtr_relu(a23.x), egtr_relu(a23.y));
-        const Split3 sx = xs::split3_fast(egtr_relu(a01.x)), sy = xs::split3_fast(egtr_relu(a01.y)),
-                     sz = xs::split3_fast(egtr_relu(a23.x)), sw = xs::split3_fast(egtr_relu(a23.y));
-        __bf16* hp = s_h + pp * kHp + 4 * lane;
-        *reinterpret_cast<uint2*>(hp) = make_uint2(pack_hi16(sx.hi, sy.hi), pack_hi16(sz.hi, sw.hi));
-        *reinterpret_cast<uint2*>(hp + 32 * kHp) = make_uint2(pack_hi16(sx.mid, sy.mid), pack_hi16(sz.mid, sw.mid));
-        *reinterpret_cast<uint2*>(hp + 64 * kHp) = make_uint2(pack_hi16(sx.lo, sy.lo), pack_hi16(sz.lo, sw.lo));
+        if constexpr (TERMS == 1) {   // rounded once, one piece
+          *reinterpret_cast<uint2*>(s_h + pp * kHp + 4 * lane) =
+              make_uint2(xs::cvt_pk_bf16_rne(egtr_relu(a01.x), egtr_relu(a01.y)),
+                         xs::cvt_pk_bf16_rne(egtr_relu(a23.x), egtr_relu(a23.y)));
+        } else {
+          const Split3 sx = xs::split3_fast(egtr_relu(a01.x)), sy = xs::split3_fast(egtr_relu(a01.y)),
+                       sz = xs::split3_fast(egtr_relu(a23.x)), sw = xs::split3_fast(egtr_relu(a23.y));
+          __bf16* hp = s_h + pp * kHp + 4 * lane;
+          *reinterpret_cast<uint2*>(hp) = make_uint2(pack_hi16(sx.hi, sy.hi), pack_hi16(sz.hi, sw.hi));
+          *reinterpret_cast<uint2*>(hp + 32 * kHp) = make_uint2(pack_hi16(sx.mid, sy.mid), pack_hi16(sz.mid, sw.mid));
+          *reinterpret_cast<uint2*>(hp + 64 * kHp) = make_uint2(pack_hi16(sx.lo, sy.lo), pack_hi16(sz.lo, sw.lo));
+        }
       }
     }
     __syncthreads();   // both waves' rows are in LDS
@@ -796,7 +831,7 @@ __global__ __launch_bounds__(64 * kRhWaves) __attribute__((amdgpu_waves_per_eu(2
 #pragma unroll 1
   for (int nt = wv * kNtPerWave; nt < (wv + 1) * kNtPerWave; ++nt) {
     // ---- layer 2: h2^T[n][pair], n = 32 nt + (r&3) + 8 (r>>2) + 4 hf ---------------------------------------
-    f32x16 acc, accc;
+    f32x16 acc, accc;   // (TERMS = 1: accc is never read)
 #pragma unroll
     for (int r = 0; r < 16; ++r) accc[r] = 0.f;
     // the main accumulator starts from the layer-2 bias (requested before the weight loads, not behind the loop): register
@@ -806,26 +841,38 @@ __global__ __launch_bounds__(64 * kRhWaves) __attribute__((amdgpu_waves_per_eu(2
       const float4 bb = *reinterpret_cast<const float4*>(b2 + nt * 32 + 8 * rq + 4 * hf);
       acc[4 * rq + 0] = bb.x; acc[4 * rq + 1] = bb.y; acc[4 * rq + 2] = bb.z; acc[4 * rq + 3] = bb.w;
     }
-    const char* wtile = w2x + (size_t)nt * (16 * 3072);
+    constexpr int kFrag = kPieces * 1024;   // bytes of one operand fragment: its pieces are consecutive KiB
+    const char* wtile = w2x + (size_t)nt * (16 * kFrag);
+    // steps of W2 loads in flight.  (One piece: 4, 8 and all 16 steps measured 563 / 561 / 562 us at B = 4, N = 200 -- the
+    // training form is bound by its 655 MB of activation stores, profiles/matmul_precision_rel_head_ab.txt)
     constexpr int kPre = 4;
-    f32x4v wq[kPre][3];
+    f32x4v wq[kPre][kPieces];
     // relation MLP: the 12 W3 operand fragments of this n tile are requested BEFORE the layer-2 loop (asm loads, oldest in the
     // in-order queue: the loop's own counted waits cover them).  Loaded at their use they were twelve exposed L2 round trips
     // per n tile -- about as long as the tile's MFMAs.
-    f32x4v w3q[2 * OT][3];
+    f32x4v w3q[2 * OT][kPieces];
     if (mlp == 0) {
-      const char* w3t = reinterpret_cast<const char*>(w3xr) + (size_t)nt * (2 * OT * 3072);
+      const char* w3t = reinterpret_cast<const char*>(w3xr) + (size_t)nt * (2 * OT * kFrag);
 #pragma unroll
       for (int f = 0; f < 2 * OT; ++f) {
-        w3q[f][0] = gload_b128_s(voff, w3t + f * 3072);
-        w3q[f][1] = gload_b128_s1k(voff, w3t + f * 3072);
-        w3q[f][2] = gload_b128_s2k(voff, w3t + f * 3072);
+        w3q[f][0] = gload_b128_s(voff, w3t + f * kFrag);
+        if constexpr (TERMS == 6) {
+          w3q[f][1] = gload_b128_s1k(voff, w3t + f * kFrag);
+          w3q[f][2] = gload_b128_s2k(voff, w3t + f * kFrag);
+        }
       }
     }
-    PrefetchX6<kPre>::template issue<0>(wq, voff, wtile);
-    PrefetchX6<kPre>::template run<0>(wq, voff, wtile, hrow, acc, accc);
+    if constexpr (TERMS == 1) {
+      PrefetchX1<kPre>::template issue<0>(wq, voff, wtile);
+      PrefetchX1<kPre>::template run<0>(wq, voff, wtile, hrow, acc);
 #pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = egtr_relu(acc[r] + accc[r]);
+      for (int r = 0; r < 16; ++r) acc[r] = egtr_relu(acc[r]);
+    } else {
+      PrefetchX6<kPre>::template issue<0>(wq, voff, wtile);
+      PrefetchX6<kPre>::template run<0>(wq, voff, wtile, hrow, acc, accc);
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[r] = egtr_relu(acc[r] + accc[r]);
+    }
     if (SAVE) {
       float* stg = s_h2 + wv * (8 * kH2Pitch);
 #pragma unroll
@@ -852,10 +899,21 @@ __global__ __launch_bounds__(64 * kRhWaves) __attribute__((amdgpu_waves_per_eu(2
       // ---- layer 3 (relation): two K = 16 steps per n tile on the split accumulators; W3 pieces pre-ordered ----------
 #pragma unroll
       for (int f = 0; f < 2 * OT; ++f) {   // the layer-2 loop ended on vmcnt(0): everything has landed
-        asm volatile("" : "+v"(w3q[f][0]), "+v"(w3q[f][1]), "+v"(w3q[f][2]));
+        if constexpr (TERMS == 1) asm volatile("" : "+v"(w3q[f][0]));
+        else asm volatile("" : "+v"(w3q[f][0]), "+v"(w3q[f][1]), "+v"(w3q[f][2]));
       }
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb) {
+        if constexpr (TERMS == 1) {   // the fp32 hidden-2 values (bias and ReLU applied) rounded once, one product per tile
+          const bf16x8 h = __builtin_bit_cast(
+              bf16x8, make_uint4(xs::cvt_pk_bf16_rne(acc[8 * kb + 0], acc[8 * kb + 1]),
+                                 xs::cvt_pk_bf16_rne(acc[8 * kb + 2], acc[8 * kb + 3]),
+                                 xs::cvt_pk_bf16_rne(acc[8 * kb + 4], acc[8 * kb + 5]),
+                                 xs::cvt_pk_bf16_rne(acc[8 * kb + 6], acc[8 * kb + 7])));
+#pragma unroll
+          for (int ot = 0; ot < OT; ++ot)
+            racc[ot] = mfma_bf16(__builtin_bit_cast(bf16x8, w3q[kb * OT + ot][0]), h, racc[ot]);
+        } else {
         uint4 phi, pmid, plo;
         {
           Split3 sp[8];
@@ -882,6 +940,7 @@ __global__ __launch_bounds__(64 * kRhWaves) __attribute__((amdgpu_waves_per_eu(2
           racc[ot] = mfma_bf16(wmid, hhi, racc[ot]);
           racc[ot] = mfma_bf16(whi, hhi, racc[ot]);
         }
+        }   // TERMS == 6
       }
     } else {
 #pragma unroll
@@ -1269,11 +1328,48 @@ extern "C" int egtr_rel_head_forward_bf16x6_save_f32(egtr_stream_t stream, const
   return egtr_check_launch();
 }
 
+// The training forward under matmul precision "bf16": rel_head_fwd_x6<., ., true, 1> on the one-piece streams of
+// egtr_rel_head_streams_bf16r_f32.  The same arguments, checks and grid as the entry above.
+extern "C" int egtr_rel_head_forward_bf16r_save_f32(egtr_stream_t stream, const float* gate_q, const float* gate_k,
+                                                    const float* uq, const float* uk, const float* b1,
+                                                    const uint16_t* w2x_rel, const float* b2r, const uint16_t* w3x_rel,
+                                                    const float* b3r, const uint16_t* w2x_conn, const float* b2c,
+                                                    const float* w3c, const float* b3c, const float* triplet_dist,
+                                                    const int64_t* node_cls, int batch, int num_query, int num_slots,
+                                                    int hidden, int num_rel, int num_cls_plus1, float* rel_logits,
+                                                    float* conn_logits, float* gate_mean, float* h1_save,
+                                                    float* h2_save) {
+  if (!gate_q || !gate_k || !uq || !uk || !b1 || !w2x_rel || !b2r || !w3x_rel || !b3r || !w2x_conn || !b2c || !w3c ||
+      !b3c || !rel_logits || !conn_logits || !h1_save || !h2_save)
+    return EGTR_E_ARG;
+  if (triplet_dist != nullptr && node_cls == nullptr) return EGTR_E_ARG;
+  if (batch <= 0 || num_query <= 0 || num_rel <= 0) return EGTR_E_ARG;
+  if (hidden != kHd || num_rel > 64 || (num_slots != 4 && num_slots != 7)) return EGTR_E_UNSUPPORTED;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const long long tiles = (long long)batch * ((num_query + 7) / 8) * ((num_query + 3) / 4);
+  if (tiles >= (1ll << 31)) return EGTR_E_UNSUPPORTED;
+  const dim3 grid((unsigned)tiles, 2);
+#define EGTR_TXR(TT, OTT)                                                                                               \
+  hipLaunchKernelGGL((rel_head_fwd_x6<TT, OTT, true, 1>), grid, dim3(64 * kRhWaves), 0, st, gate_q, gate_k, uq, uk, b1,  \
+                     w2x_rel, b2r, w3x_rel, b3r, w2x_conn, b2c, w3c, b3c, triplet_dist, node_cls, batch, num_query,      \
+                     num_rel, num_cls_plus1, rel_logits, conn_logits, gate_mean, 0, h1_save, h2_save)
+  if (num_slots == 4) {
+    if (num_rel <= 32) EGTR_TXR(4, 1); else EGTR_TXR(4, 2);
+  } else {
+    if (num_rel <= 32) EGTR_TXR(7, 1); else EGTR_TXR(7, 2);
+  }
+#undef EGTR_TXR
+  return egtr_check_launch();
+}
+
 // The operand streams of rel_head_fwd_x6 from the fp32 weights in ONE launch (training rebuilds them every step):
 //   w2x [8 nt][16 t][3 piece][2 hf][32 pi][8 e]      = piece of W2[32 nt + pi][16 t + 8 hf + e]          (both MLPs)
 //   w3x [8 nt][2 kb][OT][3 piece][2 hf][32 pi][8 e]  = piece of W3[32 ot + pi][32 nt + 16 kb + (e & 3) + 8 (e >> 2) + 4 hf]
 // (rows of W3 beyond num_rel are zero), pieces rounded to nearest (hi + mid + lo == w to fp32 precision).
+// PIECES = 1 (the streams of TERMS = 1): the same order without the piece dimension, every element rounded ONCE to nearest even
+// (xs::bf16_rne_bits, bit-equal to torch's float -> bfloat16 cast: an Inf or a NaN stays in its element).
 namespace {
+template <int PIECES>
 __global__ __launch_bounds__(256) void rel_head_streams_f32(const float* __restrict__ w2r, const float* __restrict__ w2c,
                                                             const float* __restrict__ w3r, int R, int OT,
                                                             unsigned short* __restrict__ w2xr,
@@ -1285,22 +1381,30 @@ __global__ __launch_bounds__(256) void rel_head_streams_f32(const float* __restr
       const int which = i / n2, j = i - which * n2;        // j walks the DESTINATION order without the piece index
       const int e = j & 7, pi = (j >> 3) & 31, hf = (j >> 8) & 1, t = (j >> 9) & 15, nt = j >> 13;
       const float w = (which ? w2c : w2r)[(32 * nt + pi) * kHd + 16 * t + 8 * hf + e];
-      const xs::Split3 sp = xs::split3_rne(w);
-      unsigned short* d = (which ? w2xc : w2xr) + (size_t)((nt * 16 + t) * 3) * 512 + (hf * 32 + pi) * 8 + e;
-      d[0] = (unsigned short)(sp.hi >> 16);
-      d[512] = (unsigned short)(sp.mid >> 16);
-      d[1024] = (unsigned short)(sp.lo >> 16);
+      unsigned short* d = (which ? w2xc : w2xr) + (size_t)((nt * 16 + t) * PIECES) * 512 + (hf * 32 + pi) * 8 + e;
+      if constexpr (PIECES == 1) {
+        d[0] = (unsigned short)(xs::bf16_rne_bits(w) >> 16);
+      } else {
+        const xs::Split3 sp = xs::split3_rne(w);
+        d[0] = (unsigned short)(sp.hi >> 16);
+        d[512] = (unsigned short)(sp.mid >> 16);
+        d[1024] = (unsigned short)(sp.lo >> 16);
+      }
     } else {
       const int j = i - 2 * n2;
       const int e = j & 7, pi = (j >> 3) & 31, hf = (j >> 8) & 1;
       const int rest = j >> 9, ot = rest % OT, kb = (rest / OT) & 1, nt = rest / (2 * OT);
       const int row = 32 * ot + pi, col = 32 * nt + 16 * kb + (e & 3) + 8 * (e >> 2) + 4 * hf;
       const float w = row < R ? w3r[row * kHd + col] : 0.f;
-      const xs::Split3 sp = xs::split3_rne(w);
-      unsigned short* d = w3x + (size_t)(((nt * 2 + kb) * OT + ot) * 3) * 512 + (hf * 32 + pi) * 8 + e;
-      d[0] = (unsigned short)(sp.hi >> 16);
-      d[512] = (unsigned short)(sp.mid >> 16);
-      d[1024] = (unsigned short)(sp.lo >> 16);
+      unsigned short* d = w3x + (size_t)(((nt * 2 + kb) * OT + ot) * PIECES) * 512 + (hf * 32 + pi) * 8 + e;
+      if constexpr (PIECES == 1) {
+        d[0] = (unsigned short)(xs::bf16_rne_bits(w) >> 16);
+      } else {
+        const xs::Split3 sp = xs::split3_rne(w);
+        d[0] = (unsigned short)(sp.hi >> 16);
+        d[512] = (unsigned short)(sp.mid >> 16);
+        d[1024] = (unsigned short)(sp.lo >> 16);
+      }
     }
   }
 }
@@ -1312,7 +1416,18 @@ extern "C" int egtr_rel_head_streams_f32(egtr_stream_t stream, const float* w2_r
   if (!w2_rel || !w2_conn || !w3_rel || !w2x_rel || !w2x_conn || !w3x_rel || num_rel <= 0) return EGTR_E_ARG;
   if (hidden != kHd || num_rel > 64) return EGTR_E_UNSUPPORTED;
   const int OT = num_rel <= 32 ? 1 : 2;
-  hipLaunchKernelGGL(rel_head_streams_f32, dim3(256), dim3(256), 0, static_cast<hipStream_t>(stream), w2_rel, w2_conn,
+  hipLaunchKernelGGL(rel_head_streams_f32<3>, dim3(256), dim3(256), 0, static_cast<hipStream_t>(stream), w2_rel, w2_conn,
+                     w3_rel, num_rel, OT, w2x_rel, w2x_conn, w3x_rel);
+  return egtr_check_launch();
+}
+
+extern "C" int egtr_rel_head_streams_bf16r_f32(egtr_stream_t stream, const float* w2_rel, const float* w2_conn,
+                                               const float* w3_rel, int hidden, int num_rel, uint16_t* w2x_rel,
+                                               uint16_t* w2x_conn, uint16_t* w3x_rel) {
+  if (!w2_rel || !w2_conn || !w3_rel || !w2x_rel || !w2x_conn || !w3x_rel || num_rel <= 0) return EGTR_E_ARG;
+  if (hidden != kHd || num_rel > 64) return EGTR_E_UNSUPPORTED;
+  const int OT = num_rel <= 32 ? 1 : 2;
+  hipLaunchKernelGGL(rel_head_streams_f32<1>, dim3(256), dim3(256), 0, static_cast<hipStream_t>(stream), w2_rel, w2_conn,
                      w3_rel, num_rel, OT, w2x_rel, w2x_conn, w3x_rel);
   return egtr_check_launch();
 }

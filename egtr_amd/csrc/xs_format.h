@@ -78,6 +78,16 @@ __device__ __forceinline__ Split3 split3_rne(float x) {
   return s;
 }
 
+// two fp32 -> one dword of two bf16, round to nearest even (v_cvt_pk_bf16_f32); a in the low half (the lower address).  The
+// one-term kernels round their ACTIVATIONS with it (gemm_split.hip, rel_head.hip): Inf and NaN survive, a finite value beyond
+// the largest bf16 (3.39e38) rounds to Inf.
+__device__ __forceinline__ unsigned cvt_pk_bf16_rne(float a, float b) {
+  typedef float f32x2 __attribute__((ext_vector_type(2)));
+  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+  const f32x2 v = {a, b};
+  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
+}
+
 // (a, b) -> one dword holding the upper halves: a in the low 16 bits (the element at the lower address)
 __device__ __forceinline__ unsigned pack_hi16(unsigned a, unsigned b) { return __builtin_amdgcn_perm(b, a, 0x07060302u); }
 

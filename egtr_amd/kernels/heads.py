@@ -8,22 +8,34 @@ from .. import _lib
 from .._lib import _chk
 from .linear import _split3_bf16
 
-__all__ = ["rel_head_split_weights", "rel_head_streams", "relation_head_split_bf16", "hungarian_match",
+__all__ = ["rel_head_split_weights", "rel_head_streams", "relation_head_split_bf16", "relation_head_train_forward", "hungarian_match",
            "pack_detection_targets", "pack_relation_bits", "relation_loss_launch"]
 
 
-def rel_head_split_weights(w2r, w3r, w2c):
+def _rel_head_pieces(w, terms):
+    """[pieces, ...] bf16: the three-way split (terms=6) or the one rounding to nearest even (terms=1) of an fp32 weight"""
+    if terms not in (1, 6):
+        raise ValueError(f"terms must be 6 (split-bf16, fp32 accuracy) or 1 (operands rounded to bf16), got {terms!r}")
+    return _split3_bf16(w) if terms == 6 else w.detach().float().to(torch.bfloat16).unsqueeze(0)
+
+
+def rel_head_split_weights(w2r, w3r, w2c, terms=6):
     """The MFMA operand streams of rel_head_fwd_x6 (layouts documented in csrc/rel_head.hip):
-    w2x [8 nt][16 t][3 piece][64 lane][8] per MLP, w3x [8 nt][2 kb][OT][3 piece][64 lane][8] (relation MLP)."""
+    w2x [8 nt][16 t][3 piece][64 lane][8] per MLP, w3x [8 nt][2 kb][OT][3 piece][64 lane][8] (relation MLP).
+    ``terms=1``: the one-piece streams of the one-term training forward, the same order without the piece dimension --
+    w2x [8 nt][16 t][64 lane][8], w3x [8 nt][2 kb][OT][64 lane][8], every element ``weight.to(torch.bfloat16)``."""
+    pieces = _rel_head_pieces(w2r, terms).shape[0]
+
     def w2x(w2):
-        p = _split3_bf16(w2).view(3, 8, 32, 16, 2, 8)         # [piece, nt, pi, t, hf, e]
-        return p.permute(1, 3, 0, 4, 2, 5).contiguous()        # [nt, t, piece, hf, pi, e]; lane = 32 hf + pi
+        p = _rel_head_pieces(w2, terms).view(pieces, 8, 32, 16, 2, 8)   # [piece, nt, pi, t, hf, e]
+        p = p.permute(1, 3, 0, 4, 2, 5).contiguous()           # [nt, t, piece, hf, pi, e]; lane = 32 hf + pi
+        return p if terms == 6 else p.squeeze(2)
 
     R = w3r.shape[0]
     OT = 1 if R <= 32 else 2
     w3p = torch.zeros(32 * OT, w3r.shape[1], dtype=torch.float32, device=w3r.device)
     w3p[:R] = w3r.detach().float()
-    q = _split3_bf16(w3p).view(3, OT, 32, w3r.shape[1])       # [piece, ot, pi, n]
+    q = _rel_head_pieces(w3p, terms).view(pieces, OT, 32, w3r.shape[1])   # [piece, ot, pi, n]
     dev = w3r.device
     nt = torch.arange(8, device=dev).view(8, 1, 1, 1)
     kb = torch.arange(2, device=dev).view(1, 2, 1, 1)
@@ -32,23 +44,72 @@ def rel_head_split_weights(w2r, w3r, w2c):
     nidx = 32 * nt + 16 * kb + (e & 3) + 8 * (e >> 2) + 4 * hf  # [nt, kb, hf, e]
     g = q[:, :, :, nidx]                                        # [piece, ot, pi, nt, kb, hf, e]
     w3x = g.permute(3, 4, 1, 0, 5, 2, 6).contiguous()           # [nt, kb, ot, piece, hf, pi, e]
+    if terms == 1:
+        w3x = w3x.squeeze(3)
     return w2x(w2r), w3x, w2x(w2c)
 
 
-def rel_head_streams(w2r, w3r, w2c):
-    """``rel_head_split_weights`` as ONE launch (egtr_rel_head_streams_f32): the same three streams, bit for bit; what the
-    training forward rebuilds after every optimizer step."""
+def rel_head_streams(w2r, w3r, w2c, terms=6):
+    """``rel_head_split_weights`` as ONE launch (egtr_rel_head_streams_f32; ``terms=1``: egtr_rel_head_streams_bf16r_f32): the
+    same three streams, bit for bit; what the training forward rebuilds after every optimizer step."""
+    if terms not in (1, 6):
+        raise ValueError(f"terms must be 6 (split-bf16, fp32 accuracy) or 1 (operands rounded to bf16), got {terms!r}")
     w2r_, w3r_, w2c_ = (_chk(t.detach().contiguous(), n, torch.float32)
                         for t, n in ((w2r, "w2r"), (w3r, "w3r"), (w2c, "w2c")))
     R = w3r_.shape[0]
     OT = 1 if R <= 32 else 2
     dev = w2r_.device
-    w2xr = torch.empty(8, 16, 3, 2, 32, 8, dtype=torch.bfloat16, device=dev)
-    w2xc = torch.empty(8, 16, 3, 2, 32, 8, dtype=torch.bfloat16, device=dev)
-    w3x = torch.empty(8, 2, OT, 3, 2, 32, 8, dtype=torch.bfloat16, device=dev)
-    _lib.launch("egtr_rel_head_streams_f32", w2r_.data_ptr(), w2c_.data_ptr(), w3r_.data_ptr(), w2r_.shape[1], R,
-                w2xr.data_ptr(), w2xc.data_ptr(), w3x.data_ptr())
+    pc = (3,) if terms == 6 else ()
+    w2xr = torch.empty(8, 16, *pc, 2, 32, 8, dtype=torch.bfloat16, device=dev)
+    w2xc = torch.empty(8, 16, *pc, 2, 32, 8, dtype=torch.bfloat16, device=dev)
+    w3x = torch.empty(8, 2, OT, *pc, 2, 32, 8, dtype=torch.bfloat16, device=dev)
+    _lib.launch("egtr_rel_head_streams_f32" if terms == 6 else "egtr_rel_head_streams_bf16r_f32", w2r_.data_ptr(),
+                w2c_.data_ptr(), w3r_.data_ptr(), w2r_.shape[1], R, w2xr.data_ptr(), w2xc.data_ptr(), w3x.data_ptr())
     return w2xr, w3x, w2xc
+
+
+def relation_head_train_forward(gate_q, gate_k, uq, uk, b1, w2r, b2r, w3r, b3r, w2c, b2c, w3c, b3c, triplet_dist, node_cls,
+                                want_gate_mean, terms, streams=None):
+    """Training forward of the relation head with layers 2 and 3 on the bf16 matrix cores: ``terms=6`` the six-term split
+    product, fp32 to the last bit (egtr_rel_head_forward_bf16x6_save_f32); ``terms=1`` one product per element, activations and
+    weights rounded once to bf16 (egtr_rel_head_forward_bf16r_save_f32).  Contiguous fp32 device tensors, hidden = 256,
+    num_rel <= 64, 4 or 7 slots (the entries answer EGTR_E_UNSUPPORTED otherwise: a RuntimeError here).  The weight streams are
+    rebuilt by one launch (``rel_head_streams``) unless ``streams`` = (w2x_rel, w3x_rel, w2x_conn) of the same ``terms`` is
+    given.  Returns (rel [B, N, N, R], conn [B, N, N], gate_mean [T] or None, h1s, h2s [2, B N N, 256]: the fp32 post-ReLU
+    activations of both layers and both MLPs).  No autograd, reads no switch."""
+    tens = [_chk(t, n, torch.float32) for t, n in zip(
+        (gate_q, gate_k, uq, uk, b1, w2r, b2r, w3r, b3r, w2c, b2c, w3c, b3c),
+        ("gate_q", "gate_k", "uq", "uk", "b1", "w2r", "b2r", "w3r", "b3r", "w2c", "b2c", "w3c", "b3c"))]
+    gq_, gk_, uq_, uk_, b1_, w2r_, b2r_, w3r_, b3r_, w2c_, b2c_, w3c_, b3c_ = tens
+    B, N, T = gq_.shape
+    Hd, R = w2r_.shape[1], w3r_.shape[0]
+    dev = gq_.device
+    w2xr, w3x, w2xc = rel_head_streams(w2r_, w3r_, w2c_, terms=terms) if streams is None else streams
+    if streams is not None:
+        pc = (3,) if terms == 6 else ()
+        OT = 1 if R <= 32 else 2
+        for t, n, shape in ((w2xr, "w2x_rel", (8, 16, *pc, 2, 32, 8)), (w2xc, "w2x_conn", (8, 16, *pc, 2, 32, 8)),
+                            (w3x, "w3x_rel", (8, 2, OT, *pc, 2, 32, 8))):
+            _chk(t, n, torch.bfloat16)
+            if tuple(t.shape) != shape:
+                raise RuntimeError(f"{n} must have shape {shape} for terms={terms}, got {tuple(t.shape)}")
+    c1 = 0
+    if triplet_dist is not None:
+        _chk(triplet_dist, "triplet_dist", torch.float32)
+        _chk(node_cls, "node_cls", torch.int64)
+        c1 = triplet_dist.shape[0]
+    rel = torch.empty(B, N, N, R, dtype=torch.float32, device=dev)
+    conn = torch.empty(B, N, N, dtype=torch.float32, device=dev)
+    gm = torch.zeros(T, dtype=torch.float32, device=dev) if want_gate_mean else None
+    h1s = torch.empty(2, B * N * N, Hd, dtype=torch.float32, device=dev)
+    h2s = torch.empty(2, B * N * N, Hd, dtype=torch.float32, device=dev)
+    _lib.launch("egtr_rel_head_forward_bf16x6_save_f32" if terms == 6 else "egtr_rel_head_forward_bf16r_save_f32",
+                gq_.data_ptr(), gk_.data_ptr(), uq_.data_ptr(), uk_.data_ptr(),
+                b1_.data_ptr(), w2xr.data_ptr(), b2r_.data_ptr(), w3x.data_ptr(), b3r_.data_ptr(), w2xc.data_ptr(),
+                b2c_.data_ptr(), w3c_.data_ptr(), b3c_.data_ptr(), _lib.ptr(triplet_dist),
+                _lib.ptr(node_cls if triplet_dist is not None else None), B, N, T, Hd, R, c1, rel.data_ptr(),
+                conn.data_ptr(), _lib.ptr(gm), h1s.data_ptr(), h2s.data_ptr())
+    return rel, conn, gm, h1s, h2s
 
 
 def relation_head_split_bf16(gate_q, gate_k, uq, uk, b1, w2x_rel, b2r, w3x_rel, b3r, w2x_conn, b2c, w3c, b3c,

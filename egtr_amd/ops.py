@@ -939,10 +939,14 @@ class deterministic:
 # (csrc/gemm_split.hip, `terms` = 1 of its entries).  Accumulation, the tensors in memory, master weights, gradients and the
 # optimizer stay fp32; bf16 has fp32's exponent range, so there is no loss scaling.  Consulted AT CALL TIME in a Function's
 # forward and kept on its ctx for the backward (a route switch, not a fall-off: nothing is counted in FALLBACKS).
+# RelationHeadFunction is covered where its split-bf16 training forward runs (4 or 7 slots, num_rel <= 64, hidden 256): layer 2
+# of both MLPs (W2 h1) and layer 3 of the relation MLP (W3 h2) round their operands in the one-term form of rel_head_fwd_x6, and
+# in the backward dh1 = dh2 W2 (with its ReLU mask and the b1 column sums: one `ex` launch per MLP) and dW2 = dh2^T h1 do.  NOT
+# rounded there: layer 1, the connectivity output layer w3c h2, the layer-3 gradients G W3 and G^T h2 (K or N = num_rel); the
+# saved h1 / h2 stay fp32.  Any other relation-head call keeps the exact-f32 kernel and backward under either mode.
 # Not covered: every inference route (module_linear, ffn_fused, the grouped projections, the relation head, the backbone) keeps
-# its bits -- a user who wants bf16 inference has the bf16 model; the relation head's training kernels (rel_head_fwd_x6 and its
-# aten::mm backward), MSDA, LayerNorm, the losses and the matcher; shapes the split kernels do not serve still take the vendor
-# GEMM in fp32.  torch's own float32_matmul_precision is neither read nor set.
+# its bits -- a user who wants bf16 inference has the bf16 model; MSDA, LayerNorm, the losses and the matcher; shapes the split
+# kernels do not serve still take the vendor GEMM in fp32.  torch's own float32_matmul_precision is neither read nor set.
 _MATMUL_PRECISIONS = ("fp32", "bf16")
 
 
@@ -1320,30 +1324,27 @@ class RelationHeadFunction(Function):
         tens = [gate_q, gate_k, uq, uk, b1, w2r, b2r, w3r, b3r, w2c, b2c, w3c, b3c]
         names = ["gate_q", "gate_k", "uq", "uk", "b1", "w2r", "b2r", "w3r", "b3r", "w2c", "b2c", "w3c", "b3c"]
         tens = [_chk(t.contiguous(), n, torch.float32) for t, n in zip(tens, names)]
-        rel = torch.empty(B, N, N, R, dtype=torch.float32, device=gate_q.device)
-        conn = torch.empty(B, N, N, dtype=torch.float32, device=gate_q.device)
-        gm = torch.zeros(T, dtype=torch.float32, device=gate_q.device) if want_gate_mean else None
-        if triplet_dist is not None:
-            _chk(triplet_dist, "triplet_dist", torch.float32)
-            _chk(node_cls, "node_cls", torch.int64)
-            c1 = triplet_dist.shape[0]
-        else:
-            c1 = 0
         need_grad = any(ctx.needs_input_grad[:13])
-        P_ = B * N * N
-        h1s = torch.empty(2, P_, Hd, dtype=torch.float32, device=gate_q.device) if need_grad else None
-        h2s = torch.empty(2, P_, Hd, dtype=torch.float32, device=gate_q.device) if need_grad else None
+        ctx.terms = 6
         if REL_HEAD_TRAIN_X6 and need_grad and GEMM_SPLIT_BF16 and Hd == 256 and R <= 64 and T in (4, 7):
             # layers 2 and 3 on the bf16 matrix cores from split operands (the inference kernel with the two activation stores the
-            # backward needs); the weight streams are rebuilt by one launch -- the weights change every step
-            gq_, gk_, uq_, uk_, b1_, w2r_, b2r_, w3r_, b3r_, w2c_, b2c_, w3c_, b3c_ = tens
-            w2xr, w3x, w2xc = rel_head_streams(w2r_, w3r_, w2c_)
-            _lib.launch("egtr_rel_head_forward_bf16x6_save_f32", gq_.data_ptr(), gk_.data_ptr(), uq_.data_ptr(), uk_.data_ptr(),
-                        b1_.data_ptr(), w2xr.data_ptr(), b2r_.data_ptr(), w3x.data_ptr(), b3r_.data_ptr(), w2xc.data_ptr(),
-                        b2c_.data_ptr(), w3c_.data_ptr(), b3c_.data_ptr(), _lib.ptr(triplet_dist),
-                        _lib.ptr(node_cls if triplet_dist is not None else None), B, N, T, Hd, R, c1, rel.data_ptr(),
-                        conn.data_ptr(), _lib.ptr(gm), h1s.data_ptr(), h2s.data_ptr())
-        else:
+            # backward needs); the weight streams are rebuilt by one launch -- the weights change every step.  Matmul precision
+            # "bf16": the one-term kernel on one-piece streams, read once -- the backward multiplies the way the forward did
+            ctx.terms = _gemm_terms()
+            rel, conn, gm, h1s, h2s = relation_head_train_forward(*tens, triplet_dist, node_cls, want_gate_mean, ctx.terms)
+        else:   # exact f32 under either matmul precision (a route, not a fall-off), and so is its backward
+            rel = torch.empty(B, N, N, R, dtype=torch.float32, device=gate_q.device)
+            conn = torch.empty(B, N, N, dtype=torch.float32, device=gate_q.device)
+            gm = torch.zeros(T, dtype=torch.float32, device=gate_q.device) if want_gate_mean else None
+            if triplet_dist is not None:
+                _chk(triplet_dist, "triplet_dist", torch.float32)
+                _chk(node_cls, "node_cls", torch.int64)
+                c1 = triplet_dist.shape[0]
+            else:
+                c1 = 0
+            P_ = B * N * N
+            h1s = torch.empty(2, P_, Hd, dtype=torch.float32, device=gate_q.device) if need_grad else None
+            h2s = torch.empty(2, P_, Hd, dtype=torch.float32, device=gate_q.device) if need_grad else None
             _lib.launch("egtr_rel_head_forward_save_f32", *[t.data_ptr() for t in tens], _lib.ptr(triplet_dist),
                         _lib.ptr(node_cls if triplet_dist is not None else None), B, N, T, Hd, R, c1, rel.data_ptr(),
                         conn.data_ptr(), _lib.ptr(gm), _lib.ptr(h1s), _lib.ptr(h2s))
@@ -1356,7 +1357,11 @@ class RelationHeadFunction(Function):
     def backward(ctx, grad_rel, grad_conn, grad_gm):
         """MLP part: rocBLAS GEMMs on the [B*N*N, 256] activations the forward kernel saved (no recomputation; the
         ReLU masks are applied with threshold_backward).  Pairwise part (gradients of the per-query tables and of
-        the gate logits): HIP, egtr_rel_head_backward_pairs_f32.  The frequency bias is an additive constant."""
+        the gate logits): HIP, egtr_rel_head_backward_pairs_f32.  The frequency bias is an additive constant.
+        A forward that took the one-term route (ctx.terms == 1, matmul precision "bf16"): the two layer-2 products of each MLP
+        round their operands once to bf16 -- dh1 = (dh2 W2) * [h1 > 0] with the 32-row partial column sums of the b1 gradient is
+        ONE egtr_linear_split_bf16_ex_f32 launch per MLP (instead of the vendor GEMM and a masked column-sum pass over its
+        result), dW2 the one-term weight gradient; layer 3 (reduction or output of num_rel / 1) stays fp32."""
         (gate_q, gate_k, uq, uk, b1, w2r, b2r, w3r, b3r, w2c, b2c, w3c, b3c, h1s, h2s) = ctx.saved_tensors
         B, N, T = gate_q.shape
         Hd = w2r.shape[1]
@@ -1365,22 +1370,37 @@ class RelationHeadFunction(Function):
         G = grad_rel.reshape(P_, R).contiguous()
         gc = grad_conn.reshape(P_, 1).contiguous()
         dh1 = torch.empty(2, P_, Hd, dtype=torch.float32, device=G.device)
-        wgrad = (linear_split_bf16_wgrad if GEMM_SPLIT_BF16 and GEMM_SPLIT_WGRAD and Hd % 128 == 0
-                 else (lambda g, h: g.t() @ h))
+        one_term = ctx.terms == 1 and Hd % 128 == 0
+        if one_term:
+            wgrad = ((lambda g, h: linear_split_bf16_wgrad(g, h, terms=1)) if GEMM_SPLIT_WGRAD else (lambda g, h: g.t() @ h))
+            colp = torch.empty(2, (P_ + 31) // 32, Hd, dtype=torch.float32, device=G.device)
+
+            def dgrad(g, w2, i):   # dh1[i] <- (g W2) * [h1s[i] > 0], colp[i] <- its column sums per 32 rows
+                linear_split_ex([dict(x=g, wt=gemm_split_tile(w2, transposed=True, terms=1), N=Hd, relu_ref=h1s[i],
+                                      colpart=colp[i], out=dh1[i])], P_, Hd, terms=1)
+        else:
+            wgrad = (linear_split_bf16_wgrad if GEMM_SPLIT_BF16 and GEMM_SPLIT_WGRAD and Hd % 128 == 0
+                     else (lambda g, h: g.t() @ h))
+
+            def dgrad(g, w2, i):
+                torch.mm(g, w2, out=dh1[i])
         # relation MLP (ReLU masks and bias gradients: one pass each, egtr_column_sum_f32, the mask applied in place)
         dh2, db2r = column_sum(G @ w3r, relu_output=h2s[0], inplace=True)
         dw3r = G.t() @ h2s[0]
         db3r = G.sum(0)   # 50 columns: the generic reduction is faster (19 vs 30 us)
-        torch.mm(dh2, w2r, out=dh1[0])
+        dgrad(dh2, w2r, 0)
         dw2r = wgrad(dh2, h1s[0])
         # connectivity MLP (one output)
         dh2, db2c = column_sum(gc * w3c, relu_output=h2s[1], inplace=True)
         dw3c = weighted_column_sum(h2s[1], gc).view(1, -1)   # gc^T h2: one pass instead of a 220 us GEMV
         db3c = gc.sum(0)
-        torch.mm(dh2, w2c, out=dh1[1])
+        dgrad(dh2, w2c, 1)
         dw2c = wgrad(dh2, h1s[1])
         del dh2
-        db1 = torch.cat([column_sum(dh1[i], relu_output=h1s[i], inplace=True)[1] for i in range(2)])
+        if one_term:   # the 32-row partial sums finished in a fixed order
+            db1 = torch.cat([column_sum(colp[i]) for i in range(2)])
+        else:
+            db1 = torch.cat([column_sum(dh1[i], relu_output=h1s[i], inplace=True)[1] for i in range(2)])
         duq = torch.empty_like(uq)
         duk = torch.empty_like(uk)
         dgq = torch.empty_like(gate_q)

@@ -44,8 +44,10 @@ enum {
   EGTR_E_UNSUPPORTED = -3
 };
 
-/* Bumped whenever an entry point is added / removed or the meaning of an argument changes; egtr_amd/_lib.py refuses a
- * library whose number differs from the one it was written against. */
+/* Bumped when an entry point is removed or when an existing entry's signature or meaning changes; egtr_amd/_lib.py refuses a
+ * library whose number differs from the one it was written against.  A purely additive change keeps the number (a caller
+ * written against it stays valid); egtr_amd/_lib.py resolves every symbol it binds at load, so a library that lacks a newer
+ * entry still fails loudly. */
 #define EGTR_ABI_VERSION 6
 int egtr_abi_version(void);
 const char* egtr_status_string(int status);
@@ -1087,6 +1089,27 @@ int egtr_rel_head_forward_bf16x6_save_f32(egtr_stream_t stream, const float* gat
  * launch (pieces rounded to nearest): what a training step rebuilds after every optimizer step.  hidden = 256, num_rel <= 64. */
 int egtr_rel_head_streams_f32(egtr_stream_t stream, const float* w2_rel, const float* w2_conn, const float* w3_rel,
                               int hidden, int num_rel, uint16_t* w2x_rel, uint16_t* w2x_conn, uint16_t* w3x_rel);
+
+/* The training forward with ONE product per element in layers 2 and 3 (matmul precision "bf16" of the training step): the
+ * post-ReLU activations of layers 1 and 2 and the weights W2 / W3 are each rounded once to bfloat16 (round to nearest even,
+ * bit-equal to a float -> bfloat16 cast: Inf and NaN survive, a finite value beyond 3.39e38 becomes Inf), one matrix
+ * instruction per k-step, fp32 accumulation.  Layer 1, the connectivity output layer, biases, frequency bias, gate_mean and the
+ * outputs are those of egtr_rel_head_forward_bf16x6_save_f32; h1_save / h2_save hold the fp32 values BEFORE the rounding.  The
+ * weights arrive as ONE-piece streams (raw bfloat16 bits) in the operand order above without the piece dimension:
+ *   w2x_*  [8 nt][16 t][64 lane][8],  w3x_rel [8 nt][2 kb][OT][64 lane][8]   (egtr_rel_head_streams_bf16r_f32 builds them).
+ * EGTR_E_UNSUPPORTED for num_slots other than 4 or 7, hidden != 256, num_rel > 64; EGTR_E_ARG for a NULL operand. */
+int egtr_rel_head_forward_bf16r_save_f32(egtr_stream_t stream, const float* gate_q, const float* gate_k, const float* uq,
+                                         const float* uk, const float* b1, const uint16_t* w2x_rel, const float* b2r,
+                                         const uint16_t* w3x_rel, const float* b3r, const uint16_t* w2x_conn,
+                                         const float* b2c, const float* w3c, const float* b3c,
+                                         const float* triplet_dist, const int64_t* node_cls, int batch, int num_query,
+                                         int num_slots, int hidden, int num_rel, int num_cls_plus1, float* rel_logits,
+                                         float* conn_logits, float* gate_mean, float* h1_save, float* h2_save);
+
+/* The one-piece streams of the entry above from the fp32 weights in one launch: every element rounded once to nearest even,
+ * rows of W3 at or beyond num_rel zero.  hidden = 256, num_rel <= 64. */
+int egtr_rel_head_streams_bf16r_f32(egtr_stream_t stream, const float* w2_rel, const float* w2_conn, const float* w3_rel,
+                                    int hidden, int num_rel, uint16_t* w2x_rel, uint16_t* w2x_conn, uint16_t* w3x_rel);
 
 
 /* Pairwise part of the relation-head backward (everything that is not a plain GEMM).  dh1 [2][B*N*N][hidden] is the

@@ -7,7 +7,10 @@ rounded once, one product), alternating the two in ONE process.  HIP events arou
       setting switched between blocks of steps;
   (c) the relative deviation of the total loss and of the global gradient norm between the two modes on the inputs of the
       tests/golden/sgg_full_train.npz fixture (600x1000, bs 2, auxiliary losses, dropout 0), next to the deviation between two
-      "fp32" runs (the atomics of the MSDA backward make the gradient norm of one mode vary from run to run).
+      "fp32" runs (the atomics of the MSDA backward make the gradient norm of one mode vary from run to run);
+  (d) the relation head at B = 4, N = 200, T = 7, R = 50: the training forward launch alone, RelationHeadFunction forward +
+      backward, and inside the backward the two data-gradient launches against torch.mm + column_sum and the two weight
+      gradients with ``terms`` 1 against 6 (profiles/matmul_precision_rel_head_ab.txt).
 
     python tools/matmul_precision_bench.py [--rounds 3] [--iters 50] [--steps 10] [--out profiles/matmul_precision_ab.txt]
 """
@@ -151,12 +154,82 @@ def deviation():
         f"(fp32 run to run {abs(n32b - n32) / abs(n32):.1e})")
 
 
+def rel_head(rounds, iters):
+    """(d) the relation head at B = 4, N = 200, T = 7, R = 50 (160 000 pairs): per piece, "fp32" against "bf16", alternating.  A
+    piece stays routed under the mode only if its "bf16" median is below its "fp32" median by more than the spread (max - min)
+    of the "fp32" rounds of this run: the verdict is printed per piece."""
+    from egtr_amd import ops
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+    from test_gpu_kernels import _head_inputs
+    B, N, T, R = 4, 200, 7, 50
+    d, trip, node = _head_inputs(1, B, N, T, R, 150)
+    dd = [v.to(DEV) for v in d.values()]
+    trip, node = trip.to(DEV), node.to(DEV)
+    w2r, w3r, w2c = dd[5], dd[7], dd[9]
+    P_, Hd = B * N * N, 256
+    g = torch.Generator().manual_seed(2)
+    g_rel, g_conn = torch.randn(B, N, N, R, generator=g).to(DEV), torch.randn(B, N, N, 1, generator=g).to(DEV)
+    say(f"(d) relation head, B = {B}, N = {N}, T = {T}, R = {R}: median of {rounds} alternating rounds x {iters} calls, us; "
+        "fp32 | bf16 | ratio | fp32 spread | verdict")
+
+    def ab(name, fns):
+        got = {"fp32": [], "bf16": []}
+        for _ in range(rounds):
+            for mode in ("fp32", "bf16"):
+                got[mode].append(time_us(fns[mode], iters))
+        m32, m16 = statistics.median(got["fp32"]), statistics.median(got["bf16"])
+        spread = max(got["fp32"]) - min(got["fp32"])
+        say(f"  {name:44s} {m32:8.1f} | {m16:8.1f} | {m32 / m16:5.2f}x | {spread:6.1f} | "
+            f"{'faster beyond the spread: routed' if m32 - m16 > spread else 'NOT faster beyond the spread'}"
+            f"   rounds {['%.1f' % v for v in got['fp32']]} | {['%.1f' % v for v in got['bf16']]}")
+
+    streams = {t: ops.rel_head_streams(w2r, w3r, w2c, terms=t) for t in (6, 1)}
+    fwd = lambda t: ops.relation_head_train_forward(*dd, trip, node, True, t, streams=streams[t])   # noqa: E731
+    ab("training forward launch", {"fp32": lambda: fwd(6), "bf16": lambda: fwd(1)})
+
+    leaves = [v.clone().requires_grad_(True) for v in dd]
+
+    def step(mode):
+        for t in leaves:
+            t.grad = None
+        with ops.matmul_precision_mode(mode):
+            rel, conn, _ = ops.RelationHeadFunction.apply(*leaves, trip, node, True)
+            torch.autograd.backward([rel, conn], [g_rel, g_conn])
+
+    ab("RelationHeadFunction forward + backward", {"fp32": lambda: step("fp32"), "bf16": lambda: step("bf16")})
+
+    _, _, _, h1s, h2s = fwd(6)
+    del h2s
+    dh2 = torch.randn(P_, Hd, generator=g).to(DEV)
+    dh1 = torch.empty(2, P_, Hd, device=DEV)
+    colp = torch.empty(2, (P_ + 31) // 32, Hd, device=DEV)
+
+    def dgrad_fp32():
+        for i, w2 in enumerate((w2r, w2c)):
+            torch.mm(dh2, w2, out=dh1[i])
+            ops.column_sum(dh1[i], relu_output=h1s[i], inplace=True)
+
+    def dgrad_bf16():
+        for i, w2 in enumerate((w2r, w2c)):
+            ops.linear_split_ex([dict(x=dh2, wt=ops.gemm_split_tile(w2, transposed=True, terms=1), N=Hd, relu_ref=h1s[i],
+                                      colpart=colp[i], out=dh1[i])], P_, Hd, terms=1)
+            ops.column_sum(colp[i])
+
+    ab("two data gradients + masks + b1 column sums", {"fp32": dgrad_fp32, "bf16": dgrad_bf16})
+    ab("two weight gradients (terms 6 | 1)",
+       {"fp32": lambda: [ops.linear_split_bf16_wgrad(dh2, h1s[i], terms=6) for i in range(2)],
+        "bf16": lambda: [ops.linear_split_bf16_wgrad(dh2, h1s[i], terms=1) for i in range(2)]})
+    del h1s, dh1, dh2, colp, leaves
+    torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--steps", type=int, default=10)
-    ap.add_argument("--skip", default="", help="comma-separated parts to leave out: a, b, c")
+    ap.add_argument("--skip", default="", help="comma-separated parts to leave out: a, b, c, d")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs the GPU: a timing from anywhere else says nothing"
@@ -169,6 +242,8 @@ def main():
         train_step(args.rounds, args.steps)
     if "c" not in skip:
         deviation()
+    if "d" not in skip:
+        rel_head(args.rounds, args.iters)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
