@@ -8,13 +8,15 @@
 //     operand fragments (64 KiB), lo in registers (each wave: the 16 fragments of its 32 rows);
 //   * the hidden dimension is walked in chunks of 64 units: layer 1 for the chunk (K = 256: 4 stages of 4 k-steps), bias +
 //     ReLU + split of the 64 x 64 chunk into LDS (24 KiB), layer 2 accumulating the chunk into the 64 x 256 output tile
-//     (K = 64: 4 stages of 1 k-step, 4 accumulator tiles per wave);
+//     (K = 64: 4 stages of 1 k-step, 4 accumulator tiles per wave) layer 1 runs one chunk ahead, so that a chunk's
+//     hand-over (bias, ReLU, split, LDS stores) issues behind the MFMAs of layer 2 of the chunk before it;
 //   * the weights arrive pre-split in the XS format and stream through a ring of three 24 KiB LDS stages filled by LDS-DMA
 //     two stages ahead (counted vmcnt, raw s_barrier, one barrier per stage): every stage, of either layer, is 24 fragments
 //     and 24 MFMAs per wave, so the two layers form ONE uniform stream of 8 stages per chunk;
 //   * the six-term split product (x6_common.h) everywhere: fp32 operands, fp32 accumulation, error of an fp32 GEMM.
 // LDS: 64 (panel) + 24 (hidden chunk) + 72 (ring) = 160 KiB, one workgroup of four waves per CU.
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include "common.h"
@@ -35,6 +37,23 @@ constexpr int kLds = kPanel + kHbuf + 3 * kStage;
 static_assert(kLds == 160 * 1024, "the whole LDS of a CU");
 constexpr int NL = 6;                            // DMA instructions per wave and stage
 typedef float f32x8 __attribute__((ext_vector_type(8)));
+
+#ifdef EGTR_FFN_X6_TIMING
+// development aid (tools/enc_tail_bench.hip): shader-clock stamps of wave 0 of every workgroup of the LAST launch, taken in
+// front of every stage top of the FFN walk and around the hand-over, kept in scalar registers and summed per position over
+// the chunks (low 32 bits: a panel is < 2^32 cycles); one record per workgroup, written after the epilogue -- no store and
+// no vector wait inside the walk.  Not for production: the stamps are scalar memory reads that the stage tops wait for.
+constexpr int kRecWg = 256, kRecN = 24;
+__device__ unsigned g_ffn_x6_rec[kRecWg][kRecN];
+#define FFN_T(v)                                        \
+  do {                                                  \
+    __builtin_amdgcn_sched_barrier(0);                  \
+    (v) = (unsigned)__builtin_amdgcn_s_memtime();       \
+    __builtin_amdgcn_sched_barrier(0);                  \
+  } while (0)
+#else
+#define FFN_T(v) do { } while (0)
+#endif
 
 struct FfnArgs {
   const float* x;        // [M, ldx] fp32
@@ -231,10 +250,15 @@ __global__ __launch_bounds__(256, 1) void ffn_x6_kernel(FfnArgs A) {
   const unsigned lds_ring = (unsigned)reinterpret_cast<uintptr_t>((lds_char*)ring);
   const int r0 = blockIdx.x * kRows;
   const int nchunk = A.F >> 6, KSf = A.F >> 4;
+#ifdef EGTR_FFN_X6_TIMING
+  unsigned tk0, tl0, ts[8], th = 0, te = 0, tsum[6] = {0, 0, 0, 0, 0, 0};   // ts: 0, 4, 5, 7 only (SGPRs are short)
+  FFN_T(tk0);
+#endif
 
   // ---- weight stream.  Global stage g: [PROJ: g < 16 = k-step g of the output projection, all 256 outputs ([8 n-blocks][3
-  //      pieces]), then] stage 8 c + s of the FFN -- s < 4: layer 1, hidden units 64 c .., k-steps 4 s .. 4 s + 3 of d_model
-  //      ([2 n-blocks][4 k-steps][3 pieces]); s >= 4: layer 2, k-step 4 c + (s - 4) of the hidden dimension, all 256 outputs
+  //      pieces]), then] the FFN's stages in the order of stage_src() below (layer 1 one chunk ahead of layer 2) -- layer 1 of
+  //      chunk c, step s: hidden units 64 c .., k-steps 4 s .. 4 s + 3 of d_model ([2 n-blocks][4 k-steps][3 pieces]); layer 2
+  //      of chunk c, step s: k-step 4 c + s of the hidden dimension, all 256 outputs
   //      ([8 n-blocks][3 pieces]).  Wave w moves fragments 6 w .. 6 w + 5 of the stage image: contiguous in LDS, and in
   //      global memory one 6 KiB run (layer 1) or two 3 KiB runs (layer 2, projection).
   const unsigned voff = lane * 16;
@@ -251,9 +275,14 @@ __global__ __launch_bounds__(256, 1) void ffn_x6_kernel(FfnArgs A) {
   // the last one again (never read; keeps every wait count an immediate).
   auto stage_src = [&](int g, const char*& base, size_t& stride) {
     g = g < nstages ? g : nstages - 1;
-    const bool pj = g < NP;
-    const int gg = g - NP, c = chunk_of(pj ? 0 : gg >> 3), st = gg & 7;
-    const bool l1 = st < 4;
+    // FFN stage gg: 0 .. 3 = layer 1 of the first chunk; then groups of eight: layer 1 of chunk q + 1, layer 2 of chunk q
+    // (layer 1 runs one chunk ahead); the last four stages: layer 2 of the last chunk.  Flags as 0 / 1 from sign bits:
+    // integer arithmetic stays on the scalar unit and makes no branch inside a stage.
+    const int gg = g - NP, h = gg - 4, q = h >> 3;
+    const int pji = (int)((unsigned)gg >> 31), first = (int)((unsigned)h >> 31);   // projection; it or the first L1 group
+    const int l1i = first | (((~h >> 2) & 1) & (int)((unsigned)(q - (nchunk - 1)) >> 31));
+    const bool pj = pji != 0, l1 = l1i != 0;
+    const int c = chunk_of((q + l1i) & (first - 1)), st = gg & 3;
     const char* b1 = A.w1 + ((size_t)((2 * c + (wave >> 1)) * kKS + 4 * (st & 3) + 2 * (wave & 1)) * 3) * kFrag;
     const char* b2 = A.w2 + ((size_t)(2 * wave * KSf + 4 * c + (st & 3)) * 3) * kFrag;
     base = l1 ? b1 : b2;
@@ -263,6 +292,15 @@ __global__ __launch_bounds__(256, 1) void ffn_x6_kernel(FfnArgs A) {
       stride = pj ? (size_t)kKS * 3 * kFrag : stride;
     }
   };
+  // Inside the walk the source is kept RUNNING instead: the stages come in groups of four (a layer of a chunk, four k-steps
+  // of the projection) inside which the source advances by a constant.  A wave issues one instruction in four cycles and
+  // nothing of a stage top hides behind an MFMA, so the ~45 scalar instructions of stage_src in front of the first MFMA of
+  // every stage were ~180 exposed cycles per stage.  (fsrc, fstride): the stage the CURRENT stage fetches (g + 3); the last
+  // stage of a fetch group computes the next group's start behind its last MFMAs, the others advance by the group's step
+  // (layer 1, fragment stride 3 KiB: four k-steps = 12 KiB; layer 2 and projection: one k-step = 3 KiB).  Beyond the last
+  // stage: the last GROUP again (never read, inside the weights).
+  const char* fsrc;
+  unsigned fstride;   // < 2^32: at most 3 KiB x F / 16
   auto issue = [&](int g, int slot) {
     const unsigned dst = lds_ring + (unsigned)slot * kStage + (unsigned)wave * (NL * kFrag);
     const char* base;
@@ -299,6 +337,45 @@ __global__ __launch_bounds__(256, 1) void ffn_x6_kernel(FfnArgs A) {
   const char* const pw = ring + (4 * wn * 3) * kFrag + lane * 16;
   auto frag = [](const char* p) { return *reinterpret_cast<const bf16x8*>(p); };
 
+  // The hand-over of a hidden chunk, in pieces: value e = 4 q + j of the wave's 32 x 32 piece (acc1 register 4 q + j: hidden
+  // index 32 wn + 8 q + 4 hf + j of the chunk -> k-step 2 wn + (q >> 1), k-group q & 1) = ReLU(acc1 + bias), split; a PAIR of
+  // values packed into one 32-bit word of each of the three pieces; twelve 8-byte stores (q, piece) into `hbuf`.  The 32
+  // bias values are wave-uniform and sit in scalar registers (bias[q] = values 8 q .. 8 q + 7).
+  f32x8 bias[4];
+  xs::Split3 hsp[2];   // the pair being split
+  uint2 hpk[4][3];     // the packed chunk piece of this lane: [q][hi, mid, lo]
+  float hv[6];         // first halves of a stage's values
+  auto ho_value_a = [&](auto E) {
+    constexpr int e = decltype(E)::value, q = e >> 2, j = e & 3;
+    const float blo = bias[q][j], bhi = bias[q][4 + j];
+    float& v = hv[e % 6];
+    v = egtr_relu(acc1[0][4 * q + j] + acc1[1][4 * q + j] + (hf ? bhi : blo));
+    asm volatile("" : "+v"(v));   // computed HERE: the compiler would sink it to its use
+  };
+  auto ho_value_b = [&](auto E) {
+    constexpr int e = decltype(E)::value;
+    xs::Split3& v = hsp[e & 1];
+    v = xs::split3_fast(hv[e % 6]);
+    asm volatile("" : "+v"(v.hi), "+v"(v.mid), "+v"(v.lo));
+  };
+  auto ho_value = [&](auto E) {
+    ho_value_a(E);
+    ho_value_b(E);
+  };
+  auto ho_pack = [&](auto P) {
+    constexpr int p = decltype(P)::value, q = p >> 1;
+    unsigned h = xs::pack_hi16(hsp[0].hi, hsp[1].hi), m = xs::pack_hi16(hsp[0].mid, hsp[1].mid),
+                   l = xs::pack_hi16(hsp[0].lo, hsp[1].lo);
+    asm volatile("" : "+v"(h), "+v"(m), "+v"(l));
+    if constexpr ((p & 1) == 0) { hpk[q][0].x = h; hpk[q][1].x = m; hpk[q][2].x = l; }
+    else { hpk[q][0].y = h; hpk[q][1].y = m; hpk[q][2].y = l; }
+  };
+  auto ho_store = [&](auto N) {
+    constexpr int n = decltype(N)::value, q = n / 3, piece = n % 3;
+    char* dst = hbuf + ((wm * 4 + 2 * wn + (q >> 1)) * 3 + piece) * kFrag + (q & 1) * 512 + li * 16 + hf * 8;
+    *reinterpret_cast<uint2*>(dst) = hpk[q][piece];
+  };
+
   // One stage in PINNED program order (sched_barrier(0) between the items; left alone, hipcc reads every operand right
   // before its use and chains six dependent MFMAs on one accumulator): 24 MFMAs, consecutive ones on different
   // accumulators; behind MFMAs 1, 3, .., 11 the six DMA instructions of stage g + 3; behind MFMAs 12 .. 17 the twelve
@@ -307,14 +384,21 @@ __global__ __launch_bounds__(256, 1) void ffn_x6_kernel(FfnArgs A) {
   // S: 0 .. 3 = layer 1 step S; 4 .. 7 = layer 2 step S - 4; 8 + ks = projection k-step ks (PROJ).
   // a / anx: operand A of this / the next stage: layer 1 = [k-step 4][hi, mid] (lo comes from the registers); layer 2 and
   // projection = the three pieces of ONE k-step in a[0][0], a[0][1], a[1][0].
-  auto stage = [&](auto S, const bf16x8 (&w)[4][3], bf16x8 (&wnx)[4][3], const bf16x8 (&a)[4][2], bf16x8 (&anx)[4][2], int g,
-                   int slot_next, int slot_fill) {
+  // HO (FFN stages only): 0 = the first layer-1 group and the last layer-2 group of a panel, 1 = a stage of the steady state,
+  // where layer 1 runs one chunk ahead of layer 2 and the hand-over of that chunk rides behind the layer-2 MFMAs -- its
+  // sixteen values (bias + ReLU + split) behind MFMAs 0, 2, .., 10 of steps 0 .. 2, one each, the packing of a pair behind
+  // the odd MFMA after it; its twelve LDS stores behind MFMAs 0 .. 11 of step 3, whose top barrier comes after everybody's
+  // last read of the previous chunk (k-step 3: read in step 2).  The first layer-2 operand of a chunk is read behind MFMA 18
+  // of the layer-1 group's last stage, at least four barriers after the chunk was stored.
+  auto stage = [&](auto S, auto HOc, const bf16x8 (&w)[4][3], bf16x8 (&wnx)[4][3], const bf16x8 (&a)[4][2],
+                   bf16x8 (&anx)[4][2], int g, int slot_next, int slot_fill) {
     constexpr int s = decltype(S)::value;
+    constexpr bool HO = decltype(HOc)::value != 0;
     const char* const wn_src = pw + slot_next * kStage;
     const unsigned dst = lds_ring + (unsigned)slot_fill * kStage + (unsigned)wave * (NL * kFrag);
-    const char* src;
-    size_t sstride;
-    stage_src(g + 3, src, sstride);
+    const char* const src = fsrc;   // stage g + 3
+    const size_t sstride = fstride;
+    size_t stride64;
     static_for<24>([&](auto I) {
       constexpr int i = decltype(I)::value;
       // the six cross terms, small ones first: (w piece, a piece)
@@ -337,6 +421,33 @@ __global__ __launch_bounds__(256, 1) void ffn_x6_kernel(FfnArgs A) {
         dma16s(src + (j / 3) * sstride + (j % 3) * kFrag, voff, dst + j * kFrag);
         __builtin_amdgcn_sched_barrier(0);
       }
+      if constexpr (HO && s >= 4 && s < 7) {
+        // six values of the hand-over per stage (four in the last): k-th value = 6 (s - 4) + k.  First halves behind MFMAs
+        // 0, 2, .., 10, second halves and the packing of the three pairs behind MFMAs 12 .. 21 -- at most ~7 instructions
+        // behind one MFMA (8 issue slots of 4 cycles), none behind an MFMA that carries a DMA instruction
+        constexpr int e0 = 6 * (s - 4);
+        constexpr int kb[10] = {0, 1, -1, 2, 3, -2, -9, 4, 5, -3};   // behind MFMA 12 + x: second half k, or -(pair + 1)
+        if constexpr (i < 12 && (i & 1) == 0 && e0 + (i >> 1) < 16) {
+          ho_value_a(std::integral_constant<int, e0 + (i >> 1)>{});
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        if constexpr (i >= 12 && i < 22) {
+          constexpr int k = kb[i - 12];
+          if constexpr (k >= 0 && e0 + k < 16) {
+            ho_value_b(std::integral_constant<int, e0 + k>{});
+            __builtin_amdgcn_sched_barrier(0);
+          }
+          if constexpr (k < 0 && k > -9 && e0 + 2 * (-k - 1) < 16) {
+            ho_pack(std::integral_constant<int, e0 / 2 + (-k - 1)>{});
+            __builtin_amdgcn_sched_barrier(0);
+          }
+        }
+      }
+      if constexpr (HO && s == 7 && i < 12 && (i & 1) == 0) {
+        ho_store(std::integral_constant<int, i>{});
+        ho_store(std::integral_constant<int, i + 1>{});
+        __builtin_amdgcn_sched_barrier(0);
+      }
       if constexpr (i >= 12 && i < 18) {
         constexpr int j = 2 * (i - 12);
         wnx[j / 3][j % 3] = frag(wn_src + j * kFrag);
@@ -344,16 +455,19 @@ __global__ __launch_bounds__(256, 1) void ffn_x6_kernel(FfnArgs A) {
         __builtin_amdgcn_sched_barrier(0);
       }
       if constexpr (s < 8) {
-        // layer 1 reads the read-only input panel, steps 1 .. 3 of layer 2 a hidden chunk finished at least a stage ago
-        // (step 0: after the barrier)
+        // the operand of the NEXT stage.  Layer 1 reads the read-only input panel.  Layer 2: steps 1 .. 3 a hidden chunk
+        // finished at least a stage ago; step 0 behind the last stage of the layer-1 group in front of it (steady state: the
+        // chunk was published four barriers ago) -- the last layer-2 group of a panel reads it after its own top barrier.
         constexpr int sx = (s + 1) & 7;
-        if constexpr (i >= 18 && i < 22 && sx < 4) {
+        constexpr bool nx_l1 = sx < 4 || (s == 3 && !HO);   // after the first layer-1 group: the next one (if any)
+        constexpr bool nx_l2 = sx > 4 || (s == 3 && HO);
+        if constexpr (i >= 18 && i < 22 && nx_l1) {
           constexpr int kl = i - 18;
-          anx[kl][0] = pfrag(4 * sx + kl, 0);
-          anx[kl][1] = pfrag(4 * sx + kl, 1);
+          anx[kl][0] = pfrag(4 * (sx & 3) + kl, 0);
+          anx[kl][1] = pfrag(4 * (sx & 3) + kl, 1);
           __builtin_amdgcn_sched_barrier(0);
         }
-        if constexpr (i == 18 && sx > 4) {
+        if constexpr (i == 18 && nx_l2) {
           anx[0][0] = frag(ph + ((sx - 4) * 3 + 0) * kFrag);
           anx[0][1] = frag(ph + ((sx - 4) * 3 + 1) * kFrag);
           anx[1][0] = frag(ph + ((sx - 4) * 3 + 2) * kFrag);
@@ -368,6 +482,17 @@ __global__ __launch_bounds__(256, 1) void ffn_x6_kernel(FfnArgs A) {
           __builtin_amdgcn_sched_barrier(0);
         }
       }
+      // the source of the next stage's fetch (stage g + 4)
+      if constexpr (i == 22) {
+        if constexpr ((s & 3) == 0) {
+          stage_src(min(g + 4, nstages - 4), fsrc, stride64);
+          fstride = (unsigned)stride64;
+        } else {
+          fsrc += fstride == 3u * kFrag ? 12 * kFrag : 3 * kFrag;
+        }
+        asm volatile("" : "+s"(fsrc), "+s"(fstride));   // computed HERE: the compiler would sink it to the next stage's top
+        __builtin_amdgcn_sched_barrier(0);
+      }
     });
   };
 
@@ -375,7 +500,6 @@ __global__ __launch_bounds__(256, 1) void ffn_x6_kernel(FfnArgs A) {
   // may stay in flight: counted vmcnt), everybody's LDS traffic of stage g - 1 is finished (lgkmcnt(0) + barrier): the
   // weights of stage g + 1 may be read (into the other register set) and the slot of stage g refilled with stage g + 3.
   bf16x8 w0[4][3], w1[4][3], a0[4][2], a1[4][2];
-  f32x8 bias[4];
   wait_vm<NL>();                      // stage 0 (stage 1 in flight)
   wait_lgkm0();
   __builtin_amdgcn_s_barrier();
@@ -384,6 +508,11 @@ __global__ __launch_bounds__(256, 1) void ffn_x6_kernel(FfnArgs A) {
   for (int u = 0; u < 4; ++u)
 #pragma unroll
     for (int p = 0; p < 3; ++p) w0[u][p] = frag(pw + (u * 3 + p) * kFrag);
+  {
+    size_t stride64;
+    stage_src(3, fsrc, stride64);   // stage 0 fetches stage 3, the last of its group
+    fstride = (unsigned)stride64;
+  }
   int slot = 0;   // ring slot of the stage being multiplied
   int g = 0;      // its global index
   auto stage_top = [&]() {
@@ -404,8 +533,8 @@ __global__ __launch_bounds__(256, 1) void ffn_x6_kernel(FfnArgs A) {
       constexpr int ks = decltype(KS)::value;
       const int sn = slot == 2 ? 0 : slot + 1;
       stage_top();
-      if constexpr ((ks & 1) == 0) stage(std::integral_constant<int, 8 + ks>{}, w0, w1, a0, a1, g, sn, slot);
-      else stage(std::integral_constant<int, 8 + ks>{}, w1, w0, a1, a0, g, sn, slot);
+      if constexpr ((ks & 1) == 0) stage(std::integral_constant<int, 8 + ks>{}, std::integral_constant<int, 0>{}, w0, w1, a0, a1, g, sn, slot);
+      else stage(std::integral_constant<int, 8 + ks>{}, std::integral_constant<int, 0>{}, w1, w0, a1, a0, g, sn, slot);
       slot = sn;
       ++g;
     });
@@ -464,63 +593,131 @@ __global__ __launch_bounds__(256, 1) void ffn_x6_kernel(FfnArgs A) {
     a0[u][0] = pfrag(u, 0);
     a0[u][1] = pfrag(u, 1);
   }
+  // ---- the FFN walk.  Layer 1 runs one chunk AHEAD of layer 2 (c: position in this workgroup's rotated chunk order):
+  //          L1(0), hand-over(0);   { L1(c + 1), L2(c) with hand-over(c + 1) behind its MFMAs } c = 0 .. nchunk - 2;   L2(nchunk - 1)
+  //      Handing a chunk over means draining the wave's MFMAs, ~150 VALU instructions, twelve LDS stores and a barrier
+  //      before the first layer-2 operand can even be read: done between L1(c) and L2(c), that span is exposed once per chunk
+  //      (one wave per SIMD: nothing else feeds the matrix pipe meanwhile).  L2(c) does not touch acc1, so in the steady
+  //      state the hand-over of chunk c + 1 issues in the shadow of L2(c)'s MFMAs (stage()); only the first one of a panel
+  //      stays exposed.  Every acc1 chunk sums the same k-steps and terms in the same order and acc2 takes the chunks in the
+  //      same order as a walk without the skew: the results are bit-identical to it.
+  //      `hbuf` holds one chunk: chunk c + 1 is stored in the last stage of L2(c), after the top barrier that follows
+  //      everybody's last read of chunk c, and published by the next top barrier.
+  // one stage of the walk: S as in stage(), HO its flavour, cb the chunk position whose layer-1 bias stage 0 fetches
+  auto walk_stage = [&](auto S, auto HOc, int cb) {
+    constexpr int s = decltype(S)::value;
+    constexpr bool HO = decltype(HOc)::value != 0;
+    const int sn = slot == 2 ? 0 : slot + 1;       // slot of stage g + 1
+#ifdef EGTR_FFN_X6_TIMING
+    if constexpr (HO && (s == 0 || s == 4 || s == 7)) FFN_T(ts[s]);
+    if constexpr (!HO && (s == 4 || s == 5)) FFN_T(ts[s]);
+#endif
+    stage_top();
+    if constexpr (s == 4 && !HO) {   // the last layer-2 group: the chunk was stored by the stage before, visible after this barrier
+      a0[0][0] = frag(ph + 0 * kFrag);
+      a0[0][1] = frag(ph + 1 * kFrag);
+      a0[1][0] = frag(ph + 2 * kFrag);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    if constexpr (s == 0) {
+      // the previous hand-over has consumed acc1 (program order)
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc1[t][r] = 0.f;
+      // the chunk's 32 layer-1 bias values of this wave (wave-uniform) as SCALAR loads, stages ahead of their use.
+      // (A vector load here would be waited for with vmcnt(0) by the compiler -- draining the two stages of DMA in
+      // flight: measured 35 of 91 us.)  Sound only while the compiler does not spill these SGPRs while the loads are in
+      // flight: tests/test_build_resources.py fails the build if this kernel has any SGPR spill.
+      const float* bp = A.b1 + 64 * chunk_of(cb) + 32 * wn;
+      asm volatile("s_load_dwordx8 %0, %4, 0x0\n\ts_load_dwordx8 %1, %4, 0x20\n\ts_load_dwordx8 %2, %4, 0x40\n\t"
+                   "s_load_dwordx8 %3, %4, 0x60"
+                   : "=&s"(bias[0]), "=&s"(bias[1]), "=&s"(bias[2]), "=&s"(bias[3])
+                   : "s"(bp));
+    }
+    if constexpr (s == 4 && HO)   // the bias values of the hand-over behind this group's MFMAs (fetched four stages ago)
+      asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(bias[0]), "+s"(bias[1]), "+s"(bias[2]), "+s"(bias[3]));
+    if constexpr ((s & 1) == 0) stage(S, HOc, w0, w1, a0, a1, g, sn, slot);
+    else stage(S, HOc, w1, w0, a1, a0, g, sn, slot);
+    slot = sn;
+    ++g;
+  };
+  constexpr std::integral_constant<int, 0> kPlain{};
+  constexpr std::integral_constant<int, 1> kSteady{};
+#ifdef EGTR_FFN_X6_TIMING
+  FFN_T(tl0);
+#endif
+  static_for<4>([&](auto S) { walk_stage(S, kPlain, 0); });
+#ifdef EGTR_FFN_X6_TIMING
+  FFN_T(th);
+#endif
+  // the first hand-over of the panel, exposed.  The bias values: SCALAR loads (they do not touch the vmcnt queue the DMA
+  // waits are counted on).
+  asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(bias[0]), "+s"(bias[1]), "+s"(bias[2]), "+s"(bias[3]));
+  static_for<16>([&](auto E) {
+    ho_value(E);
+    if constexpr (decltype(E)::value & 1) ho_pack(std::integral_constant<int, (decltype(E)::value >> 1)>{});
+  });
+  static_for<12>([&](auto N) { ho_store(N); });
+#ifdef EGTR_FFN_X6_TIMING
+  FFN_T(te);
+  tsum[4] = te - th;
+#endif
 #pragma unroll 1
-  for (int c = 0; c < nchunk; ++c) {
-    static_for<8>([&](auto S) {
-      constexpr int s = decltype(S)::value;
-      const int sn = slot == 2 ? 0 : slot + 1;       // slot of stage g + 1
-      stage_top();
-      if constexpr (s == 4) {          // the hidden chunk was written by the stage before: visible after this barrier
-        a0[0][0] = frag(ph + 0 * kFrag);
-        a0[0][1] = frag(ph + 1 * kFrag);
-        a0[1][0] = frag(ph + 2 * kFrag);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      if constexpr (s == 0) {
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc1[t][r] = 0.f;
-        // the chunk's 32 layer-1 bias values of this wave (wave-uniform) as SCALAR loads, three stages ahead of their use.
-        // (A vector load here would be waited for with vmcnt(0) by the compiler -- draining the two stages of DMA in
-        // flight: measured 35 of 91 us.)  Sound only while the compiler does not spill these SGPRs while the loads are in
-        // flight: tests/test_build_resources.py fails the build if this kernel has any SGPR spill.
-        const float* bp = A.b1 + 64 * chunk_of(c) + 32 * wn;
-        asm volatile("s_load_dwordx8 %0, %4, 0x0\n\ts_load_dwordx8 %1, %4, 0x20\n\ts_load_dwordx8 %2, %4, 0x40\n\t"
-                     "s_load_dwordx8 %3, %4, 0x60"
-                     : "=&s"(bias[0]), "=&s"(bias[1]), "=&s"(bias[2]), "=&s"(bias[3])
-                     : "s"(bp));
-      }
-      if constexpr ((s & 1) == 0) stage(S, w0, w1, a0, a1, g, sn, slot);
-      else stage(S, w1, w0, a1, a0, g, sn, slot);
-      if constexpr (s == 3) {
-        // bias + ReLU + split of the wave's 32 x 32 piece of the hidden chunk -> XS fragments in LDS.  The 32 bias values
-        // are wave-uniform: SCALAR loads (they do not touch the vmcnt queue the DMA waits are counted on).
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(bias[0]), "+s"(bias[1]), "+s"(bias[2]), "+s"(bias[3]));
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          float h[4];
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const float blo = bias[q][j], bhi = bias[q][4 + j];   // bias[q] = values 8 q .. 8 q + 7 of the 32
-            h[j] = egtr_relu(acc1[0][4 * q + j] + acc1[1][4 * q + j] + (hf ? bhi : blo));
-          }
-          // hidden index inside the chunk: 32 wn + 8 q + 4 hf + j -> k-step 2 wn + (q >> 1), k-group q & 1
-          char* dst = hbuf + ((wm * 4 + 2 * wn + (q >> 1)) * 3) * kFrag + (q & 1) * 512 + li * 16 + hf * 8;
-          const xs::Split3 s0 = xs::split3_fast(h[0]), s1 = xs::split3_fast(h[1]), s2 = xs::split3_fast(h[2]),
-                           s3 = xs::split3_fast(h[3]);
-          *reinterpret_cast<uint2*>(dst) = make_uint2(xs::pack_hi16(s0.hi, s1.hi), xs::pack_hi16(s2.hi, s3.hi));
-          *reinterpret_cast<uint2*>(dst + kFrag) = make_uint2(xs::pack_hi16(s0.mid, s1.mid), xs::pack_hi16(s2.mid, s3.mid));
-          *reinterpret_cast<uint2*>(dst + 2 * kFrag) = make_uint2(xs::pack_hi16(s0.lo, s1.lo), xs::pack_hi16(s2.lo, s3.lo));
-        }
-      }
-      slot = sn;
-      ++g;
-    });
+  for (int c = 0; c + 1 < nchunk; ++c) {
+    static_for<8>([&](auto S) { walk_stage(S, kSteady, c + 1); });
+#ifdef EGTR_FFN_X6_TIMING
+    FFN_T(te);
+    tsum[0] += ts[4] - ts[0];   // L1 stages 0 .. 3
+    tsum[2] += ts[7] - ts[4];   // L2 stages 0 .. 2, the hand-over's VALU work behind their MFMAs
+    tsum[3] += te - ts[7];      // L2 stage 3, the hand-over's LDS stores behind its MFMAs
+#endif
   }
+  static_for<4>([&](auto S) { walk_stage(std::integral_constant<int, 4 + decltype(S)::value>{}, kPlain, 0); });
+#ifdef EGTR_FFN_X6_TIMING
+  unsigned tl1;
+  FFN_T(tl1);
+#endif
   wait_vm<0>();   // the surplus re-loads of the tail must have landed before this workgroup's LDS can be handed on
-  final_epilogue<PROJ>(acc2, A, r0, wave, lane, reinterpret_cast<float*>(ring), [&](int t, int q) { return y1[t][q]; });
+  // The epilogue's arguments are read AGAIN from the kernel-argument segment (the pointer laundered, so that the loads stay
+  // behind the walk): ~16 scalar registers of pointers and sizes nobody needs inside the walk would otherwise be live through
+  // it, next to the 32 of the bias values -- and this kernel must not spill a scalar register (tests/test_build_resources.py).
+#if defined(__HIP_DEVICE_COMPILE__)
+  typedef const __attribute__((address_space(4))) unsigned* KernargWords;
+  KernargWords ka = (KernargWords)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(ka));
+  FfnArgs Ae;   // FfnArgs is the kernel's only argument: offset 0 of the segment
+  static_assert(sizeof(FfnArgs) % 4 == 0, "copied in 32-bit words");
+#pragma unroll
+  for (unsigned i = 0; i < sizeof(FfnArgs) / 4; ++i) reinterpret_cast<unsigned*>(&Ae)[i] = ka[i];
+  // a pointer that comes out of memory is a generic one (flat loads and stores): build the epilogue's pointers from their
+  // bits as GLOBAL pointers, which is what kernel arguments are
+  auto global_ptr = [&](size_t offset) {
+    typedef const __attribute__((address_space(4))) unsigned long long* KernargQuads;
+    const unsigned long long bits = *(KernargQuads)((const __attribute__((address_space(4))) char*)ka + offset);
+    return (float*)(__attribute__((address_space(1))) float*)bits;
+  };
+  Ae.res = global_ptr(offsetof(FfnArgs, res)); Ae.b2 = global_ptr(offsetof(FfnArgs, b2));
+  Ae.gamma = global_ptr(offsetof(FfnArgs, gamma)); Ae.beta = global_ptr(offsetof(FfnArgs, beta));
+  Ae.pos = global_ptr(offsetof(FfnArgs, pos)); Ae.out = global_ptr(offsetof(FfnArgs, out));
+  Ae.out_pos = global_ptr(offsetof(FfnArgs, out_pos));
+#else
+  const FfnArgs& Ae = A;
+#endif
+  final_epilogue<PROJ>(acc2, Ae, r0, wave, lane, reinterpret_cast<float*>(ring), [&](int t, int q) { return y1[t][q]; });
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#ifdef EGTR_FFN_X6_TIMING
+  unsigned tk1;
+  FFN_T(tk1);
+  if (tid == 0 && blockIdx.x < kRecWg) {
+    unsigned* rec = g_ffn_x6_rec[blockIdx.x];
+    for (int k = 0; k < 5; ++k) rec[k] = tsum[k];
+    rec[5] = ts[5] - ts[4];   // stage 0 of the last layer-2 group: its operand is read after the top barrier
+    rec[6] = tl1 - tl0;       // the FFN walk
+    rec[7] = tk1 - tk0;       // the workgroup
+    rec[8] = tl0 - tk0;       // everything in front of the FFN walk
+  }
+#endif
 }
 
 
@@ -632,6 +829,13 @@ __global__ __launch_bounds__(256, 1) void proj_x6_kernel(FfnArgs A) {
 }
 
 }  // namespace
+
+#ifdef EGTR_FFN_X6_TIMING
+extern "C" int egtr_ffn_x6_stamps(unsigned* host_out) {   // host_out: kRecWg x kRecN
+  return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_ffn_x6_rec), sizeof(unsigned) * kRecWg * kRecN) == hipSuccess ? EGTR_OK
+                                                                                                                  : EGTR_E_LAUNCH;
+}
+#endif
 
 extern "C" int egtr_ffn_x6_f32(egtr_stream_t stream, const float* x, int ldx, const void* w1_xs, const float* b1,
                                const void* w2_xs, const float* b2, const float* ln_gamma, const float* ln_beta, float eps,

@@ -1,15 +1,21 @@
 // Stand-alone development harness of the encoder-tail kernel (csrc/ffn_x6.hip, ffn_x6_kernel<true>): launch time on random
-// inputs (correctness: tests/test_gpu_pinning.py; the cycle-stamp instrumentation of round 3 is in the history, 7146666).
+// inputs (correctness: tests/test_gpu_pinning.py, tests/test_gpu_ffn_handover.py).  With -DEGTR_FFN_X6_TIMING on the same command
+// line: the kernel's cycle stamps around the stages of the FFN walk and its hand-over (profiles/ffn_x6_handover_ab.txt).
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/enc_tail_bench.hip egtr_amd/csrc/ffn_x6.hip \
 //         egtr_amd/csrc/xs_split.hip egtr_amd/csrc/capi.hip -o build/enc_tail_bench && build/enc_tail_bench [M F iters with_pos]
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <random>
 #include <vector>
 
 #include "../include/egtr_hip.h"
+
+#ifdef EGTR_FFN_X6_TIMING
+extern "C" int egtr_ffn_x6_stamps(unsigned* host_out);   // csrc/ffn_x6.hip, stamp build: [256 workgroups][24]
+#endif
 
 #define CK(x)                                                                   \
   do {                                                                          \
@@ -70,5 +76,32 @@ int main(int argc, char** argv) {
   float ms;
   CK(hipEventElapsedTime(&ms, e0, e1));
   printf("M=%d F=%d: %.2f us per launch\n", M, F, ms * 1e3 / iters);
+#ifdef EGTR_FFN_X6_TIMING
+  {
+    // mean / min / max over the workgroups of the last launch; the steady-state sums per stage
+    static const char* const names[9] = {"steady state: L1 stages 0-3, per stage", nullptr,
+                                         "steady state: L2 stages 0-2 (hand-over VALU behind the MFMAs), per stage",
+                                         "steady state: L2 stage 3 (hand-over LDS stores behind the MFMAs)",
+                                         "first hand-over, exposed (last L1 MFMA to the next top), per panel",
+                                         "last L2 group, stage 0 (operand read after the top), per panel", "FFN walk, per panel",
+                                         "workgroup, per panel", "in front of the FFN walk, per panel"};
+    static const int per[9] = {4, 0, 3, 1, 0, 0, 0, 0, 0};   // stages summed per steady-state iteration; 0: once per panel
+    std::vector<unsigned> rec(256 * 24);
+    if (egtr_ffn_x6_stamps(rec.data())) return 2;
+    const int nwg = std::min(256, (M + 63) / 64), nchunk = F / 64;
+    for (int k = 0; k < 9; ++k) {
+      if (names[k] == nullptr) continue;
+      double sum = 0, lo = 1e30, hi = 0;
+      const double div = per[k] ? per[k] * std::max(1, nchunk - 1) : 1;
+      for (int b = 0; b < nwg; ++b) {
+        const double v = rec[b * 24 + k] / div;
+        sum += v;
+        lo = std::min(lo, v);
+        hi = std::max(hi, v);
+      }
+      printf("  %-74s mean %9.0f  min %9.0f  max %9.0f cycles%s\n", names[k], sum / nwg, lo, hi, "");
+    }
+  }
+#endif
   return 0;
 }
