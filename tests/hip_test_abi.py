@@ -42,6 +42,24 @@ def msda_forward_variant(value, spatial_shapes, level_start_index, sampling_loc,
     return out
 
 
+def msda_forward_fused_bf16_byte_mask(value, spatial_shapes, level_start_index, sampling_offsets, attn_logits, reference_points,
+                                      keep_mask):
+    """egtr_msda_forward_fused_bf16 with its BYTE mask parameter (include/egtr_hip.h), which the product binding never passes: it
+    packs the mask into bits.  Contiguous bf16 operands, keep_mask [B, S] uint8."""
+    B, S, M, D = value.shape
+    L = spatial_shapes.shape[0]
+    Lq, P = sampling_offsets.shape[1], sampling_offsets.shape[4]
+    for t, n in ((value, "value"), (sampling_offsets, "sampling_offsets"), (attn_logits, "attn_logits"),
+                 (reference_points, "reference_points")):
+        _chk(t, n, torch.bfloat16)
+    _chk(keep_mask, "keep_mask", torch.uint8)
+    out = torch.empty(B, Lq, M * D, dtype=torch.bfloat16, device=value.device)
+    _lib.launch("egtr_msda_forward_fused_bf16", value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(),
+                sampling_offsets.data_ptr(), attn_logits.data_ptr(), reference_points.data_ptr(), B, S, M, D, L, Lq, P,
+                out.data_ptr(), M * L * P * 2, M * L * P, keep_mask.data_ptr(), None, what="egtr_msda_forward_fused_bf16(byte mask)")
+    return out
+
+
 def msda_backward_variant(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output, variant):
     """fp32 backward with an explicit kernel choice (include/egtr_hip_test.h)."""
     h = _handle()
