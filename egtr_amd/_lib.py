@@ -118,6 +118,9 @@ SIGNATURES = {
     "egtr_relation_loss_det_workspace_bytes": [_I, _I],
     "egtr_relation_loss_det_f32": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, ctypes.c_float, _I, _I, _P, _P, _P, _P],
     "egtr_relation_loss_det_bits_f32": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, ctypes.c_float, _I, _I, _P, _P, _P, _P],
+    "egtr_relation_loss_all_workspace_bytes": [_I, _I],
+    "egtr_relation_loss_all_f32": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, ctypes.c_float, _P, _P, _P, _P],
+    "egtr_relation_loss_all_bits_f32": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, ctypes.c_float, _P, _P, _P, _P],
     "egtr_pack_relations_u64": [_P, _P, _P, _I, _I, _I, _I, _P],
     "egtr_rel_head_forward_bf16w": [_P] * 16 + [_I] * 6 + [_P] * 3,
     "egtr_ffn_layernorm_bf16": [_P] * 7 + [ctypes.c_float, _P, _I, _P, _P, _I, _I, _I],
@@ -177,6 +180,7 @@ _RESTYPES = {"egtr_status_string": ctypes.c_char_p, "egtr_last_hip_error": ctype
              "egtr_msda_backward_bf16_workspace_floats": ctypes.c_longlong,
              "egtr_msda_backward_det_workspace_bytes": ctypes.c_longlong,
              "egtr_relation_loss_det_workspace_bytes": ctypes.c_longlong,
+             "egtr_relation_loss_all_workspace_bytes": ctypes.c_longlong,
              "egtr_hungarian_match_scratch_doubles": ctypes.c_longlong,
              "egtr_relation_loss_workspace_bytes": ctypes.c_longlong,
              "egtr_column_sum_workspace_floats": ctypes.c_longlong,

@@ -16,6 +16,8 @@
 // All counts stay on the device; the only inputs from the host are tensor shapes.
 // The passes that read the target are templates on a target accessor: dense fp32 [N, N, R] per image (the reference's format,
 // egtr_relation_loss_f32) or one 64-bit word per (subject, object) pair (egtr_relation_loss_bits_f32).
+// Evaluation mode (and training with both sample counts None) selects nothing: BCE over all elements, egtr_relation_loss_all_*:
+// maps | all-elements pass | connectivity | finalize.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -108,15 +110,11 @@ struct PackedTarget {   // [B, N, N] 64-bit words, bit r of word (row, col) = th
 
 constexpr int kPrepT = 1024;   // one workgroup per image, sixteen waves: the T x T x R count below is ~500 dependent gathers per thread with four
 // ---- prep: per image  tq (query -> target row), wq (1 - sigmoid(matching cost)), mq (matched), block counts ------------
-template <class Tgt>
-__global__ __launch_bounds__(kPrepT) void rel_loss_prep(const int64_t* __restrict__ pred_idx,
-                                                     const int64_t* __restrict__ tgt_idx,
-                                                     const float* __restrict__ match_cost,
-                                                     const int* __restrict__ out_off,
-                                                     const Tgt target_rel, int N, int R,
-                                                     float nonmatching_cost, int k_neg, int k_nm, ImgState* st,
-                                                     int* tq, float* wq, unsigned char* mq, int* total_sel) {
-  __shared__ int s_cnt[2];
+// The maps of one image, shared by the sampled and the un-sampled route; every thread of the workgroup (kPrepT) calls it and
+// gets T back (0 for an image the matcher refused).  Ends on a barrier: tq / wq / mq of the image are complete for the caller.
+__device__ __forceinline__ int rel_prep_maps(const int64_t* __restrict__ pred_idx, const int64_t* __restrict__ tgt_idx,
+                                             const float* __restrict__ match_cost, const int* __restrict__ out_off, int N,
+                                             float nonmatching_cost, int* tq, float* wq, unsigned char* mq) {
   __shared__ int s_scan[kPrepT];
   const int b = blockIdx.x, tid = threadIdx.x;
   const int o0 = out_off[b];
@@ -134,7 +132,6 @@ __global__ __launch_bounds__(kPrepT) void rel_loss_prep(const int64_t* __restric
   int* tq_b = tq + (size_t)b * N;
   float* wq_b = wq + (size_t)b * N;
   unsigned char* mq_b = mq + (size_t)b * N;
-  if (tid < 2) s_cnt[tid] = 0;
   for (int q = tid; q < N; q += kPrepT) { mq_b[q] = 0; wq_b[q] = 1.0f - 1.0f / (1.0f + expf(-nonmatching_cost)); }
   __syncthreads();
   for (int t = tid; t < T; t += kPrepT) {
@@ -161,6 +158,22 @@ __global__ __launch_bounds__(kPrepT) void rel_loss_prep(const int64_t* __restric
     base += s_scan[kPrepT - 1];
     __syncthreads();
   }
+  return T;
+}
+
+template <class Tgt>
+__global__ __launch_bounds__(kPrepT) void rel_loss_prep(const int64_t* __restrict__ pred_idx,
+                                                     const int64_t* __restrict__ tgt_idx,
+                                                     const float* __restrict__ match_cost,
+                                                     const int* __restrict__ out_off,
+                                                     const Tgt target_rel, int N, int R,
+                                                     float nonmatching_cost, int k_neg, int k_nm, ImgState* st,
+                                                     int* tq, float* wq, unsigned char* mq, int* total_sel) {
+  __shared__ int s_cnt[2];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int o0 = out_off[b];
+  if (tid < 2) s_cnt[tid] = 0;
+  const int T = rel_prep_maps(pred_idx, tgt_idx, match_cost, out_off, N, nonmatching_cost, tq, wq, mq);
   // counts over the matched block: true = target != 0, false candidates = target != 1 (egtr:838-840)
   int nt = 0, nf = 0;
   target_rel.image(b, N, R).count_block(tgt_idx + o0, T, N, tid, kPrepT, nt, nf);
@@ -187,6 +200,15 @@ __global__ __launch_bounds__(kPrepT) void rel_loss_prep(const int64_t* __restric
     st[b] = s;
     atomicAdd(total_sel, s.n_sel);
   }
+}
+
+// the maps alone: the un-sampled loss (rel_loss_all below) selects nothing, so it needs no block counts and no ImgState
+__global__ __launch_bounds__(kPrepT) void rel_all_prep(const int64_t* __restrict__ pred_idx,
+                                                       const int64_t* __restrict__ tgt_idx,
+                                                       const float* __restrict__ match_cost,
+                                                       const int* __restrict__ out_off, int N, float nonmatching_cost,
+                                                       int* tq, float* wq, unsigned char* mq) {
+  rel_prep_maps(pred_idx, tgt_idx, match_cost, out_off, N, nonmatching_cost, tq, wq, mq);
 }
 
 // ---- histogram pass: digit PASS (0: bits 31..21, 1: bits 20..10, 2: bits 9..0) of the candidates under the prefix --------
@@ -459,7 +481,84 @@ __global__ __launch_bounds__(kLT) void rel_loss_final(const float* __restrict__ 
   }
 }
 
+// ---- un-sampled relation loss (egtr:806-829 with both sample counts None: evaluation mode, validation_loss) ----------------
+// BCE over ALL N N R elements of an image against y = t(tq[qa], tq[qb], r) * (wq[qa] wq[qb]); the loss is a mean over every
+// element, so it is evaluated in query order through the maps of rel_prep_maps: no selection, no counts, no tickets.  One
+// workgroup per (image, subject query row): coalesced reads of the row's N R logits, one double partial per row (lanes by
+// shuffle tree, waves in index order), pair flags for conn_loss.  GRAD = false (validation runs under no_grad): nothing but the
+// partial and the flags is written.  inv_cnt = 1 / (B N N R).
+template <class Tgt, bool GRAD>
+__global__ __launch_bounds__(kLT) void rel_loss_all(const float* __restrict__ pred_rel, const Tgt target_rel, int N, int R,
+                                                    const int* __restrict__ tq, const float* __restrict__ wq, float inv_cnt,
+                                                    float* __restrict__ grad_rel, unsigned char* __restrict__ pairflag,
+                                                    double* __restrict__ partial) {
+  __shared__ double s_red[kLT / 64];
+  const int b = blockIdx.y, qa = blockIdx.x, tid = threadIdx.x;
+  const int* tq_b = tq + (size_t)b * N;
+  const float* wq_b = wq + (size_t)b * N;
+  const typename Tgt::Image rel = target_rel.image(b, N, R);
+  const int NR = N * R;
+  const float* pr = pred_rel + ((size_t)b * N + qa) * NR;
+  unsigned char* pf = pairflag + ((size_t)b * N + qa) * N;
+  const float invR = 1.0f / (float)R;
+  // (a target row is < N for the matcher's one-to-one indices; the min keeps a malformed index list inside the target)
+  const size_t trow = (size_t)min(tq_b[qa], N - 1) * N;
+  const float wa = wq_b[qa];
+  double acc = 0.0;
+  for (int e = tid; e < NR; e += kLT) {
+    const int qb = (int)(((float)e + 0.5f) * invR);
+    const float t = rel.pair(trow + min(tq_b[qb], N - 1)).at(e - qb * R);
+    if (t != 0.f) pf[qb] = 1;                          // benign race: every writer stores 1
+    const float x = pr[e];
+    const float y = t * (wa * wq_b[qb]);               // target * weight[a] * weight[b]  (egtr:826-828)
+    acc += (double)bce_logits(x, y);
+    if constexpr (GRAD) grad_rel[((size_t)b * N + qa) * NR + e] = (1.0f / (1.0f + expf(-x)) - y) * inv_cnt;
+  }
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+  if ((tid & 63) == 0) s_red[tid >> 6] = acc;
+  __syncthreads();
+  if (tid == 0) {
+    double t = 0.0;
+    for (int w = 0; w < kLT / 64; ++w) t += s_red[w];
+    partial[(size_t)b * N + qa] = t;
+  }
+}
+
+// one workgroup: both sums in a fixed order -- every thread a contiguous run of partials in index order, lanes by shuffle tree,
+// waves in index order -- then the two fp32 means
+__global__ __launch_bounds__(kLT) void rel_loss_all_finalize(const double* __restrict__ partial_rel, int n_rel,
+                                                             const double* __restrict__ partial_conn, int n_conn,
+                                                             double n_elem, double n_pairs, float* __restrict__ loss_out) {
+  __shared__ double s_fin[2][kLT / 64];
+  const int tid = threadIdx.x;
+  const int cr = (n_rel + kLT - 1) / kLT, cc = (n_conn + kLT - 1) / kLT;
+  double sr = 0.0, sc = 0.0;
+  for (int i = tid * cr; i < min((tid + 1) * cr, n_rel); ++i) sr += partial_rel[i];
+  for (int i = tid * cc; i < min((tid + 1) * cc, n_conn); ++i) sc += partial_conn[i];
+  for (int o = 32; o > 0; o >>= 1) {
+    sr += __shfl_xor(sr, o);
+    sc += __shfl_xor(sc, o);
+  }
+  if ((tid & 63) == 0) {
+    s_fin[0][tid >> 6] = sr;
+    s_fin[1][tid >> 6] = sc;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double tr = 0.0, tc = 0.0;
+    for (int w = 0; w < kLT / 64; ++w) {
+      tr += s_fin[0][w];
+      tc += s_fin[1][w];
+    }
+    loss_out[0] = (float)(tr / n_elem);
+    loss_out[1] = (float)(tc / n_pairs);
+  }
+}
+
 // ---- connectivity BCE (egtr:786-793, 815) + final reduction of both losses (last workgroup, fixed order) ----------------
+// FINAL = false (the un-sampled route): the partials only, summed by rel_loss_all_finalize -- no ticket, no total_sel;
+// GRAD = false: no gradient is written (grad_conn may be NULL).
+template <bool FINAL = true, bool GRAD = true>
 __global__ __launch_bounds__(kLT) void conn_loss(const float* __restrict__ pred_conn,
                                                  const unsigned char* __restrict__ pairflag, long long n_pairs,
                                                  float* __restrict__ grad_conn, double* __restrict__ partial_conn,
@@ -474,7 +573,7 @@ __global__ __launch_bounds__(kLT) void conn_loss(const float* __restrict__ pred_
   for (long long i = (long long)blockIdx.x * kLT + tid; i < n_pairs; i += (long long)gridDim.x * kLT) {
     const float x = pred_conn[i], y = pairflag[i] ? 1.0f : 0.0f;
     acc += (double)bce_logits(x, y);
-    grad_conn[i] = (1.0f / (1.0f + expf(-x)) - y) * inv;
+    if constexpr (GRAD) grad_conn[i] = (1.0f / (1.0f + expf(-x)) - y) * inv;
   }
   for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
   if ((tid & 63) == 0) s_red[tid >> 6] = acc;
@@ -483,9 +582,11 @@ __global__ __launch_bounds__(kLT) void conn_loss(const float* __restrict__ pred_
     double t = 0.0;
     for (int w = 0; w < kLT / 64; ++w) t += s_red[w];
     partial_conn[blockIdx.x] = t;
+    if constexpr (!FINAL) return;
     __threadfence();
     s_last = atomicAdd(done, 1u) == gridDim.x - 1;
   }
+  if constexpr (!FINAL) return;
   __syncthreads();
   if (s_last) {
     // The last workgroup sums the partials of both losses -- every thread a fixed strided share, then lanes and waves in a fixed
@@ -605,8 +706,8 @@ static int relation_loss_launch(egtr_stream_t stream, const float* pred_rel, con
   }
   const long long n_pairs = B * N * N;
   const int cblocks = (int)std::min<long long>((n_pairs + kLT - 1) / kLT, 1024);
-  hipLaunchKernelGGL(conn_loss, dim3(cblocks), dim3(kLT), 0, st, pred_conn, pairflag, n_pairs, grad_conn, partial_conn,
-                     partial_rel, (int)(B * rows), total_sel, done, loss_out);
+  hipLaunchKernelGGL((conn_loss<true, true>), dim3(cblocks), dim3(kLT), 0, st, pred_conn, pairflag, n_pairs, grad_conn,
+                     partial_conn, partial_rel, (int)(B * rows), total_sel, done, loss_out);
   return egtr_check_launch();
 }
 
@@ -665,6 +766,99 @@ extern "C" int egtr_relation_loss_det_bits_f32(egtr_stream_t stream, const float
                               PackedTarget{reinterpret_cast<const unsigned long long*>(rel_bits)}, pred_idx, tgt_idx,
                               match_cost, out_offsets, batch, num_query, num_rel, nonmatching_cost, sample_negatives,
                               sample_nonmatching, loss_out, grad_rel, grad_conn, workspace, true);
+}
+
+// ---- un-sampled entries (evaluation mode / both sample counts None): BCE over every element, see rel_loss_all ------------
+// Launches: maps | all-elements pass | connectivity | finalize.  Deterministic by construction (no atomics on values, no tickets).
+// workspace layout: tq, wq [B, N] | mq [B N] | pair flags [B N N] | partial sums: B N of the relations, kAllConnBlocks of the connectivity
+namespace {
+constexpr int kAllConnBlocks = 1024;
+}
+
+extern "C" long long egtr_relation_loss_all_workspace_bytes(int batch, int num_query) {
+  if (batch <= 0 || num_query <= 0) return 0;
+  const long long B = batch, N = num_query;
+  long long bytes = B * N * 4 * 2;             // tq, wq
+  bytes += ((B * N + 15) / 16) * 16;           // mq
+  bytes += ((B * N * N + 15) / 16) * 16;       // pairflag
+  bytes += (B * N + kAllConnBlocks) * 8;       // partial sums (relations + connectivity)
+  return bytes + 256;
+}
+
+template <class Tgt>
+static int relation_loss_all_launch(egtr_stream_t stream, const float* pred_rel, const float* pred_conn, const Tgt target_rel,
+                                    const int64_t* pred_idx, const int64_t* tgt_idx, const float* match_cost,
+                                    const int* out_offsets, int batch, int num_query, int num_rel, float nonmatching_cost,
+                                    float* loss_out, float* grad_rel, float* grad_conn, void* workspace) {
+  if (!pred_rel || !pred_conn || !pred_idx || !tgt_idx || !match_cost || !out_offsets || !loss_out || !workspace)
+    return EGTR_E_ARG;
+  if ((grad_rel == nullptr) != (grad_conn == nullptr)) return EGTR_E_ARG;   // value-only: both NULL
+  if (batch <= 0 || num_query <= 0 || num_rel <= 0) return EGTR_E_ARG;
+  if ((long long)num_query * num_rel >= (1 << 22) || num_query > 4096 || batch > 65535) return EGTR_E_UNSUPPORTED;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const long long B = batch, N = num_query;
+  char* p = static_cast<char*>(workspace);
+  int* tq = reinterpret_cast<int*>(p);
+  p += B * N * 4;
+  float* wq = reinterpret_cast<float*>(p);
+  p += B * N * 4;
+  unsigned char* mq = reinterpret_cast<unsigned char*>(p);
+  p += ((B * N + 15) / 16) * 16;
+  unsigned char* pairflag = reinterpret_cast<unsigned char*>(p);
+  const size_t flag_bytes = (size_t)(((B * N * N + 15) / 16) * 16);
+  p += flag_bytes;
+  p = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(p) + 7) & ~(uintptr_t)7);
+  double* partial_rel = reinterpret_cast<double*>(p);
+  double* partial_conn = partial_rel + B * N;
+  if (hipMemsetAsync(pairflag, 0, flag_bytes, st) != hipSuccess) return EGTR_E_LAUNCH;
+  hipLaunchKernelGGL(rel_all_prep, dim3(batch), dim3(kPrepT), 0, st, pred_idx, tgt_idx, match_cost, out_offsets, num_query,
+                     nonmatching_cost, tq, wq, mq);
+  const double n_pairs = (double)(B * N * N), n_elem = n_pairs * (double)num_rel;
+  const float inv_cnt = (float)(1.0 / n_elem);
+  const dim3 ga(num_query, batch);
+  const long long np = B * N * N;
+  const int cblocks = (int)std::min<long long>((np + kLT - 1) / kLT, kAllConnBlocks);
+  if (grad_rel) {
+    hipLaunchKernelGGL((rel_loss_all<Tgt, true>), ga, dim3(kLT), 0, st, pred_rel, target_rel, num_query, num_rel,
+                       (const int*)tq, (const float*)wq, inv_cnt, grad_rel, pairflag, partial_rel);
+    hipLaunchKernelGGL((conn_loss<false, true>), dim3(cblocks), dim3(kLT), 0, st, pred_conn, pairflag, np, grad_conn,
+                       partial_conn, (const double*)nullptr, 0, (const int*)nullptr, (unsigned*)nullptr, (float*)nullptr);
+  } else {
+    hipLaunchKernelGGL((rel_loss_all<Tgt, false>), ga, dim3(kLT), 0, st, pred_rel, target_rel, num_query, num_rel,
+                       (const int*)tq, (const float*)wq, inv_cnt, (float*)nullptr, pairflag, partial_rel);
+    hipLaunchKernelGGL((conn_loss<false, false>), dim3(cblocks), dim3(kLT), 0, st, pred_conn, pairflag, np, (float*)nullptr,
+                       partial_conn, (const double*)nullptr, 0, (const int*)nullptr, (unsigned*)nullptr, (float*)nullptr);
+  }
+  hipLaunchKernelGGL(rel_loss_all_finalize, dim3(1), dim3(kLT), 0, st, (const double*)partial_rel, (int)(B * N),
+                     (const double*)partial_conn, cblocks, n_elem, n_pairs, loss_out);
+  return egtr_check_launch();
+}
+
+// The arguments of egtr_relation_loss_f32 without the two sample counts.  grad_rel / grad_conn: both device buffers, or both
+// NULL for the value alone (nothing of their size is written).
+extern "C" int egtr_relation_loss_all_f32(egtr_stream_t stream, const float* pred_rel, const float* pred_conn,
+                                          const float* const* target_rel, const int64_t* pred_idx, const int64_t* tgt_idx,
+                                          const float* match_cost, const int* out_offsets, int batch, int num_query,
+                                          int num_rel, float nonmatching_cost, float* loss_out, float* grad_rel,
+                                          float* grad_conn, void* workspace) {
+  if (!target_rel) return EGTR_E_ARG;
+  return relation_loss_all_launch(stream, pred_rel, pred_conn, DenseTarget{target_rel}, pred_idx, tgt_idx, match_cost,
+                                  out_offsets, batch, num_query, num_rel, nonmatching_cost, loss_out, grad_rel, grad_conn,
+                                  workspace);
+}
+
+// packed words: the same passes, order and arithmetic -- the same bits as the dense entry on the dense form of the same target
+extern "C" int egtr_relation_loss_all_bits_f32(egtr_stream_t stream, const float* pred_rel, const float* pred_conn,
+                                               const uint64_t* rel_bits, const int64_t* pred_idx, const int64_t* tgt_idx,
+                                               const float* match_cost, const int* out_offsets, int batch, int num_query,
+                                               int num_rel, float nonmatching_cost, float* loss_out, float* grad_rel,
+                                               float* grad_conn, void* workspace) {
+  if (!rel_bits) return EGTR_E_ARG;
+  if (num_rel > 64) return EGTR_E_UNSUPPORTED;
+  return relation_loss_all_launch(stream, pred_rel, pred_conn,
+                                  PackedTarget{reinterpret_cast<const unsigned long long*>(rel_bits)}, pred_idx, tgt_idx,
+                                  match_cost, out_offsets, batch, num_query, num_rel, nonmatching_cost, loss_out, grad_rel,
+                                  grad_conn, workspace);
 }
 
 // ---- detection losses of one output set (labels / boxes / cardinality, egtr:611-659, 661-670, 692-712) ------------------

@@ -522,17 +522,25 @@ class SceneGraphGenerationLoss(nn.Module):
         device tensors with CPU index tensors, egtr:761-785; same values)."""
         dense = rel_targets.has_dense(targets)
         packed = not dense and not any("rel" in t for t in targets)   # every target carries ``rel_triplets`` only
-        if (self.model_training and outputs["pred_rel"].is_cuda and outputs["pred_rel"].dtype == torch.float32
-                and self.rel_sample_negatives is not None and self.rel_sample_nonmatching is not None
-                and self.rel_sample_negatives_largest and self.rel_sample_nonmatching_largest
+        sampled = (self.model_training and self.rel_sample_negatives is not None
+                   and self.rel_sample_nonmatching is not None
+                   and self.rel_sample_negatives_largest and self.rel_sample_nonmatching_largest)
+        # evaluation mode (validation_loss, egtr:806-809) and training without sampling: BCE over ALL elements
+        # (shapes beyond the entry's limits -- include/egtr_hip.h -- stay on the composition, as before)
+        B_, N_, _, R_ = outputs["pred_rel"].shape
+        unsampled = ops.RELATION_LOSS_ALL and N_ * R_ < (1 << 22) and N_ <= 4096 and B_ <= 65535 and (
+            not self.model_training or (self.rel_sample_negatives is None and self.rel_sample_nonmatching is None))
+        if ((sampled or unsampled) and outputs["pred_rel"].is_cuda and outputs["pred_rel"].dtype == torch.float32
                 and not self.force_device_relations
                 and ((dense and all(t["rel"].is_cuda and t["rel"].dtype == torch.float32 for t in targets))
                      or packed)):
-            # the training configuration (train_egtr.py:514-527): value and gradient in one HIP pass, no host sync;
-            # ``rel_triplets`` targets as packed words (no dense target is built), dense ``rel`` targets as they are
+            # the training configuration (train_egtr.py:514-527) and the un-sampled one: value and gradient in one HIP
+            # pipeline, no host sync; ``rel_triplets`` targets as packed words (no dense target is built), dense ``rel``
+            # targets as they are
             loss_rel, loss_conn = ops.relation_losses(
                 outputs["pred_rel"], outputs["pred_connectivity"], targets, indices, matching_costs,
-                float(self.nonmatching_cost), self.rel_sample_negatives, self.rel_sample_nonmatching,
+                float(self.nonmatching_cost), None if unsampled else self.rel_sample_negatives,
+                None if unsampled else self.rel_sample_nonmatching,
                 rel_bits=self._rel_bits(targets, outputs["pred_rel"].device) if packed else None)
             return {"loss_rel": loss_rel, "loss_connectivity": loss_conn}
         # every other route evaluates the reference's tensor composition on the dense target: ``rel_triplets`` targets are

@@ -9,7 +9,7 @@ from .._lib import _chk
 from .linear import _split3_bf16
 
 __all__ = ["rel_head_split_weights", "rel_head_streams", "relation_head_split_bf16", "relation_head_train_forward", "hungarian_match",
-           "pack_detection_targets", "pack_relation_bits", "relation_loss_launch"]
+           "pack_detection_targets", "pack_relation_bits", "relation_loss_launch", "relation_loss_all_launch"]
 
 
 def _rel_head_pieces(w, terms):
@@ -258,4 +258,23 @@ def relation_loss_launch(pred_rel, pred_conn, target, packed, pred_idx, tgt_idx,
                 pred_conn.data_ptr(), target.data_ptr(), pred_idx.data_ptr(), tgt_idx.data_ptr(), match_cost.data_ptr(),
                 out_off.data_ptr(), B, N, R, float(nonmatching_cost), int(sample_negatives), int(sample_nonmatching),
                 loss.data_ptr(), grad_rel.data_ptr(), grad_conn.data_ptr(), ws.data_ptr())
+    return loss, grad_rel, grad_conn
+
+
+def relation_loss_all_launch(pred_rel, pred_conn, target, packed, pred_idx, tgt_idx, match_cost, out_off, nonmatching_cost,
+                             want_grad=True):
+    """egtr_relation_loss_all_f32 / (``packed``) egtr_relation_loss_all_bits_f32: the un-sampled relation loss -- BCE over all
+    N N R elements -- and the connectivity loss; ``target`` as in ``relation_loss_launch``.  Returns (loss [2], grad_rel,
+    grad_conn); ``want_grad=False`` is the value-only launch: no gradient buffer is allocated or written, both come back None."""
+    B, N, _, R = pred_rel.shape
+    dev = pred_rel.device
+    if packed and tuple(_chk(target, "rel_bits", torch.int64).shape) != (B, N, N):
+        raise RuntimeError(f"rel_bits must have shape {(B, N, N)}, got {tuple(target.shape)}")
+    loss = torch.empty(2, dtype=torch.float32, device=dev)
+    grad_rel = torch.empty_like(pred_rel) if want_grad else None
+    grad_conn = torch.empty_like(pred_conn) if want_grad else None
+    ws = torch.empty(int(_lib.lib().egtr_relation_loss_all_workspace_bytes(B, N)), dtype=torch.uint8, device=dev)
+    _lib.launch("egtr_relation_loss_all_" + ("bits_f32" if packed else "f32"), pred_rel.data_ptr(), pred_conn.data_ptr(),
+                target.data_ptr(), pred_idx.data_ptr(), tgt_idx.data_ptr(), match_cost.data_ptr(), out_off.data_ptr(), B, N, R,
+                float(nonmatching_cost), loss.data_ptr(), _lib.ptr(grad_rel), _lib.ptr(grad_conn), ws.data_ptr())
     return loss, grad_rel, grad_conn

@@ -885,6 +885,8 @@ def decoder_layer_train(layer, x, pos, ref, value, spatial_shapes, level_start_i
 #   EGTR_MATMUL_PRECISION=bf16  ops.MATMUL_PRECISION        (opt-IN) training token GEMMs: six-term split-bf16, fp32 to the last bit  ->
 #                                                           ONE product per element, operands rounded once to bf16 (nearest even),
 #                                                           fp32 accumulation; see set_matmul_precision() below
+#   (module attribute only)     ops.RELATION_LOSS_ALL       un-sampled relation loss (evaluation mode; both rel_sample_* None): one HIP
+#                                                           pipeline over all elements  ->  the criterion's per-image tensor composition
 # Not route switches: EGTR_HIP_LIBRARY (another build of the library), EGTR_STRICT_FAST_PATH (below), EGTR_TRUST_CHECKPOINT_PICKLE.
 ENV_ROUTE_SWITCHES = ("EGTR_DECODER_CLUSTER", "EGTR_GEMM_SPLIT_BF16", "EGTR_REL_HEAD_SPLIT_BF16", "EGTR_FFN_FUSED",
                       "EGTR_BACKBONE_NHWC", "EGTR_ENCODER_TRAIN_FUSED", "EGTR_TOKEN_LINEAR", "EGTR_DETERMINISTIC",
@@ -1552,6 +1554,38 @@ class RelationLossFunction(Function):
         return grad_rel * g_rel, grad_conn * g_conn, None, None, None, None, None, None, None, None, None
 
 
+RELATION_LOSS_ALL = True   # module attribute (tests patch it for the switch-off twin); no environment switch
+
+
+class RelationLossAllFunction(Function):
+    """loss_rel / loss_connectivity of the SGG criterion WITHOUT sampling -- evaluation mode (validation_loss) and training with
+    both ``rel_sample_*`` None: BCE over all N N R elements (csrc/loss.hip, egtr_relation_loss_all_f32; ``packed``:
+    egtr_relation_loss_all_bits_f32).  ``want_grad``: None = when ``pred_rel`` or ``pred_conn`` requires grad; False is the
+    value-only launch -- no gradient buffer exists.  Backward only scales the stored gradients."""
+
+    @staticmethod
+    def forward(ctx, pred_rel, pred_conn, target, pred_idx, tgt_idx, match_cost, out_off, nonmatching_cost, packed=False,
+                want_grad=None):
+        pr = _chk(pred_rel.detach().contiguous(), "pred_rel", torch.float32)
+        pc = _chk(pred_conn.detach().contiguous(), "pred_connectivity", torch.float32)
+        if want_grad is None:
+            want_grad = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        loss, grad_rel, grad_conn = relation_loss_all_launch(pr, pc, target, packed, pred_idx, tgt_idx, match_cost, out_off,
+                                                             nonmatching_cost, want_grad=bool(want_grad))
+        ctx.has_grad = bool(want_grad)
+        if ctx.has_grad:
+            ctx.save_for_backward(grad_rel, grad_conn)
+        return loss[0], loss[1]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_rel, g_conn):
+        if not ctx.has_grad:
+            raise RuntimeError("RelationLossAllFunction ran its value-only launch (want_grad=False): there is no gradient")
+        grad_rel, grad_conn = ctx.saved_tensors
+        return grad_rel * g_rel, grad_conn * g_conn, None, None, None, None, None, None, None, None
+
+
 class ClampNonFiniteFunction(Function):
     """dd:1346-1351 ("clamp the states iff any element is inf / nan") with the decision on the device: one reduction pass
     raises a flag, the in-place clamp and the gradient mask return at once while it is clear (csrc/elementwise.hip)."""
@@ -1646,7 +1680,13 @@ def relation_losses(pred_rel, pred_conn, targets, indices, matching_costs, nonma
     """(loss_rel, loss_connectivity) for device tensors: see RelationLossFunction.  ``indices`` / ``matching_costs``: the
     matcher's per-image device tensors; ``targets[b]["rel"]``: dense fp32 [N, N, R] on the device.  Targets that carry
     ``"rel_triplets"`` and no ``"rel"`` take the packed entry: ``rel_bits`` (``egtr_amd.targets.pack_relations``) when the
-    caller packed the batch already, else packed here -- no dense target exists on that route."""
+    caller packed the batch already, else packed here -- no dense target exists on that route.
+    ``sample_negatives`` and ``sample_nonmatching`` both None: the un-sampled loss over all elements
+    (RelationLossAllFunction; value-only when nothing requires grad).  Exactly one None is not a kernel route (the criterion
+    keeps that configuration on its tensor composition): ValueError."""
+    if (sample_negatives is None) != (sample_nonmatching is None):
+        raise ValueError("relation_losses takes both sample counts or neither: with exactly one of sample_negatives / "
+                         "sample_nonmatching None the criterion's tensor route (_loss_relations_device) evaluates the loss")
     dev = pred_rel.device
     packed = not rel_targets.has_dense(targets)
     if packed:
@@ -1671,8 +1711,13 @@ def relation_losses(pred_rel, pred_conn, targets, indices, matching_costs, nonma
         pi = torch.zeros(1, dtype=torch.int64, device=dev)
         ti = torch.zeros(1, dtype=torch.int64, device=dev)
         mc = torch.zeros(1, dtype=torch.float32, device=dev)
-    out = RelationLossFunction.apply(pred_rel, pred_conn, target, pi, ti, mc, out_off, nonmatching_cost,
-                                     sample_negatives, sample_nonmatching, packed)
+    if sample_negatives is None:
+        want_grad = torch.is_grad_enabled() and (pred_rel.requires_grad or pred_conn.requires_grad)
+        out = RelationLossAllFunction.apply(pred_rel, pred_conn, target, pi, ti, mc, out_off, nonmatching_cost, packed,
+                                            want_grad)
+    else:
+        out = RelationLossFunction.apply(pred_rel, pred_conn, target, pi, ti, mc, out_off, nonmatching_cost,
+                                         sample_negatives, sample_nonmatching, packed)
     if not packed:
         del rels   # (kept alive until the launches were enqueued; the caller's targets own the storage)
     return out

@@ -483,6 +483,50 @@ class DataParallelTrainer:
             self.opt.zero_grad(set_to_none=True)
         return loss.detach(), loss_dict, boundary
 
+    def validation_step(self, batch):
+        """One validation batch (train_egtr.py:333-336): the RAW model in evaluation mode under ``torch.no_grad()`` -- no DDP
+        synchronisation, no graph capture -- through ``common_step``.  Returns (loss, loss_dict), detached, with
+        ``loss_dict["loss"] = loss``.  In evaluation mode the criterion's relation loss is un-sampled (BCE over every element):
+        on the device that is ops.RelationLossAllFunction's value-only launch, with no host synchronisation.  Every module's
+        ``training`` flag is restored on the way out, after an exception too.
+
+        The device matcher's per-step statuses of the validation forward are dropped, and the ones the current accumulation
+        window had recorded are kept: nothing is stepped here, so a cost matrix refused in a validation batch must neither pile
+        up over an epoch nor make the next training window skip its optimizer step.  The refusal itself is not lost: its
+        ValueError is raised by ``raise_if_invalid`` at the top of the next ``training_step`` or by ``finalize()``, and the
+        batch's loss terms are NaN."""
+        from . import deformable_detr as dd
+        window = dd.DeformableDetrHungarianMatcher.take_step_statuses()
+        flags = [(m, m.training) for m in self.raw.modules()]   # per module: a submodule kept in eval mode stays there
+        wrapped, graph_wanted = self.model, self._graph_wanted
+        self.model, self._graph_wanted = self.raw, False
+        self.raw.eval()
+        try:
+            with torch.no_grad():
+                loss, loss_dict = self.common_step(batch)
+            loss = loss.detach()
+            loss_dict = {k: v.detach() for k, v in loss_dict.items()}
+            loss_dict["loss"] = loss
+            return loss, loss_dict
+        finally:
+            self.model, self._graph_wanted = wrapped, graph_wanted
+            for m, flag in flags:
+                m.training = flag
+            dd.DeformableDetrHungarianMatcher.take_step_statuses()
+            dd._STEP_MATCHER_STATUS.extend(window)
+
+    @staticmethod
+    def validation_epoch_end(outputs):
+        """The reference's epoch summary (train_egtr.py:338-348): per key of the steps' loss dicts the mean over the steps, as
+        ``{"validation_<key>": float}``.  ``outputs``: the ``validation_step`` results, (loss, loss_dict) pairs or the loss dicts
+        alone.  The one host wait of a validation epoch: every mean is formed on the device, one copy brings them over."""
+        dicts = [o[1] if isinstance(o, (tuple, list)) else o for o in outputs]
+        if not dicts:
+            return {}
+        keys = list(dicts[0])
+        means = torch.stack([torch.stack([torch.as_tensor(d[k]).detach().float() for d in dicts]).mean() for k in keys])
+        return {f"validation_{k}": v for k, v in zip(keys, means.tolist())}
+
     def finalize(self):
         """After the last step of a run: raise what the device matcher refused in it (``training_step`` reports a refusal at
         the top of the NEXT step; there is none after the last one)."""

@@ -532,6 +532,29 @@ int egtr_relation_loss_det_bits_f32(egtr_stream_t stream, const float* pred_rel,
                                     float nonmatching_cost, int sample_negatives, int sample_nonmatching, float* loss_out,
                                     float* grad_rel, float* grad_conn, void* workspace);
 
+/* The UN-SAMPLED relation loss (model/egtr.py:806-829 with both sample counts None: what the criterion computes in evaluation
+ * mode, i.e. validation_loss, and in training with rel_sample_negatives = rel_sample_nonmatching = None):
+ *   loss_out[0] = loss_rel = mean over ALL batch N N R elements of BCEWithLogits(pred_rel, target * w_a w_b)
+ *   loss_out[1] = loss_connectivity, as above
+ *   grad_rel = (sigmoid(pred_rel) - target * w_a w_b) / (batch N N R), grad_conn as above -- OPTIONAL: both NULL for the value
+ *   alone (nothing of their size is written), one of them NULL is EGTR_E_ARG.
+ * The arguments of egtr_relation_loss_f32 / egtr_relation_loss_bits_f32 without the two sample counts; a dense target is read
+ * as a number in the loss and as `!= 0` for the connectivity.  Four launches (maps, all-elements pass, connectivity, finalize),
+ * no atomics on values and no tickets: the same inputs give the same bits, and both entries return the same bits on the dense
+ * form of the same targets.  workspace: egtr_relation_loss_all_workspace_bytes() bytes.  EGTR_E_UNSUPPORTED: num_rel > 64 on
+ * the packed entry; on both, num_query * num_rel >= 2^22, num_query > 4096 or batch > 65535 (the first two limits are those of
+ * the sampled entries above). */
+long long egtr_relation_loss_all_workspace_bytes(int batch, int num_query);
+int egtr_relation_loss_all_f32(egtr_stream_t stream, const float* pred_rel, const float* pred_conn,
+                               const float* const* target_rel, const int64_t* pred_idx, const int64_t* tgt_idx,
+                               const float* match_cost, const int* out_offsets, int batch, int num_query, int num_rel,
+                               float nonmatching_cost, float* loss_out, float* grad_rel, float* grad_conn, void* workspace);
+int egtr_relation_loss_all_bits_f32(egtr_stream_t stream, const float* pred_rel, const float* pred_conn,
+                                    const uint64_t* rel_bits, const int64_t* pred_idx, const int64_t* tgt_idx,
+                                    const float* match_cost, const int* out_offsets, int batch, int num_query, int num_rel,
+                                    float nonmatching_cost, float* loss_out, float* grad_rel, float* grad_conn,
+                                    void* workspace);
+
 /* IoU matrix of the reference's native evaluator routine, lib/fpn/box_intersections_cpu/bbox.pyx: mode 0 =
  * bbox_overlaps (:21-61), mode 1 = bbox_intersections (:64-108).  boxes [num_boxes, 4], query_boxes [num_query, 4]
  * (x0, y0, x1, y1), float64 like the reference (DTYPE = np.float), "+1 pixel" convention; out [num_boxes, num_query],

@@ -26,6 +26,7 @@ SOURCES = [
     ("gemm_split", ["gemm_split.hip", "xs_format.h", "x6_common.h"]),
     ("wgrad_split", ["gemm_split.hip", "xs_format.h", "x6_common.h"]),
     ("decoder_layer_cluster", ["dec_layer.hip", "msda_common.h"]),
+    ("rel_loss", ["loss.hip"]),
 ]
 
 
