@@ -99,6 +99,10 @@ SIGNATURES = {
     "egtr_hungarian_match_f32": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, ctypes.c_float, ctypes.c_float,
                                  ctypes.c_float, _I, ctypes.c_float, ctypes.c_float, _P, _P, _P, _P, _P, _P, _P],
     "egtr_hungarian_match_scratch_doubles": [_I, _I, ctypes.c_longlong],
+    "egtr_hungarian_match_large_f32": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, ctypes.c_float, ctypes.c_float,
+                                       ctypes.c_float, _I, ctypes.c_float, ctypes.c_float, _P, _P, _P, _P, _P, _P, _P,
+                                       ctypes.c_longlong],
+    "egtr_hungarian_match_large_workspace_bytes": [_I, _I, _I, ctypes.c_longlong],
     "egtr_add_layernorm_backward_f32": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, ctypes.c_float],
     "egtr_add_layernorm_backward_workspace_floats": [_I],
     "egtr_msda_geometry_forward_f32": [_P, _P, ctypes.c_longlong, _P, ctypes.c_longlong, _P, _I, _P, _P, _P, ctypes.c_longlong, _I, _I, _I],
@@ -182,6 +186,7 @@ _RESTYPES = {"egtr_status_string": ctypes.c_char_p, "egtr_last_hip_error": ctype
              "egtr_relation_loss_det_workspace_bytes": ctypes.c_longlong,
              "egtr_relation_loss_all_workspace_bytes": ctypes.c_longlong,
              "egtr_hungarian_match_scratch_doubles": ctypes.c_longlong,
+             "egtr_hungarian_match_large_workspace_bytes": ctypes.c_longlong,
              "egtr_relation_loss_workspace_bytes": ctypes.c_longlong,
              "egtr_column_sum_workspace_floats": ctypes.c_longlong,
              "egtr_add_layernorm_backward_workspace_floats": ctypes.c_longlong,

@@ -1651,10 +1651,11 @@ class DeformableDetrHungarianMatcher(nn.Module):
     def prepare(self, outputs, targets):
         """First half of ``forward``.  GPU: the whole matcher is ENQUEUED here (one launch, asynchronous) and ``finish``
         only slices its outputs -- no host synchronisation at all.  CPU: the cost matrix."""
-        if outputs["logits"].is_cuda and outputs["logits"].dtype == torch.float32 and \
-                max(outputs["logits"].shape[1], max((len(t["class_labels"]) for t in targets), default=0)) <= 1024:
-            # (larger sets -- the two-stage variant's per-token proposals -- take the reference's route below: cost matrix
-            # on the device, scipy on the host; the device solver keeps its matrix in LDS, csrc/matcher.hip)
+        if outputs["logits"].is_cuda and outputs["logits"].dtype == torch.float32 and ops.hungarian_match_route(
+                outputs["logits"].shape[1], max((len(t["class_labels"]) for t in targets), default=0)) is not None:
+            # (up to 1024 a side: the one-wave kernel with its state in LDS; the two-stage variant's per-token proposals, up
+            # to 65 536 of them against up to 512 targets: the 16-wave kernel with its state in global memory,
+            # csrc/matcher.hip.  Anything else takes the reference's route below: cost matrix on the device, scipy on the host)
             cm = iss = None
             if self.smoothing:
                 cm, iss = self._smoothing_scalars()

@@ -1,7 +1,8 @@
 """Bindings of the relation-head forward kernels and their weight packers (csrc/rel_head*.hip), the device matcher
 (csrc/matcher.hip), the target packing of the loss kernels and the relation loss on dense / bit-packed targets (csrc/loss.hip,
 csrc/rel_targets.hip).  No routing decisions here -- ``egtr_amd.ops`` decides and
-re-exports every name below."""
+re-exports every name below -- but one: which of the matcher's two entries serves a shape (``hungarian_match_route``, the
+limits of csrc/matcher.hip; ``hungarian_match`` and ``DeformableDetrHungarianMatcher.prepare`` both ask it)."""
 import torch
 
 from .. import _lib
@@ -9,6 +10,7 @@ from .._lib import _chk
 from .linear import _split3_bf16
 
 __all__ = ["rel_head_split_weights", "rel_head_streams", "relation_head_split_bf16", "relation_head_train_forward", "hungarian_match",
+           "hungarian_match_route", "HUNGARIAN_MAX_SIDE", "HUNGARIAN_LARGE_MAX_TARGETS", "HUNGARIAN_LARGE_MAX_QUERIES",
            "pack_detection_targets", "pack_relation_bits", "relation_loss_launch", "relation_loss_all_launch"]
 
 
@@ -145,16 +147,35 @@ def relation_head_split_bf16(gate_q, gate_k, uq, uk, b1, w2x_rel, b2r, w3x_rel, 
     return rel, conn.unsqueeze(-1), gm
 
 
+HUNGARIAN_MAX_SIDE = 1024              # egtr_hungarian_match_f32: max(N, T)
+HUNGARIAN_LARGE_MAX_TARGETS = 512      # egtr_hungarian_match_large_f32: T < N, T <= 512, N <= 65 536
+HUNGARIAN_LARGE_MAX_QUERIES = 65536
+
+
+def hungarian_match_route(num_query, max_targets):
+    """Which entry serves ``num_query`` queries against at most ``max_targets`` targets per image (the limits of
+    csrc/matcher.hip, one place for ``hungarian_match`` and ``DeformableDetrHungarianMatcher.prepare``): ``"small"``
+    (egtr_hungarian_match_f32, everything up to 1024 a side), ``"large"`` (egtr_hungarian_match_large_f32, proposal-sized
+    query sets) or ``None`` (neither: the caller keeps the host route)."""
+    if max(num_query, max_targets) <= HUNGARIAN_MAX_SIDE:
+        return "small"
+    if max_targets < num_query <= HUNGARIAN_LARGE_MAX_QUERIES and max_targets <= HUNGARIAN_LARGE_MAX_TARGETS:
+        return "large"
+    return None
+
+
 @torch.no_grad()
 def hungarian_match(logits, pred_boxes, targets, class_cost, bbox_cost, giou_cost, cost_min=None,
-                    inverse_sigmoid_smoothing=None, cost_in=None, want_cost=False, want_status=False):
+                    inverse_sigmoid_smoothing=None, cost_in=None, want_cost=False, want_status=False, large=None):
     """DeformableDetrHungarianMatcher.forward on the device (egtr_hungarian_match_f32): cost matrix + linear sum
     assignment per image in one launch, nothing copied to the host (the reference's ``.cpu()`` at dd:2985 is a device
     synchronisation per step).  ``targets``: list of dicts with "class_labels" / "boxes" (device tensors); their COUNTS
     are host integers (tensor shapes), so output shapes are static.  ``cost_min`` / ``inverse_sigmoid_smoothing``: the two
     fp32 scalars of the adaptive-smoothing offset (dd:2992-2998) or None.  ``cost_in``: per-image [N, T_b] cost matrices
     to solve instead (tests).  Returns (pred_idx, tgt_idx, match_cost) flat device tensors + the per-image counts
-    [+ cost blocks] [+ status]: entries of image b are sorted by query index, i.e. scipy's output order."""
+    [+ cost blocks] [+ status]: entries of image b are sorted by query index, i.e. scipy's output order.
+    ``large``: None routes by size (``hungarian_match_route``), True forces egtr_hungarian_match_large_f32 (any N > T;
+    tests reach its edges at small sizes this way), False the one-wave entry.  Same tuple, same bits."""
     lib = _lib.lib()
     if cost_in is not None:
         B = len(cost_in)
@@ -189,17 +210,27 @@ def hungarian_match(logits, pred_boxes, targets, class_cost, bbox_cost, giou_cos
     cost_out = torch.empty(max(N * offs[-1], 1), dtype=torch.float32, device=dev) if want_cost else None
     status = torch.zeros(B, dtype=torch.int32, device=dev) if want_status else None
     smooth = 1 if cost_min is not None else 0
-    n_scr = lib.egtr_hungarian_match_scratch_doubles(N, max(sizes) if sizes else 0, offs[-1])
-    scratch = torch.empty(n_scr, dtype=torch.float64, device=dev) if n_scr > 0 else None
-    if max(sizes, default=0) > 0:
-        _lib.launch("egtr_hungarian_match_f32", _lib.ptr(lg), _lib.ptr(bx),
-                    ti.data_ptr() if ti is not None and ti.numel() else None,
-                    tb.data_ptr() if tb is not None and tb.numel() else None, meta.data_ptr(), meta.data_ptr() + 4 * (B + 1),
-                    B, N, K, max(sizes) if sizes else 0, float(class_cost), float(bbox_cost), float(giou_cost), smooth,
-                    float(cost_min) if smooth else 0.0, float(inverse_sigmoid_smoothing) if smooth else 0.0,
-                    pred_idx.data_ptr(), tgt_idx.data_ptr(), mcost.data_ptr(), _lib.ptr(cost_out), _lib.ptr(cin),
-                    _lib.ptr(status), _lib.ptr(scratch))
-    out = [pred_idx[:ooffs[-1]], tgt_idx[:ooffs[-1]], mcost[:ooffs[-1]], n_out]
+    max_t = max(sizes, default=0)
+    if large is None:
+        large = hungarian_match_route(N, max_t) == "large"
+    common = (_lib.ptr(lg), _lib.ptr(bx), ti.data_ptr() if ti is not None and ti.numel() else None,
+              tb.data_ptr() if tb is not None and tb.numel() else None, meta.data_ptr(), meta.data_ptr() + 4 * (B + 1),
+              B, N, K, max_t, float(class_cost), float(bbox_cost), float(giou_cost), smooth,
+              float(cost_min) if smooth else 0.0, float(inverse_sigmoid_smoothing) if smooth else 0.0,
+              pred_idx.data_ptr(), tgt_idx.data_ptr(), mcost.data_ptr(), _lib.ptr(cost_out), _lib.ptr(cin),
+              _lib.ptr(status))
+    if large and max_t > 0:
+        n_ws = lib.egtr_hungarian_match_large_workspace_bytes(B, N, max_t, offs[-1])
+        if n_ws <= 0:
+            raise _lib.EgtrHipError(f"egtr_hungarian_match_large_f32 serves T < N, T <= {HUNGARIAN_LARGE_MAX_TARGETS}, "
+                                    f"N <= {HUNGARIAN_LARGE_MAX_QUERIES}; got N = {N}, T = {max_t}")
+        workspace = torch.empty(n_ws, dtype=torch.uint8, device=dev)
+        _lib.launch("egtr_hungarian_match_large_f32", *common, workspace.data_ptr(), n_ws)
+    elif max_t > 0:
+        n_scr = lib.egtr_hungarian_match_scratch_doubles(N, max_t, offs[-1])
+        scratch = torch.empty(n_scr, dtype=torch.float64, device=dev) if n_scr > 0 else None
+        _lib.launch("egtr_hungarian_match_f32", *common, _lib.ptr(scratch))
+    out =[pred_idx[:ooffs[-1]], tgt_idx[:ooffs[-1]], mcost[:ooffs[-1]], n_out]
     if want_cost:
         out.append([cost_out[N * offs[i]: N * offs[i + 1]].view(N, sizes[i]) for i in range(B)])
     if want_status:

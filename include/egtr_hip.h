@@ -479,6 +479,27 @@ int egtr_hungarian_match_f32(egtr_stream_t stream, const float* logits, const fl
                              const float* cost_in, int* status, double* scratch);
 long long egtr_hungarian_match_scratch_doubles(int num_query, int max_targets, long long total_targets);
 
+/* The same matcher for proposal-sized query sets (the two-stage variant matches every encoder token: 12 537 queries per
+ * image at 600x1000, 22 223 at 800x1333).  Domain: max_targets < num_query, max_targets <= 512, num_query <= 65 536 -- the
+ * problem is then always scipy's transposed one (rows = targets, columns = queries).  One workgroup of 1024 threads per
+ * image; the fp32 cost block and the per-column solver state live in `workspace` (device,
+ * egtr_hungarian_match_large_workspace_bytes(...) bytes; the query is host arithmetic and answers 0 outside the domain),
+ * the column scan of every shortest-path step is spread over all 16 waves.  Arguments, outputs, cost_in / cost_out and
+ * the status words are those of egtr_hungarian_match_f32 (status 2 also when a search exceeds its bound of num_query
+ * column removals); indices and costs are bit-identical to that entry wherever both serve a shape.  NULL required
+ * pointers and a workspace that is too small are EGTR_E_ARG, a shape outside the domain is EGTR_E_UNSUPPORTED, both
+ * before any HIP call.  (The target counts are device data: the host check holds workspace_bytes against the query's
+ * answer for total_targets = max_targets, the least a batch can have; an image whose cost block would still end past
+ * workspace_bytes, or whose T_b is outside the domain, is refused by the kernel with status 2 and writes nothing there.) */
+int egtr_hungarian_match_large_f32(egtr_stream_t stream, const float* logits, const float* boxes, const int64_t* tgt_ids,
+                                   const float* tgt_boxes, const int* tgt_offsets, const int* out_offsets, int batch,
+                                   int num_query, int num_logits, int max_targets, float class_cost, float bbox_cost,
+                                   float giou_cost, int smoothing, float cost_min, float inverse_sigmoid_smoothing,
+                                   int64_t* pred_idx, int64_t* tgt_idx, float* match_cost, float* cost_out,
+                                   const float* cost_in, int* status, void* workspace, long long workspace_bytes);
+long long egtr_hungarian_match_large_workspace_bytes(int batch, int num_query, int max_targets,
+                                                     long long total_targets);
+
 /* Relation + connectivity losses of SceneGraphGenerationLoss in training mode (model/egtr.py:754-923 with
  * rel_sample_negatives / rel_sample_nonmatching set and *_largest = True), value AND gradient, without the reference's
  * per-image nonzero() index lists, host-side counts and gathers:
