@@ -172,6 +172,9 @@ SIGNATURES = {
     "egtr_rel_head_forward_bf16r_save_f32": [_P] * 16 + [_I] * 6 + [_P] * 5,
     "egtr_rel_head_streams_bf16r_f32": [_P] * 4 + [_I] * 2 + [_P] * 3,
     "egtr_rel_head_forward_save_f32": [_P] * 16 + [_I] * 6 + [_P] * 5,
+    "egtr_rel_head_forward_wide_f32": [_P] * 16 + [_I] * 6 + [_P] * 5,
+    "egtr_rel_head_forward_wide_bf16x6_f32": [_P] * 16 + [_I] * 6 + [_P] * 3 + [_I],
+    "egtr_rel_head_streams_wide_f32": [_P] * 4 + [_I] * 2 + [_P] * 3,
     "egtr_rel_head_backward_pairs_f32": [_P] * 6 + [_I] * 4 + [_P] * 5,
     "egtr_decoder_layer_f32": [_P, _P],
     "egtr_decoder_layer_workspace": [_I, _I, _P, _P, _P],

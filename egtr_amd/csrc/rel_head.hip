@@ -77,17 +77,25 @@ struct PrefetchRow {
     wq[I] = gload_b128<I * 16>(wrow);
     if constexpr (I + 1 < PRE) issue<I + 1>(wq, wrow);
   }
-  template <int S4>
+  // SWAP (the wide kernels' layer 3): the activations are the A operand and the weight row the B operand, D[pair][out row]
+  template <int S4, bool SWAP = false>
   static __device__ __forceinline__ void run(f32x4v (&wq)[PRE], const float4* wrow, const float (&h1)[128], f32x16& acc) {
     constexpr int newer = (31 - S4) < (PRE - 1) ? (31 - S4) : (PRE - 1);  // own loads issued after this one
     vm_wait<newer>(wq[S4 % PRE]);
     const f32x4v w = wq[S4 % PRE];
-    acc = mfma32(w.x, h1[4 * S4 + 0], acc);
-    acc = mfma32(w.y, h1[4 * S4 + 1], acc);
-    acc = mfma32(w.z, h1[4 * S4 + 2], acc);
-    acc = mfma32(w.w, h1[4 * S4 + 3], acc);
+    if constexpr (SWAP) {
+      acc = mfma32(h1[4 * S4 + 0], w.x, acc);
+      acc = mfma32(h1[4 * S4 + 1], w.y, acc);
+      acc = mfma32(h1[4 * S4 + 2], w.z, acc);
+      acc = mfma32(h1[4 * S4 + 3], w.w, acc);
+    } else {
+      acc = mfma32(w.x, h1[4 * S4 + 0], acc);
+      acc = mfma32(w.y, h1[4 * S4 + 1], acc);
+      acc = mfma32(w.z, h1[4 * S4 + 2], acc);
+      acc = mfma32(w.w, h1[4 * S4 + 3], acc);
+    }
     if constexpr (S4 + PRE < 32) wq[S4 % PRE] = gload_b128<(S4 + PRE) * 16>(wrow);
-    if constexpr (S4 + 1 < 32) run<S4 + 1>(wq, wrow, h1, acc);
+    if constexpr (S4 + 1 < 32) run<S4 + 1, SWAP>(wq, wrow, h1, acc);
   }
 };
 
@@ -634,7 +642,8 @@ struct PrefetchX6 {
     wq[I][2] = gload_b128_s2k(voff, wtile + I * 3072);
     if constexpr (I + 1 < PRE) issue<I + 1>(wq, voff, wtile);
   }
-  template <int S>
+  // SWAP (the wide kernel's layer 3): the activation pieces are the A operands and the weight pieces the B operands
+  template <int S, bool SWAP = false>
   static __device__ __forceinline__ void run(f32x4v (&wq)[PRE][3], unsigned voff, const char* wtile,
                                              const __bf16* hrow, f32x16& acc_m, f32x16& acc_c) {
     constexpr int newer = 3 * ((15 - S) < (PRE - 1) ? (15 - S) : (PRE - 1));  // own loads issued after this step's
@@ -647,18 +656,27 @@ struct PrefetchX6 {
     const bf16x8 hhi = *reinterpret_cast<const bf16x8*>(hrow + 16 * S);
     const bf16x8 hmid = *reinterpret_cast<const bf16x8*>(hrow + 32 * kHp + 16 * S);
     const bf16x8 hlo = *reinterpret_cast<const bf16x8*>(hrow + 64 * kHp + 16 * S);
-    acc_c = mfma_bf16(whi, hlo, acc_c);
-    acc_m = mfma_bf16(whi, hhi, acc_m);
-    acc_c = mfma_bf16(wlo, hhi, acc_c);
-    acc_c = mfma_bf16(wmid, hmid, acc_c);
-    acc_c = mfma_bf16(whi, hmid, acc_c);
-    acc_c = mfma_bf16(wmid, hhi, acc_c);
+    if constexpr (SWAP) {
+      acc_c = mfma_bf16(hlo, whi, acc_c);
+      acc_m = mfma_bf16(hhi, whi, acc_m);
+      acc_c = mfma_bf16(hhi, wlo, acc_c);
+      acc_c = mfma_bf16(hmid, wmid, acc_c);
+      acc_c = mfma_bf16(hmid, whi, acc_c);
+      acc_c = mfma_bf16(hhi, wmid, acc_c);
+    } else {
+      acc_c = mfma_bf16(whi, hlo, acc_c);
+      acc_m = mfma_bf16(whi, hhi, acc_m);
+      acc_c = mfma_bf16(wlo, hhi, acc_c);
+      acc_c = mfma_bf16(wmid, hmid, acc_c);
+      acc_c = mfma_bf16(whi, hmid, acc_c);
+      acc_c = mfma_bf16(wmid, hhi, acc_c);
+    }
     if constexpr (S + PRE < 16) {
       wq[S % PRE][0] = gload_b128_s(voff, wtile + (S + PRE) * 3072);
       wq[S % PRE][1] = gload_b128_s1k(voff, wtile + (S + PRE) * 3072);
       wq[S % PRE][2] = gload_b128_s2k(voff, wtile + (S + PRE) * 3072);
     }
-    if constexpr (S + 1 < 16) run<S + 1>(wq, voff, wtile, hrow, acc_m, acc_c);
+    if constexpr (S + 1 < 16) run<S + 1, SWAP>(wq, voff, wtile, hrow, acc_m, acc_c);
   }
 };
 
@@ -1011,6 +1029,446 @@ int launch_T(hipStream_t st, int R, dim3 grid, const float* gate_q, const float*
                        b3r, w2c, b2c, w3c, b3c, triplet, node_cls, B, N, R, C1, rel, conn, gate_mean, h1_save,
                        h2_save);
   return 0;
+}
+
+// ------------------------------------------------------------------------------------- more than 64 predicate classes
+// The kernels above keep OT <= 2 layer-3 accumulators live across the hidden-2 tiles and stage the whole 32 x R output tile in
+// the layer-1 buffer; neither scales to R = 256.  The wide kernels finish layer 2 first -- layers 1 and 2 are the narrow
+// kernels' instruction for instruction, so h1 and h2 carry the same bits -- and hand the tile's hidden-2 activations through
+// the (by then free) layer-1 LDS buffer back to the lanes in the layout layer 2 read h1 in.  Layer 3 is then the layer-2 inner
+// product once more, per 32-wide OUTPUT tile with the whole K = 256 in one accumulator: the two waves split the output tiles
+// (ot = wave, wave + 2, ...), no cross-wave sum.  The operands are swapped (activations = A, weights = B), so the accumulator is
+// D[pair][out]: a register of the 64 lanes is two runs of 32 consecutive outputs of two pairs, stored as it is -- no output
+// staging, and LDS does not grow with R.  The connectivity MLP (blockIdx.y = 1) is the narrow kernels' code.
+template <int T>
+__global__ __launch_bounds__(64 * kRhWaves) void rel_head_fwd_wide_f32(
+    const float* __restrict__ gate_q, const float* __restrict__ gate_k, const float* __restrict__ uq,
+    const float* __restrict__ uk, const float* __restrict__ b1, const float* __restrict__ w2r,
+    const float* __restrict__ b2r, const float* __restrict__ w3r, const float* __restrict__ b3r,
+    const float* __restrict__ w2c, const float* __restrict__ b2c, const float* __restrict__ w3c,
+    const float* __restrict__ b3c, const float* __restrict__ triplet, const int64_t* __restrict__ node_cls, int B,
+    int N, int R, int C1, float* __restrict__ rel_logits, float* __restrict__ conn_logits,
+    float* __restrict__ gate_mean, float* __restrict__ h1_save, float* __restrict__ h2_save) {
+  // one buffer, two lives: the layer-1 transpose, then the hidden-2 transpose (both [32 pairs][256] at pitch 260)
+  __shared__ __attribute__((aligned(16))) float s_buf[32 * kH1Stride];
+  __shared__ int s_tb[32];
+  __shared__ long long s_pp[32];
+  __shared__ float s_cacc[kRhWaves][32];
+  const int lane = threadIdx.x & 63, pi = lane & 31, hf = lane >> 5;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int mlp = blockIdx.y;
+  const long long total = (long long)B * N * N;
+  const int tj = (N + 3) >> 2, ti = (N + 7) >> 3;
+  const int b = blockIdx.x / (ti * tj);
+  const int trem = blockIdx.x - b * ti * tj;
+  const int i0 = (trem / tj) * 8, j0 = (trem - (trem / tj) * tj) * 4;
+  const int i_raw = i0 + (pi >> 2), j_raw = j0 + (pi & 3);
+  const bool valid = i_raw < N && j_raw < N;
+  const int i = i_raw < N ? i_raw : N - 1, j = j_raw < N ? j_raw : N - 1;   // clamped: loads stay in range
+  const long long p = ((long long)b * N + i) * N + j;
+  const size_t qi = (size_t)b * N + i, kj = (size_t)b * N + j;
+
+  float g[T];
+#pragma unroll
+  for (int t = 0; t < T; ++t) {
+    const float x = gate_q[qi * T + t] + gate_k[kj * T + t];
+    g[t] = 1.f / (1.f + expf(-x));
+  }
+  if (gate_mean != nullptr && mlp == 0 && wv == 0) {
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+      float v = (valid && hf == 0) ? g[t] : 0.f;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o);
+      if (lane == 0) unsafeAtomicAdd(gate_mean + t, v / (float)total);
+    }
+  }
+
+  // ---- layer 1: as rel_head_fwd_f32 ---------------------------------------------------------------------------------
+  float hx[128];   // the lane's 128 channels {128 hf + s} of its pair: of h1 for layer 2, of h2 for layer 3
+  {
+    const int krow_l = (int)kj;
+    const float4 bias4 = reinterpret_cast<const float4*>(b1 + mlp * kHd)[lane];
+    const float4* uq4 = reinterpret_cast<const float4*>(uq) + mlp * (kHd / 4) + lane;
+    const float4* uk4 = reinterpret_cast<const float4*>(uk) + mlp * (kHd / 4) + lane;
+    constexpr int ROW4 = 2 * kHd / 4;
+    float4 kk[4][T];
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) {
+      const int kr = __builtin_amdgcn_readlane(krow_l, jj);
+      const float4* pk = uk4 + (size_t)kr * T * ROW4;
+#pragma unroll
+      for (int t = 0; t < T; ++t) kk[jj][t] = pk[t * ROW4];
+    }
+    auto qrow_of = [&](int ii) { return b * N + (i0 + ii < N ? i0 + ii : N - 1); };
+    const int ii0 = wv * (8 / kRhWaves);
+    float4 ua[2][T];
+    {
+      const float4* pq = uq4 + (size_t)qrow_of(ii0) * T * ROW4;
+#pragma unroll
+      for (int t = 0; t < T; ++t) ua[0][t] = pq[t * ROW4];
+    }
+#pragma unroll
+    for (int iu = 0; iu < 8 / kRhWaves; ++iu) {
+      const int ii = ii0 + iu;
+      if (iu + 1 < 8 / kRhWaves) {
+        const float4* pq = uq4 + (size_t)qrow_of(ii + 1) * T * ROW4;
+#pragma unroll
+        for (int t = 0; t < T; ++t) ua[(iu + 1) & 1][t] = pq[t * ROW4];
+      }
+#pragma unroll
+      for (int jj = 0; jj < 4; ++jj) {
+        const int pp = ii * 4 + jj;
+        float4 acc = bias4;
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+          const float4 a = ua[iu & 1][t];
+          const float4 c = kk[jj][t];
+          const float gt = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(g[t]), pp));
+          acc.x += gt * (a.x + c.x);
+          acc.y += gt * (a.y + c.y);
+          acc.z += gt * (a.z + c.z);
+          acc.w += gt * (a.w + c.w);
+        }
+        const float4 hv = make_float4(egtr_relu(acc.x), egtr_relu(acc.y), egtr_relu(acc.z), egtr_relu(acc.w));
+        *reinterpret_cast<float4*>(&s_buf[pp * kH1Stride + 4 * lane]) = hv;
+        if (h1_save != nullptr && i0 + ii < N && j0 + jj < N)
+          reinterpret_cast<float4*>(h1_save + ((size_t)mlp * total +
+                                               (size_t)(((long long)b * N + i0 + ii) * N + j0 + jj)) * kHd)[lane] = hv;
+      }
+    }
+    __syncthreads();   // both waves' rows are in LDS
+    {
+      const float4* hp = reinterpret_cast<const float4*>(&s_buf[pi * kH1Stride + hf * 128]);
+#pragma unroll
+      for (int s4 = 0; s4 < 32; ++s4) {
+        const float4 v = hp[s4];
+        hx[4 * s4 + 0] = v.x;
+        hx[4 * s4 + 1] = v.y;
+        hx[4 * s4 + 2] = v.z;
+        hx[4 * s4 + 3] = v.w;
+      }
+    }
+    __syncthreads();   // the buffer is reused for the hidden-2 tiles
+  }
+
+  const float* w2 = mlp ? w2c : w2r;
+  const float* b2 = mlp ? b2c : b2r;
+  float cacc = 0.f;
+  constexpr int kPre = 8;
+  constexpr int kNtPerWave = kHd / 32 / kRhWaves;
+#pragma unroll 1
+  for (int nt = wv * kNtPerWave; nt < (wv + 1) * kNtPerWave; ++nt) {
+    // ---- layer 2: as rel_head_fwd_f32; h2^T[n][pair], n = 32 nt + (r&3) + 8 (r>>2) + 4 hf -----------------------------
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    const float4* wrow = reinterpret_cast<const float4*>(w2 + (size_t)(nt * 32 + pi) * kHd + hf * 128);
+    f32x4v wq[kPre];
+    PrefetchRow<kPre>::template issue<0>(wq, wrow);
+    PrefetchRow<kPre>::template run<0>(wq, wrow, hx, acc);
+#pragma unroll
+    for (int rq = 0; rq < 4; ++rq) {
+      const int n0 = nt * 32 + 8 * rq + 4 * hf;
+      const float4 bb = *reinterpret_cast<const float4*>(b2 + n0);
+      acc[4 * rq + 0] = egtr_relu(acc[4 * rq + 0] + bb.x);
+      acc[4 * rq + 1] = egtr_relu(acc[4 * rq + 1] + bb.y);
+      acc[4 * rq + 2] = egtr_relu(acc[4 * rq + 2] + bb.z);
+      acc[4 * rq + 3] = egtr_relu(acc[4 * rq + 3] + bb.w);
+      const float4 hv = make_float4(acc[4 * rq + 0], acc[4 * rq + 1], acc[4 * rq + 2], acc[4 * rq + 3]);
+      if (h2_save != nullptr && valid)
+        *reinterpret_cast<float4*>(h2_save + ((size_t)mlp * total + (size_t)p) * kHd + n0) = hv;
+      if (mlp == 0) *reinterpret_cast<float4*>(&s_buf[pi * kH1Stride + n0]) = hv;   // for layer 3, behind the barrier below
+    }
+    if (mlp == 1) {
+#pragma unroll
+      for (int rq = 0; rq < 4; ++rq) {
+        const float4 w = *reinterpret_cast<const float4*>(w3c + nt * 32 + 8 * rq + 4 * hf);
+        cacc += w.x * acc[4 * rq + 0] + w.y * acc[4 * rq + 1] + w.z * acc[4 * rq + 2] + w.w * acc[4 * rq + 3];
+      }
+    }
+  }
+
+  if (mlp == 1) {
+    cacc += __shfl_xor(cacc, 32);
+    if (hf == 0) s_cacc[wv][pi] = cacc;
+    __syncthreads();
+    if (wv == 0 && valid && hf == 0) {
+      float v = s_cacc[0][pi];
+#pragma unroll
+      for (int w = 1; w < kRhWaves; ++w) v += s_cacc[w][pi];
+      conn_logits[p] = v + b3c[0];
+    }
+    return;
+  }
+  if (wv == 0 && hf == 0) {
+    int tb = -1;
+    if (triplet != nullptr) tb = ((int)node_cls[qi] * C1 + (int)node_cls[kj]) * R;
+    s_tb[pi] = tb;
+    s_pp[pi] = valid ? p : -1;
+  }
+  __syncthreads();   // both waves' hidden-2 tiles are in LDS
+  {
+    const float4* hp = reinterpret_cast<const float4*>(&s_buf[pi * kH1Stride + hf * 128]);
+#pragma unroll
+    for (int s4 = 0; s4 < 32; ++s4) {
+      const float4 v = hp[s4];
+      hx[4 * s4 + 0] = v.x;
+      hx[4 * s4 + 1] = v.y;
+      hx[4 * s4 + 2] = v.z;
+      hx[4 * s4 + 3] = v.w;
+    }
+  }
+  // ---- layer 3: rel[pair][ro] = sum_n h2[pair][n] W3[ro][n], ro = 32 ot + pi the lane's output row, n = 128 hf + s its k slots;
+  // accumulator register r <-> pair (r&3) + 8 (r>>2) + 4 hf of the tile ---------------------------------------------------
+  const int OT = (R + 31) >> 5;
+#pragma unroll 1
+  for (int ot = wv; ot < OT; ot += kRhWaves) {
+    const int ro = ot * 32 + pi;
+    const bool rok = ro < R;
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    const float4* wrow = reinterpret_cast<const float4*>(w3r + (size_t)(rok ? ro : R - 1) * kHd + hf * 128);
+    f32x4v wq[kPre];
+    PrefetchRow<kPre>::template issue<0>(wq, wrow);
+    PrefetchRow<kPre>::template run<0, true>(wq, wrow, hx, acc);
+    const float bias = b3r[rok ? ro : R - 1];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int q = (r & 3) + 8 * (r >> 2) + 4 * hf;
+      const long long po = s_pp[q];
+      const int tb = s_tb[q];
+      if (po >= 0 && rok) {   // a half-wave writes 32 consecutive floats of one pair
+        float v = acc[r] + bias;
+        if (tb >= 0) v += triplet[tb + ro];
+        rel_logits[(size_t)po * R + ro] = v;
+      }
+    }
+  }
+}
+
+// The split-bf16 form (rel_head_fwd_x6<T, ., false, 6> above R = 64): layers 1 and 2 are that kernel's; the wave keeps its four
+// finished hidden-2 tiles in registers until every wave has stopped reading the h1 pieces, splits them into their three bf16
+// pieces over the h1 pieces in LDS (same [piece][pair][264] layout), and layer 3 is PrefetchX6 once more per 32-wide output tile
+// on a W3 stream in the W2 stream's order, w3x [OT][16 t][3 piece][64 lane][8] (egtr_rel_head_streams_wide_f32), operands swapped.
+template <int T>
+__global__ __launch_bounds__(64 * kRhWaves) __attribute__((amdgpu_waves_per_eu(2, 2))) void rel_head_fwd_wide_x6(
+    const float* __restrict__ gate_q, const float* __restrict__ gate_k, const float* __restrict__ uq,
+    const float* __restrict__ uk, const float* __restrict__ b1, const unsigned short* __restrict__ w2xr,
+    const float* __restrict__ b2r, const unsigned short* __restrict__ w3xr, const float* __restrict__ b3r,
+    const unsigned short* __restrict__ w2xc, const float* __restrict__ b2c, const float* __restrict__ w3c,
+    const float* __restrict__ b3c, const float* __restrict__ triplet, const int64_t* __restrict__ node_cls, int B,
+    int N, int R, int C1, float* __restrict__ rel_logits, float* __restrict__ conn_logits,
+    float* __restrict__ gate_mean, int apply_sigmoid) {
+  __shared__ __attribute__((aligned(16))) __bf16 s_h[3 * 32 * kHp];   // the h1 pieces, then the h2 pieces
+  __shared__ int s_tb[32];
+  __shared__ long long s_pp[32];
+  __shared__ float s_cacc[kRhWaves][32];
+  const int lane = threadIdx.x & 63, pi = lane & 31, hf = lane >> 5;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int mlp = blockIdx.y;
+  const long long total = (long long)B * N * N;
+  const int tj = (N + 3) >> 2, ti = (N + 7) >> 3;
+  const int b = blockIdx.x / (ti * tj);
+  const int trem = blockIdx.x - b * ti * tj;
+  const int i0 = (trem / tj) * 8, j0 = (trem - (trem / tj) * tj) * 4;
+  const int i_raw = i0 + (pi >> 2), j_raw = j0 + (pi & 3);
+  const bool valid = i_raw < N && j_raw < N;
+  const int i = i_raw < N ? i_raw : N - 1, j = j_raw < N ? j_raw : N - 1;
+  const long long p = ((long long)b * N + i) * N + j;
+  const size_t qi = (size_t)b * N + i, kj = (size_t)b * N + j;
+
+  float g[T];
+#pragma unroll
+  for (int t = 0; t < T; ++t) {
+    const float x = gate_q[qi * T + t] + gate_k[kj * T + t];
+    g[t] = 1.f / (1.f + expf(-x));
+  }
+  if (gate_mean != nullptr && mlp == 0 && wv == 0) {
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+      float v = (valid && hf == 0) ? g[t] : 0.f;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o);
+      if (lane == 0) unsafeAtomicAdd(gate_mean + t, v / (float)total);
+    }
+  }
+
+  // ---- layer 1: as rel_head_fwd_x6 ------------------------------------------------------------------------------------
+  {
+    const int krow_l = (int)kj;
+    const float4 bias4 = reinterpret_cast<const float4*>(b1 + mlp * kHd)[lane];
+    const float4* uq4 = reinterpret_cast<const float4*>(uq) + mlp * (kHd / 4) + lane;
+    const float4* uk4 = reinterpret_cast<const float4*>(uk) + mlp * (kHd / 4) + lane;
+    constexpr int ROW4 = 2 * kHd / 4;
+    float4 kk[4][T];
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) {
+      const int kr = __builtin_amdgcn_readlane(krow_l, jj);
+      const float4* pk = uk4 + (size_t)kr * T * ROW4;
+#pragma unroll
+      for (int t = 0; t < T; ++t) kk[jj][t] = pk[t * ROW4];
+    }
+    auto qrow_of = [&](int ii) { return b * N + (i0 + ii < N ? i0 + ii : N - 1); };
+    const int ii0 = wv * (8 / kRhWaves);
+    float4 ua[2][T];
+    {
+      const float4* pq = uq4 + (size_t)qrow_of(ii0) * T * ROW4;
+#pragma unroll
+      for (int t = 0; t < T; ++t) ua[0][t] = pq[t * ROW4];
+    }
+#pragma unroll
+    for (int iu = 0; iu < 8 / kRhWaves; ++iu) {
+      const int ii = ii0 + iu;
+      if (iu + 1 < 8 / kRhWaves) {
+        const float4* pq = uq4 + (size_t)qrow_of(ii + 1) * T * ROW4;
+#pragma unroll
+        for (int t = 0; t < T; ++t) ua[(iu + 1) & 1][t] = pq[t * ROW4];
+      }
+#pragma unroll
+      for (int jj = 0; jj < 4; ++jj) {
+        const int pp = ii * 4 + jj;
+        f32x2v a01 = {bias4.x, bias4.y}, a23 = {bias4.z, bias4.w};
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+          const float4 a = ua[iu & 1][t];
+          const float4 c = kk[jj][t];
+          const float gt = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(g[t]), pp));
+          const f32x2v gg = {gt, gt};
+          const f32x2v u01 = {a.x + c.x, a.y + c.y}, u23 = {a.z + c.z, a.w + c.w};
+          a01 = gg * u01 + a01;
+          a23 = gg * u23 + a23;
+        }
+        const Split3 sx = xs::split3_fast(egtr_relu(a01.x)), sy = xs::split3_fast(egtr_relu(a01.y)),
+                     sz = xs::split3_fast(egtr_relu(a23.x)), sw = xs::split3_fast(egtr_relu(a23.y));
+        __bf16* hp = s_h + pp * kHp + 4 * lane;
+        *reinterpret_cast<uint2*>(hp) = make_uint2(pack_hi16(sx.hi, sy.hi), pack_hi16(sz.hi, sw.hi));
+        *reinterpret_cast<uint2*>(hp + 32 * kHp) = make_uint2(pack_hi16(sx.mid, sy.mid), pack_hi16(sz.mid, sw.mid));
+        *reinterpret_cast<uint2*>(hp + 64 * kHp) = make_uint2(pack_hi16(sx.lo, sy.lo), pack_hi16(sz.lo, sw.lo));
+      }
+    }
+    __syncthreads();   // both waves' rows are in LDS
+  }
+
+  const char* w2x = reinterpret_cast<const char*>(mlp ? w2xc : w2xr);
+  const float* b2 = mlp ? b2c : b2r;
+  float cacc = 0.f;
+  const unsigned voff = (unsigned)lane * 16u;
+  const __bf16* hrow = s_h + pi * kHp + 8 * hf;
+  constexpr int kPre = 4;
+  constexpr int kNtPerWave = kHd / 32 / kRhWaves;
+  f32x16 h2t[kNtPerWave];   // the wave's hidden-2 tiles (bias and ReLU applied)
+#pragma unroll
+  for (int ntl = 0; ntl < kNtPerWave; ++ntl) {
+    const int nt = wv * kNtPerWave + ntl;
+    // ---- layer 2: as rel_head_fwd_x6; register 4 rq + j <-> hidden-2 unit 32 nt + 8 rq + 4 hf + j ----------------------
+    f32x16 acc, accc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) accc[r] = 0.f;
+#pragma unroll
+    for (int rq = 0; rq < 4; ++rq) {
+      const float4 bb = *reinterpret_cast<const float4*>(b2 + nt * 32 + 8 * rq + 4 * hf);
+      acc[4 * rq + 0] = bb.x; acc[4 * rq + 1] = bb.y; acc[4 * rq + 2] = bb.z; acc[4 * rq + 3] = bb.w;
+    }
+    const char* wtile = w2x + (size_t)nt * (16 * 3072);
+    f32x4v wq[kPre][3];
+    PrefetchX6<kPre>::template issue<0>(wq, voff, wtile);
+    PrefetchX6<kPre>::template run<0>(wq, voff, wtile, hrow, acc, accc);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = egtr_relu(acc[r] + accc[r]);
+    h2t[ntl] = acc;
+    if (mlp == 1) {
+#pragma unroll
+      for (int rq = 0; rq < 4; ++rq) {
+        const float4 w = *reinterpret_cast<const float4*>(w3c + nt * 32 + 8 * rq + 4 * hf);
+        cacc += w.x * acc[4 * rq + 0] + w.y * acc[4 * rq + 1] + w.z * acc[4 * rq + 2] + w.w * acc[4 * rq + 3];
+      }
+    }
+  }
+
+  if (mlp == 1) {
+    cacc += __shfl_xor(cacc, 32);
+    if (hf == 0) s_cacc[wv][pi] = cacc;
+    __syncthreads();
+    if (wv == 0 && valid && hf == 0) {
+      float v = s_cacc[0][pi];
+#pragma unroll
+      for (int w = 1; w < kRhWaves; ++w) v += s_cacc[w][pi];
+      v += b3c[0];
+      conn_logits[p] = apply_sigmoid ? (float)(1.0 / (1.0 + exp(-(double)v))) : v;
+    }
+    return;
+  }
+  __syncthreads();   // every wave has finished reading the h1 pieces: the buffer takes the h2 pieces
+#pragma unroll
+  for (int ntl = 0; ntl < kNtPerWave; ++ntl) {
+#pragma unroll
+    for (int rq = 0; rq < 4; ++rq) {
+      const Split3 sx = xs::split3_fast(h2t[ntl][4 * rq + 0]), sy = xs::split3_fast(h2t[ntl][4 * rq + 1]),
+                   sz = xs::split3_fast(h2t[ntl][4 * rq + 2]), sw = xs::split3_fast(h2t[ntl][4 * rq + 3]);
+      __bf16* hp = s_h + pi * kHp + (wv * kNtPerWave + ntl) * 32 + 8 * rq + 4 * hf;
+      *reinterpret_cast<uint2*>(hp) = make_uint2(pack_hi16(sx.hi, sy.hi), pack_hi16(sz.hi, sw.hi));
+      *reinterpret_cast<uint2*>(hp + 32 * kHp) = make_uint2(pack_hi16(sx.mid, sy.mid), pack_hi16(sz.mid, sw.mid));
+      *reinterpret_cast<uint2*>(hp + 64 * kHp) = make_uint2(pack_hi16(sx.lo, sy.lo), pack_hi16(sz.lo, sw.lo));
+    }
+  }
+  if (wv == 0 && hf == 0) {
+    int tb = -1;
+    if (triplet != nullptr) tb = ((int)node_cls[qi] * C1 + (int)node_cls[kj]) * R;
+    s_tb[pi] = tb;
+    s_pp[pi] = valid ? p : -1;
+  }
+  __syncthreads();   // both waves' pieces are in LDS
+  // ---- layer 3: rel[pair][ro], ro = 32 ot + pi; accumulator register r <-> pair (r&3) + 8 (r>>2) + 4 hf ------------------
+  const int OT = (R + 31) >> 5;
+#pragma unroll 1
+  for (int ot = wv; ot < OT; ot += kRhWaves) {
+    const int ro = ot * 32 + pi;
+    const bool rok = ro < R;
+    f32x16 acc, accc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { acc[r] = 0.f; accc[r] = 0.f; }
+    const char* wtile = reinterpret_cast<const char*>(w3xr) + (size_t)ot * (16 * 3072);
+    f32x4v wq[kPre][3];
+    PrefetchX6<kPre>::template issue<0>(wq, voff, wtile);
+    PrefetchX6<kPre>::template run<0, true>(wq, voff, wtile, hrow, acc, accc);
+    const float bias = b3r[rok ? ro : R - 1];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int q = (r & 3) + 8 * (r >> 2) + 4 * hf;
+      const long long po = s_pp[q];
+      const int tb = s_tb[q];
+      if (po >= 0 && rok) {   // a half-wave writes 32 consecutive floats of one pair
+        float v = acc[r] + accc[r] + bias;
+        if (tb >= 0) v += triplet[tb + ro];
+        // (the sigmoid through float64: correctly rounded but for the final cast, where 1 / (1 + expf(-v)) is up to 2 ulps off --
+        // expf's ulp, the sum's and the quotient's half; ~50 VALU instructions per 96 matrix instructions of the tile)
+        rel_logits[(size_t)po * R + ro] = apply_sigmoid ? (float)(1.0 / (1.0 + exp(-(double)v))) : v;
+      }
+    }
+  }
+}
+
+// w2x as rel_head_streams_f32<3>; w3x [OT][16 t][3 piece][2 hf][32 pi][8 e] = piece of W3[32 ot + pi][16 t + 8 hf + e], rows
+// beyond R zero: the W2 order with the output tile in place of the hidden-2 tile
+__global__ __launch_bounds__(256) void rel_head_streams_wide_f32(const float* __restrict__ w2r, const float* __restrict__ w2c,
+                                                                 const float* __restrict__ w3r, int R, int OT,
+                                                                 unsigned short* __restrict__ w2xr,
+                                                                 unsigned short* __restrict__ w2xc,
+                                                                 unsigned short* __restrict__ w3x) {
+  const int n2 = kHd * kHd, n3 = OT * 32 * kHd;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < 2 * n2 + n3; i += gridDim.x * 256) {
+    const int which = i < 2 * n2 ? i / n2 : 2, j = i - which * n2;   // j walks the DESTINATION order without the piece index
+    const int e = j & 7, pi = (j >> 3) & 31, hf = (j >> 8) & 1, t = (j >> 9) & 15, tile = j >> 13;
+    const int row = 32 * tile + pi, col = 16 * t + 8 * hf + e;
+    const float w = which == 2 ? (row < R ? w3r[row * kHd + col] : 0.f) : (which ? w2c : w2r)[row * kHd + col];
+    unsigned short* d = (which == 2 ? w3x : which ? w2xc : w2xr) + (size_t)((tile * 16 + t) * 3) * 512 + (hf * 32 + pi) * 8 + e;
+    const xs::Split3 sp = xs::split3_rne(w);
+    d[0] = (unsigned short)(sp.hi >> 16);
+    d[512] = (unsigned short)(sp.mid >> 16);
+    d[1024] = (unsigned short)(sp.lo >> 16);
+  }
 }
 
 // ------------------------------------------------------------------------------------------------------ backward
@@ -1429,5 +1887,80 @@ extern "C" int egtr_rel_head_streams_bf16r_f32(egtr_stream_t stream, const float
   const int OT = num_rel <= 32 ? 1 : 2;
   hipLaunchKernelGGL(rel_head_streams_f32<1>, dim3(256), dim3(256), 0, static_cast<hipStream_t>(stream), w2_rel, w2_conn,
                      w3_rel, num_rel, OT, w2x_rel, w2x_conn, w3x_rel);
+  return egtr_check_launch();
+}
+
+// ---- more than 64 predicate classes (1 <= num_rel <= 256): rel_head_fwd_wide_f32 / rel_head_fwd_wide_x6 -----------------------
+extern "C" int egtr_rel_head_forward_wide_f32(egtr_stream_t stream, const float* gate_q, const float* gate_k,
+                                              const float* uq, const float* uk, const float* b1, const float* w2r,
+                                              const float* b2r, const float* w3r, const float* b3r, const float* w2c,
+                                              const float* b2c, const float* w3c, const float* b3c,
+                                              const float* triplet_dist, const int64_t* node_cls, int batch,
+                                              int num_query, int num_slots, int hidden, int num_rel,
+                                              int num_cls_plus1, float* rel_logits, float* conn_logits,
+                                              float* gate_mean, float* h1_save, float* h2_save) {
+  if (!gate_q || !gate_k || !uq || !uk || !b1 || !w2r || !b2r || !w3r || !b3r || !w2c || !b2c || !w3c || !b3c ||
+      !rel_logits || !conn_logits)
+    return EGTR_E_ARG;
+  if (triplet_dist != nullptr && node_cls == nullptr) return EGTR_E_ARG;
+  if (batch <= 0 || num_query <= 0 || num_slots <= 0 || num_rel <= 0) return EGTR_E_ARG;
+  if (hidden != kHd || num_rel > 256 || num_slots > 10) return EGTR_E_UNSUPPORTED;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const long long tiles = (long long)batch * ((num_query + 7) / 8) * ((num_query + 3) / 4);
+  if (tiles >= (1ll << 31)) return EGTR_E_UNSUPPORTED;
+  const dim3 grid((unsigned)tiles, 2);
+#define EGTR_TW(TT)                                                                                                  \
+  case TT:                                                                                                           \
+    hipLaunchKernelGGL((rel_head_fwd_wide_f32<TT>), grid, dim3(64 * kRhWaves), 0, st, gate_q, gate_k, uq, uk, b1, w2r, \
+                       b2r, w3r, b3r, w2c, b2c, w3c, b3c, triplet_dist, node_cls, batch, num_query, num_rel,         \
+                       num_cls_plus1, rel_logits, conn_logits, gate_mean, h1_save, h2_save);                         \
+    break;
+  switch (num_slots) {
+    EGTR_TW(1) EGTR_TW(2) EGTR_TW(3) EGTR_TW(4) EGTR_TW(5) EGTR_TW(6) EGTR_TW(7) EGTR_TW(8) EGTR_TW(9) EGTR_TW(10)
+    default: return EGTR_E_UNSUPPORTED;
+  }
+#undef EGTR_TW
+  return egtr_check_launch();
+}
+
+extern "C" int egtr_rel_head_forward_wide_bf16x6_f32(egtr_stream_t stream, const float* gate_q, const float* gate_k,
+                                                     const float* uq, const float* uk, const float* b1,
+                                                     const uint16_t* w2x_rel, const float* b2r, const uint16_t* w3x_rel,
+                                                     const float* b3r, const uint16_t* w2x_conn, const float* b2c,
+                                                     const float* w3c, const float* b3c, const float* triplet_dist,
+                                                     const int64_t* node_cls, int batch, int num_query, int num_slots,
+                                                     int hidden, int num_rel, int num_cls_plus1, float* rel_logits,
+                                                     float* conn_logits, float* gate_mean, int apply_sigmoid) {
+  if (!gate_q || !gate_k || !uq || !uk || !b1 || !w2x_rel || !b2r || !w3x_rel || !b3r || !w2x_conn || !b2c || !w3c ||
+      !b3c || !rel_logits || !conn_logits)
+    return EGTR_E_ARG;
+  if (triplet_dist != nullptr && node_cls == nullptr) return EGTR_E_ARG;
+  if (batch <= 0 || num_query <= 0 || num_slots <= 0 || num_rel <= 0) return EGTR_E_ARG;
+  if (hidden != kHd || num_rel > 256 || num_slots > 9) return EGTR_E_UNSUPPORTED;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const long long tiles = (long long)batch * ((num_query + 7) / 8) * ((num_query + 3) / 4);
+  if (tiles >= (1ll << 31)) return EGTR_E_UNSUPPORTED;
+  const dim3 grid((unsigned)tiles, 2);
+#define EGTR_TWX(TT)                                                                                                 \
+  case TT:                                                                                                           \
+    hipLaunchKernelGGL((rel_head_fwd_wide_x6<TT>), grid, dim3(64 * kRhWaves), 0, st, gate_q, gate_k, uq, uk, b1,     \
+                       w2x_rel, b2r, w3x_rel, b3r, w2x_conn, b2c, w3c, b3c, triplet_dist, node_cls, batch, num_query, \
+                       num_rel, num_cls_plus1, rel_logits, conn_logits, gate_mean, apply_sigmoid);                   \
+    break;
+  switch (num_slots) {
+    EGTR_TWX(1) EGTR_TWX(2) EGTR_TWX(3) EGTR_TWX(4) EGTR_TWX(5) EGTR_TWX(6) EGTR_TWX(7) EGTR_TWX(8) EGTR_TWX(9)
+    default: return EGTR_E_UNSUPPORTED;
+  }
+#undef EGTR_TWX
+  return egtr_check_launch();
+}
+
+extern "C" int egtr_rel_head_streams_wide_f32(egtr_stream_t stream, const float* w2_rel, const float* w2_conn,
+                                              const float* w3_rel, int hidden, int num_rel, uint16_t* w2x_rel,
+                                              uint16_t* w2x_conn, uint16_t* w3x_rel) {
+  if (!w2_rel || !w2_conn || !w3_rel || !w2x_rel || !w2x_conn || !w3x_rel || num_rel <= 0) return EGTR_E_ARG;
+  if (hidden != kHd || num_rel > 256) return EGTR_E_UNSUPPORTED;
+  hipLaunchKernelGGL(rel_head_streams_wide_f32, dim3(256), dim3(256), 0, static_cast<hipStream_t>(stream), w2_rel, w2_conn,
+                     w3_rel, num_rel, (num_rel + 31) / 32, w2x_rel, w2x_conn, w3x_rel);
   return egtr_check_launch();
 }

@@ -463,7 +463,8 @@ class SceneGraphGenerationLoss(nn.Module):
         per image on ``device``; targets that carry ``rel`` pass through untouched."""
         if rel_targets.has_dense(targets):
             return targets
-        bits = self._rel_bits(targets, device) if not any("rel" in t for t in targets) else None
+        bits = (self._rel_bits(targets, device)
+                if not any("rel" in t for t in targets) and self.num_rel_labels <= rel_targets.MAX_REL_LABELS else None)
         return rel_targets.dense_targets(targets, self.num_object_queries, self.num_rel_labels, device, bits)
 
     @torch.no_grad()
@@ -474,7 +475,9 @@ class SceneGraphGenerationLoss(nn.Module):
         # subject and object are both matched; no dense target is built.
         num, den = [], []
         bits = None
-        if not any("rel" in t for t in targets):
+        if self.num_rel_labels > rel_targets.MAX_REL_LABELS:   # no packed words above 64 predicates: dense targets
+            targets = self._dense_targets(targets, matching_costs[0].device)
+        elif not any("rel" in t for t in targets):
             bits = self._rel_bits(targets, matching_costs[0].device)
         else:
             targets = self._dense_targets(targets, matching_costs[0].device)
@@ -520,6 +523,10 @@ class SceneGraphGenerationLoss(nn.Module):
     def loss_relations(self, outputs, targets, indices, matching_costs, num_boxes):
         """egtr:754-815.  Index tensors are moved to the logits' device once per image (the reference indexes
         device tensors with CPU index tensors, egtr:761-785; same values)."""
+        if self.num_rel_labels > rel_targets.MAX_REL_LABELS:
+            # a word holds 64 predicates: above that ``rel_triplets`` targets are materialised densely (once per step by
+            # ``forward``, here when the term is called on its own) and take the dense loss entries, generic in R
+            targets = self._dense_targets(targets, outputs["pred_rel"].device)
         dense = rel_targets.has_dense(targets)
         packed = not dense and not any("rel" in t for t in targets)   # every target carries ``rel_triplets`` only
         sampled = (self.model_training and self.rel_sample_negatives is not None
@@ -723,6 +730,9 @@ class SceneGraphGenerationLoss(nn.Module):
         """``_forward`` with the words of ``rel_triplets`` targets packed ONCE for the step (egtr_amd.targets.pack_relations)
         and shared by the terms that read relation targets."""
         if (any(name in self.losses for name in ("relations", "uncertainty")) and "pred_rel" in outputs
+                and self.num_rel_labels > rel_targets.MAX_REL_LABELS):
+            targets = self._dense_targets(targets, outputs["pred_rel"].device)   # no words above 64 predicates
+        elif (any(name in self.losses for name in ("relations", "uncertainty")) and "pred_rel" in outputs
                 and not any("rel" in t for t in targets)):
             dev = outputs["pred_rel"].device
             self._rel_bits_cache = (targets, dev, rel_targets.pack_relations(

@@ -9,7 +9,8 @@ from .. import _lib
 from .._lib import _chk
 from .linear import _split3_bf16
 
-__all__ = ["rel_head_split_weights", "rel_head_streams", "relation_head_split_bf16", "relation_head_train_forward", "hungarian_match",
+__all__ = ["rel_head_split_weights", "rel_head_streams", "relation_head_split_bf16", "relation_head_train_forward",
+           "REL_HEAD_MAX_REL", "REL_HEAD_NARROW_MAX_REL", "rel_head_streams_wide", "relation_head_split_bf16_wide", "hungarian_match",
            "hungarian_match_route", "HUNGARIAN_MAX_SIDE", "HUNGARIAN_LARGE_MAX_TARGETS", "HUNGARIAN_LARGE_MAX_QUERIES",
            "pack_detection_targets", "pack_relation_bits", "relation_loss_launch", "relation_loss_all_launch"]
 
@@ -141,6 +142,59 @@ def relation_head_split_bf16(gate_q, gate_k, uq, uk, b1, w2x_rel, b2r, w3x_rel, 
         _chk(node_cls, "node_cls", torch.int64)
         c1 = td.shape[0]
     _lib.launch("egtr_rel_head_forward_bf16x6_f32", gq.data_ptr(), gk.data_ptr(), uq_.data_ptr(), uk_.data_ptr(),
+                b1_.data_ptr(), w2x_rel.data_ptr(), b2r_.data_ptr(), w3x_rel.data_ptr(), b3r_.data_ptr(), w2x_conn.data_ptr(),
+                b2c_.data_ptr(), w3c_.data_ptr(), b3c_.data_ptr(), _lib.ptr(td), _lib.ptr(node_cls if td is not None else None),
+                B, N, T, 256, R, c1, rel.data_ptr(), conn.data_ptr(), _lib.ptr(gm), 1 if sigmoid else 0)
+    return rel, conn.unsqueeze(-1), gm
+
+
+REL_HEAD_NARROW_MAX_REL = 64    # every entry but the wide ones
+REL_HEAD_MAX_REL = 256          # egtr_rel_head_forward_wide_f32 / _wide_bf16x6_f32 (the evaluators' kEvalMaxRel)
+
+
+def rel_head_streams_wide(w2r, w3r, w2c):
+    """The operand streams of egtr_rel_head_forward_wide_bf16x6_f32 in one launch (egtr_rel_head_streams_wide_f32), num_rel <=
+    256: w2x [8 nt][16 t][3 piece][2 hf][32 pi][8] per MLP as ``rel_head_streams``, and the relation output weights in the SAME
+    order, w3x [OT][16 t][3 piece][2 hf][32 pi][8] = piece(W3)[32 ot + pi][16 t + 8 hf + e], OT = ceil(num_rel / 32), rows
+    beyond num_rel zero."""
+    w2r_, w3r_, w2c_ = (_chk(t.detach().contiguous(), n, torch.float32)
+                        for t, n in ((w2r, "w2r"), (w3r, "w3r"), (w2c, "w2c")))
+    R = w3r_.shape[0]
+    dev = w2r_.device
+    w2xr = torch.empty(8, 16, 3, 2, 32, 8, dtype=torch.bfloat16, device=dev)
+    w2xc = torch.empty(8, 16, 3, 2, 32, 8, dtype=torch.bfloat16, device=dev)
+    w3x = torch.empty((R + 31) // 32, 16, 3, 2, 32, 8, dtype=torch.bfloat16, device=dev)
+    _lib.launch("egtr_rel_head_streams_wide_f32", w2r_.data_ptr(), w2c_.data_ptr(), w3r_.data_ptr(), w2r_.shape[1], R,
+                w2xr.data_ptr(), w2xc.data_ptr(), w3x.data_ptr())
+    return w2xr, w3x, w2xc
+
+
+def relation_head_split_bf16_wide(gate_q, gate_k, uq, uk, b1, w2x_rel, b2r, w3x_rel, b3r, w2x_conn, b2c, w3c, b3c,
+                                  num_rel, triplet_dist=None, node_cls=None, want_gate_mean=False, sigmoid=False):
+    """``relation_head_split_bf16`` for up to 256 predicate classes (egtr_rel_head_forward_wide_bf16x6_f32; the streams from
+    ``rel_head_streams_wide``).  No autograd."""
+    B, N, T = gate_q.shape
+    dev = gate_q.device
+    f32 = [_chk(t.detach().contiguous(), n, torch.float32)
+           for t, n in ((gate_q, "gate_q"), (gate_k, "gate_k"), (uq, "uq"), (uk, "uk"), (b1, "b1"), (b2r, "b2r"),
+                        (b3r, "b3r"), (b2c, "b2c"), (w3c, "w3c"), (b3c, "b3c"))]
+    gq, gk, uq_, uk_, b1_, b2r_, b3r_, b2c_, w3c_, b3c_ = f32
+    R = int(num_rel)
+    for t, n, shape in ((w2x_rel, "w2x_rel", (8, 16, 3, 2, 32, 8)), (w2x_conn, "w2x_conn", (8, 16, 3, 2, 32, 8)),
+                        (w3x_rel, "w3x_rel", ((R + 31) // 32, 16, 3, 2, 32, 8))):
+        _chk(t, n, torch.bfloat16)
+        if tuple(t.shape) != shape:
+            raise RuntimeError(f"{n} must have shape {shape}, got {tuple(t.shape)}")
+    rel = torch.empty(B, N, N, R, dtype=torch.float32, device=dev)
+    conn = torch.empty(B, N, N, dtype=torch.float32, device=dev)
+    gm = torch.zeros(T, dtype=torch.float32, device=dev) if want_gate_mean else None
+    td = None
+    c1 = 0
+    if triplet_dist is not None:
+        td = _chk(triplet_dist.detach().contiguous(), "triplet_dist", torch.float32)
+        _chk(node_cls, "node_cls", torch.int64)
+        c1 = td.shape[0]
+    _lib.launch("egtr_rel_head_forward_wide_bf16x6_f32", gq.data_ptr(), gk.data_ptr(), uq_.data_ptr(), uk_.data_ptr(),
                 b1_.data_ptr(), w2x_rel.data_ptr(), b2r_.data_ptr(), w3x_rel.data_ptr(), b3r_.data_ptr(), w2x_conn.data_ptr(),
                 b2c_.data_ptr(), w3c_.data_ptr(), b3c_.data_ptr(), _lib.ptr(td), _lib.ptr(node_cls if td is not None else None),
                 B, N, T, 256, R, c1, rel.data_ptr(), conn.data_ptr(), _lib.ptr(gm), 1 if sigmoid else 0)

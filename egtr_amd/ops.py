@@ -1347,7 +1347,9 @@ class RelationHeadFunction(Function):
             P_ = B * N * N
             h1s = torch.empty(2, P_, Hd, dtype=torch.float32, device=gate_q.device) if need_grad else None
             h2s = torch.empty(2, P_, Hd, dtype=torch.float32, device=gate_q.device) if need_grad else None
-            _lib.launch("egtr_rel_head_forward_save_f32", *[t.data_ptr() for t in tens], _lib.ptr(triplet_dist),
+            # more than 64 predicate classes: the wide entry (layer 3 per output tile), the same arithmetic and the same saves
+            _lib.launch("egtr_rel_head_forward_wide_f32" if R > REL_HEAD_NARROW_MAX_REL else "egtr_rel_head_forward_save_f32",
+                        *[t.data_ptr() for t in tens], _lib.ptr(triplet_dist),
                         _lib.ptr(node_cls if triplet_dist is not None else None), B, N, T, Hd, R, c1, rel.data_ptr(),
                         conn.data_ptr(), _lib.ptr(gm), _lib.ptr(h1s), _lib.ptr(h2s))
         if need_grad:
@@ -1428,6 +1430,8 @@ def relation_head_bf16w(gate_q, gate_k, uq, uk, b1, w2r, b2r, w3r, b3r, w2c, b2c
     Hd = w2r.shape[1]
     R = w3r.shape[0]
     dev = gate_q.device
+    if R > REL_HEAD_NARROW_MAX_REL:   # neither bf16 entry serves them: ``_relation_head`` routes such a model to the fp32 wide kernel
+        raise ValueError(f"relation_head_bf16w serves at most {REL_HEAD_NARROW_MAX_REL} predicate classes, got {R}")
     packed = REL_HEAD_BF16_PACKED and T <= 10 and Hd == 256 and R <= 64
     tables = []
     for t, n in ((uq, "uq"), (uk, "uk")):
@@ -1505,9 +1509,14 @@ def relation_head(gate_q, gate_k, uq, uk, b1, w2r, b2r, w3r, b3r, w2c, b2c, w3c,
 def _relation_head(gate_q, gate_k, uq, uk, b1, w2r, b2r, w3r, b3r, w2c, b2c, w3c, b3c, triplet_dist, node_cls,
                    want_gate_mean, owner, sigmoid):
     if (REL_HEAD_SPLIT_BF16 and owner is not None and gate_q.dtype == torch.float32 and gate_q.is_cuda
-            and w2r.shape == (256, 256) and w3r.shape[0] <= 64 and gate_q.shape[-1] <= 9
+            and w2r.shape == (256, 256) and w3r.shape[0] <= REL_HEAD_MAX_REL and gate_q.shape[-1] <= 9
             and not (torch.is_grad_enabled() and any(
                 t.requires_grad for t in (gate_q, gate_k, uq, uk, b1, w2r, b2r, w3r, b3r, w2c, b2c, w3c, b3c)))):
+        if w3r.shape[0] > REL_HEAD_NARROW_MAX_REL:   # 65 .. 256 predicate classes: the wide kernel, streams of their own
+            w2xr, w3xr, w2xc = cached_weights(owner, "rel_head_split_bf16_wide", [w2r, w3r, w2c],
+                                              lambda: rel_head_streams_wide(w2r, w3r, w2c))
+            return relation_head_split_bf16_wide(gate_q, gate_k, uq, uk, b1, w2xr, b2r, w3xr, b3r, w2xc, b2c, w3c, b3c,
+                                                 w3r.shape[0], triplet_dist, node_cls, want_gate_mean, sigmoid)
         w2xr, w3xr, w2xc = cached_weights(owner, "rel_head_split_bf16", [w2r, w3r, w2c],
                                           lambda: rel_head_split_weights(w2r, w3r, w2c))
         return relation_head_split_bf16(gate_q, gate_k, uq, uk, b1, w2xr, b2r, w3xr, b3r, w2xc, b2c, w3c, b3c,
@@ -1516,7 +1525,10 @@ def _relation_head(gate_q, gate_k, uq, uk, b1, w2r, b2r, w3r, b3r, w2c, b2c, w3c
         rel, conn, gm = _relation_head(gate_q, gate_k, uq, uk, b1, w2r, b2r, w3r, b3r, w2c, b2c, w3c, b3c, triplet_dist,
                                        node_cls, want_gate_mean, None, False)
         return rel.sigmoid(), conn.sigmoid(), gm
-    if gate_q.dtype == torch.bfloat16 and not (torch.is_grad_enabled() and any(
+    # (a bf16 model has no fast route above 64 predicate classes: egtr_rel_head_forward_bf16w / _bf16p refuse them, the call
+    # falls through to the fp32 wide kernel on widened operands below)
+    if gate_q.dtype == torch.bfloat16 and w3r.shape[0] <= REL_HEAD_NARROW_MAX_REL and not (
+            torch.is_grad_enabled() and any(
             t.requires_grad for t in (gate_q, gate_k, uq, uk, b1, w2r, b2r, w3r, b3r, w2c, b2c, w3c, b3c))):
         rel, conn, gm = relation_head_bf16w(gate_q, gate_k, uq, uk, b1, w2r, b2r, w3r, b3r, w2c, b2c, w3c, b3c,
                                             triplet_dist, node_cls, want_gate_mean)

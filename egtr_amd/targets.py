@@ -10,14 +10,18 @@ themselves instead:
 
 A dict that has ``"rel"`` is read as before, whatever else it carries.  Below the public interface the triplets become
 ``rel_bits``: int64 [B, N, N] read as unsigned, bit p of word [b, s, o] set iff (s, o, p) is a triplet of image b (a target
-value is 0 or 1 and R <= 64 for every supported dataset).  The loss kernels read the words (csrc/loss.hip,
-egtr_relation_loss_bits_f32); ``unpack_relations`` gives the dense tensor back to the routes that evaluate the reference's
-tensor composition."""
+value is 0 or 1).  The loss kernels read the words (csrc/loss.hip, egtr_relation_loss_bits_f32); ``unpack_relations`` gives the
+dense tensor back to the routes that evaluate the reference's tensor composition.
+
+A word holds 64 predicates.  With a larger vocabulary (``num_rel_labels`` > ``MAX_REL_LABELS``, up to the relation head's 256)
+there are no words: ``dense_targets`` materialises the triplets as the dense tensor directly (``materialize_relations``) and
+the criterion takes the dense loss entries, which are generic in R."""
 import torch
 
 from .kernels.heads import pack_relation_bits
 
-__all__ = ["MAX_REL_LABELS", "relation_triplets", "has_dense", "pack_relations", "unpack_relations", "dense_targets"]
+__all__ = ["MAX_REL_LABELS", "relation_triplets", "has_dense", "pack_relations", "unpack_relations", "materialize_relations",
+           "dense_targets"]
 
 MAX_REL_LABELS = 64
 _INT64_MIN = -(1 << 63)
@@ -110,12 +114,33 @@ def unpack_relations(rel_bits, b, num_rel_labels):
     return ((rel_bits[b].unsqueeze(-1) >> shifts) & 1).to(torch.float32)
 
 
+def materialize_relations(target, b, num_queries, num_rel_labels, device):
+    """The dense fp32 [N, N, R] target of ONE image (index ``b`` in its batch, for the message) from its ``"rel_triplets"``, any
+    R: one zero fill, one indexed write, no synchronisation.  Host triplets are checked like ``pack_relations`` checks them
+    (ValueError); a row that already lives on a device and has an index out of range is dropped, like the pack kernel's guard
+    -- it is written to a spare element behind the tensor."""
+    N, R = int(num_queries), int(num_rel_labels)
+    t = _triplets_of(target)
+    if not t.is_cuda:
+        _check_host(t, b, N, R)
+    flat = torch.zeros(N * N * R + 1, dtype=torch.float32, device=device)
+    if t.shape[0]:
+        t = t.to(device)
+        ok = (t >= 0).all(1) & (t[:, 0] < N) & (t[:, 1] < N) & (t[:, 2] < R)
+        flat.index_fill_(0, torch.where(ok, (t[:, 0] * N + t[:, 1]) * R + t[:, 2], N * N * R), 1.0)
+    return flat[:N * N * R].view(N, N, R)
+
+
 def dense_targets(targets, num_queries, num_rel_labels, device, rel_bits=None):
     """The targets with a dense ``"rel"`` each: a target that already has one is passed through, the others get theirs from
     the packed words (``rel_bits`` of the whole batch when the caller already packed it).  For the routes that evaluate the
-    reference's tensor composition; N N R floats per image."""
+    reference's tensor composition; N N R floats per image.  More than ``MAX_REL_LABELS`` predicates: straight from the
+    triplets (``materialize_relations``), no words."""
     if has_dense(targets):
         return targets
+    if rel_bits is None and int(num_rel_labels) > MAX_REL_LABELS:
+        return [t if "rel" in t else dict(t, rel=materialize_relations(t, i, num_queries, num_rel_labels, device))
+                for i, t in enumerate(targets)]
     if rel_bits is None:
         missing = [i for i, t in enumerate(targets) if "rel" not in t]
         rel_bits = pack_relations([targets[i] for i in missing], num_queries, num_rel_labels, device)

@@ -1134,6 +1134,40 @@ int egtr_rel_head_forward_bf16x6_save_f32(egtr_stream_t stream, const float* gat
 int egtr_rel_head_streams_f32(egtr_stream_t stream, const float* w2_rel, const float* w2_conn, const float* w3_rel,
                               int hidden, int num_rel, uint16_t* w2x_rel, uint16_t* w2x_conn, uint16_t* w3x_rel);
 
+/* ---- 1 <= num_rel <= 256 predicate classes (the entries above answer EGTR_E_UNSUPPORTED for num_rel > 64) ----
+ * The same arithmetic with layer 3 restructured: layers 1 and 2 are computed once per pair tile, then the relation output layer
+ * runs per 32-wide output tile over the whole hidden width, so nothing in the kernel grows with num_rel.  Where both serve
+ * (num_rel <= 64) h1 / h2 / conn / gate_mean are bit-equal to the narrow entry's; rel differs by the order of the fp32 additions
+ * of layer 3 (one chain of 256 instead of two of 128 summed).
+ * EGTR_E_UNSUPPORTED for num_rel > 256, hidden != 256 or a slot count outside the range, EGTR_E_ARG for a NULL operand or a
+ * frequency-bias table without node_cls -- before anything is written.
+ *
+ * egtr_rel_head_forward_wide_f32: arguments, slot range (num_slots <= 10) and kernel arithmetic (exact f32,
+ * v_mfma_f32_32x32x2_f32) of egtr_rel_head_forward_save_f32; gate_mean / h1_save / h2_save optional.  The training forward. */
+int egtr_rel_head_forward_wide_f32(egtr_stream_t stream, const float* gate_q, const float* gate_k, const float* uq,
+                                   const float* uk, const float* b1, const float* w2r, const float* b2r,
+                                   const float* w3r, const float* b3r, const float* w2c, const float* b2c,
+                                   const float* w3c, const float* b3c, const float* triplet_dist,
+                                   const int64_t* node_cls, int batch, int num_query, int num_slots, int hidden,
+                                   int num_rel, int num_cls_plus1, float* rel_logits, float* conn_logits,
+                                   float* gate_mean, float* h1_save, float* h2_save);
+
+/* egtr_rel_head_forward_wide_bf16x6_f32: arguments and slot range (num_slots <= 9) of egtr_rel_head_forward_bf16x6_f32, the
+ * six-term split product.  Inference only.  w2x_* as there; the relation output weights in the SAME order as w2x,
+ *   w3x_rel [OT][16 t][3 piece][64 lane][8], OT = ceil(num_rel / 32):
+ *           piece(W3)[32 ot + (lane & 31)][16 t + 8 (lane >> 5) + e], rows >= num_rel zero
+ * (egtr_rel_head_streams_wide_f32 builds all three streams in one launch). */
+int egtr_rel_head_forward_wide_bf16x6_f32(egtr_stream_t stream, const float* gate_q, const float* gate_k, const float* uq,
+                                          const float* uk, const float* b1, const uint16_t* w2x_rel, const float* b2r,
+                                          const uint16_t* w3x_rel, const float* b3r, const uint16_t* w2x_conn,
+                                          const float* b2c, const float* w3c, const float* b3c,
+                                          const float* triplet_dist, const int64_t* node_cls, int batch, int num_query,
+                                          int num_slots, int hidden, int num_rel, int num_cls_plus1, float* rel_logits,
+                                          float* conn_logits, float* gate_mean, int apply_sigmoid);
+
+int egtr_rel_head_streams_wide_f32(egtr_stream_t stream, const float* w2_rel, const float* w2_conn, const float* w3_rel,
+                                   int hidden, int num_rel, uint16_t* w2x_rel, uint16_t* w2x_conn, uint16_t* w3x_rel);
+
 /* The training forward with ONE product per element in layers 2 and 3 (matmul precision "bf16" of the training step): the
  * post-ReLU activations of layers 1 and 2 and the weights W2 / W3 are each rounded once to bfloat16 (round to nearest even,
  * bit-equal to a float -> bfloat16 cast: Inf and NaN survive, a finite value beyond 3.39e38 becomes Inf), one matrix
