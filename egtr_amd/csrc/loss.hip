@@ -15,7 +15,8 @@
 // Launches: prep | 3 x (histogram, find) | final (loss terms, dense d loss / d pred_rel, pair flags) | connectivity.
 // All counts stay on the device; the only inputs from the host are tensor shapes.
 // The passes that read the target are templates on a target accessor: dense fp32 [N, N, R] per image (the reference's format,
-// egtr_relation_loss_f32) or one 64-bit word per (subject, object) pair (egtr_relation_loss_bits_f32).
+// egtr_relation_loss_f32), one 64-bit word per (subject, object) pair (egtr_relation_loss_bits_f32) or, for 65 to
+// 256 predicates, ceil(R / 64) words per pair (egtr_relation_loss_wide_bits_f32).
 // Evaluation mode (and training with both sample counts None) selects nothing: BCE over all elements, egtr_relation_loss_all_*:
 // maps | all-elements pass | connectivity | finalize.
 #include <hip/hip_runtime.h>
@@ -106,6 +107,37 @@ struct PackedTarget {   // [B, N, N] 64-bit words, bit r of word (row, col) = th
     }
   };
   __device__ __forceinline__ Image image(int b, int N, int R) const { return Image{bits + (size_t)b * N * N, R}; }
+};
+
+struct PackedTargetWide {   // [B, N, N, W] 64-bit words, W = ceil(R / 64): bit r & 63 of word r >> 6 of pair (row, col) = the
+  const unsigned long long* bits;   // target of predicate r (R <= 256); bits at positions >= R are zero
+  struct Pair {
+    const unsigned long long* w;
+    __device__ __forceinline__ float at(int r) const { return ((w[r >> 6] >> (r & 63)) & 1ull) ? 1.0f : 0.0f; }   // ONE word
+  };
+  struct Image {
+    const unsigned long long* w;
+    int R, W;
+    __device__ __forceinline__ Pair pair(size_t rc) const { return Pair{w + rc * W}; }
+    __device__ __forceinline__ void count_block(const int64_t* tg, int T, int N, int tid, int nthreads, int& nt,
+                                                int& nf) const {
+      // popcount over the T x T x W words, the LAST word of a pair masked to its R - 64 (W - 1) valid bits (1 .. 64: no shift by 64)
+      const int tail = R - 64 * (W - 1);
+      const unsigned long long last = tail >= 64 ? ~0ull : ((1ull << tail) - 1ull);
+      int n = 0;
+      for (int e = tid; e < T * T * W; e += nthreads) {
+        const int pr = e / W, k = e - pr * W, a = pr / T, c = pr - a * T;
+        const unsigned long long v = w[((size_t)tg[a] * N + (size_t)tg[c]) * W + k];
+        n += __popcll(k == W - 1 ? (v & last) : v);
+      }
+      nt += n;
+      nf += (tid == 0 ? T * T * R : 0) - n;   // summed over the workgroup: T T R - n_true
+    }
+  };
+  __device__ __forceinline__ Image image(int b, int N, int R) const {
+    const int W = (R + 63) >> 6;
+    return Image{bits + (size_t)b * N * N * W, R, W};
+  }
 };
 
 constexpr int kPrepT = 1024;   // one workgroup per image, sixteen waves: the T x T x R count below is ~500 dependent gathers per thread with four
@@ -251,8 +283,9 @@ __global__ __launch_bounds__(kLT) void rel_loss_hist(const float* __restrict__ p
         prob = 1;
       }
       const unsigned key = key_of(pr[(size_t)qa * NR + e]);
-      if (PASS == 1 && (key >> 21) != (s.prefix[prob] >> 21)) continue;
-      if (PASS == 2 && (key >> 10) != (s.prefix[prob] >> 10)) continue;
+      const unsigned pref = prob ? s.prefix[1] : s.prefix[0];   // a select: indexing the local copy by `prob` put it in scratch
+      if (PASS == 1 && (key >> 21) != (pref >> 21)) continue;
+      if (PASS == 2 && (key >> 10) != (pref >> 10)) continue;
       atomicAdd(&s_h[prob][(key >> kShift) & kMask], 1u);
     }
   }
@@ -857,6 +890,54 @@ extern "C" int egtr_relation_loss_all_bits_f32(egtr_stream_t stream, const float
   if (num_rel > 64) return EGTR_E_UNSUPPORTED;
   return relation_loss_all_launch(stream, pred_rel, pred_conn,
                                   PackedTarget{reinterpret_cast<const unsigned long long*>(rel_bits)}, pred_idx, tgt_idx,
+                                  match_cost, out_offsets, batch, num_query, num_rel, nonmatching_cost, loss_out, grad_rel,
+                                  grad_conn, workspace);
+}
+
+// ---- wide packed words: rel_bits [batch, N, N, W], W = ceil(num_rel / 64), num_rel <= 256 (egtr_pack_relations_wide_u64) ------
+// The argument lists and workspaces of the _bits_ entries; the same kernel templates through PackedTargetWide, so each returns the
+// bits of the dense entry on the dense form of the same target.  With W = 1 the memory is that of the [batch, N, N] words.
+namespace {
+constexpr int kWideMaxRel = 256;
+}
+
+extern "C" int egtr_relation_loss_wide_bits_f32(egtr_stream_t stream, const float* pred_rel, const float* pred_conn,
+                                                const uint64_t* rel_bits, const int64_t* pred_idx, const int64_t* tgt_idx,
+                                                const float* match_cost, const int* out_offsets, int batch, int num_query,
+                                                int num_rel, float nonmatching_cost, int sample_negatives,
+                                                int sample_nonmatching, float* loss_out, float* grad_rel, float* grad_conn,
+                                                void* workspace) {
+  if (!rel_bits) return EGTR_E_ARG;
+  if (num_rel > kWideMaxRel) return EGTR_E_UNSUPPORTED;
+  return relation_loss_launch(stream, pred_rel, pred_conn,
+                              PackedTargetWide{reinterpret_cast<const unsigned long long*>(rel_bits)}, pred_idx, tgt_idx,
+                              match_cost, out_offsets, batch, num_query, num_rel, nonmatching_cost, sample_negatives,
+                              sample_nonmatching, loss_out, grad_rel, grad_conn, workspace);
+}
+
+extern "C" int egtr_relation_loss_det_wide_bits_f32(egtr_stream_t stream, const float* pred_rel, const float* pred_conn,
+                                                    const uint64_t* rel_bits, const int64_t* pred_idx, const int64_t* tgt_idx,
+                                                    const float* match_cost, const int* out_offsets, int batch, int num_query,
+                                                    int num_rel, float nonmatching_cost, int sample_negatives,
+                                                    int sample_nonmatching, float* loss_out, float* grad_rel,
+                                                    float* grad_conn, void* workspace) {
+  if (!rel_bits) return EGTR_E_ARG;
+  if (num_rel > kWideMaxRel) return EGTR_E_UNSUPPORTED;
+  return relation_loss_launch(stream, pred_rel, pred_conn,
+                              PackedTargetWide{reinterpret_cast<const unsigned long long*>(rel_bits)}, pred_idx, tgt_idx,
+                              match_cost, out_offsets, batch, num_query, num_rel, nonmatching_cost, sample_negatives,
+                              sample_nonmatching, loss_out, grad_rel, grad_conn, workspace, true);
+}
+
+extern "C" int egtr_relation_loss_all_wide_bits_f32(egtr_stream_t stream, const float* pred_rel, const float* pred_conn,
+                                                    const uint64_t* rel_bits, const int64_t* pred_idx, const int64_t* tgt_idx,
+                                                    const float* match_cost, const int* out_offsets, int batch, int num_query,
+                                                    int num_rel, float nonmatching_cost, float* loss_out, float* grad_rel,
+                                                    float* grad_conn, void* workspace) {
+  if (!rel_bits) return EGTR_E_ARG;
+  if (num_rel > kWideMaxRel) return EGTR_E_UNSUPPORTED;
+  return relation_loss_all_launch(stream, pred_rel, pred_conn,
+                                  PackedTargetWide{reinterpret_cast<const unsigned long long*>(rel_bits)}, pred_idx, tgt_idx,
                                   match_cost, out_offsets, batch, num_query, num_rel, nonmatching_cost, loss_out, grad_rel,
                                   grad_conn, workspace);
 }

@@ -449,22 +449,38 @@ class SceneGraphGenerationLoss(nn.Module):
         card_pred = (logits.argmax(-1) != logits.shape[-1] - 1).sum(1)
         return {"cardinality_error": F.l1_loss(card_pred.float(), tgt_lengths.float())}
 
-    def _rel_bits(self, targets, device):
-        """The packed words [B, N, N] of a batch of ``rel_triplets`` targets (egtr_amd.targets.pack_relations): packed once
-        per step by ``forward`` and shared by the loss terms; packed here when a term is called on its own."""
+    def _cached_bits(self, targets, device):
         c = self._rel_bits_cache
-        if c is not None and c[0] is targets and c[1] == device:
-            return c[2]
-        return rel_targets.pack_relations(targets, self.num_object_queries, self.num_rel_labels, device)
+        return c[2] if c is not None and c[0] is targets and c[1] == device else None
+
+    def _rel_bits(self, targets, device):
+        """The packed words of a batch of ``rel_triplets`` targets -- [B, N, N] up to 64 predicates
+        (egtr_amd.targets.pack_relations), the wide [B, N, N, W] up to 256 (pack_relations_wide): packed once
+        per step by ``forward`` and shared by the loss terms; packed here when a term is called on its own."""
+        bits = self._cached_bits(targets, device)
+        if bits is not None:
+            return bits
+        pack = (rel_targets.pack_relations_wide if self.num_rel_labels > rel_targets.MAX_REL_LABELS
+                else rel_targets.pack_relations)
+        return pack(targets, self.num_object_queries, self.num_rel_labels, device)
+
+    def _dense_first(self, targets):
+        """Above 64 predicates, what cannot take the wide words -- more than 256 predicates, or a batch in which some target
+        carries the dense ``rel`` -- is given dense targets before anything else, and takes the dense loss entries."""
+        R = self.num_rel_labels
+        return R > rel_targets.MAX_PACKED_REL_LABELS or (R > rel_targets.MAX_REL_LABELS and any("rel" in t for t in targets))
 
     def _dense_targets(self, targets, device):
         """The targets with a dense fp32 [N, N, R] ``rel`` each -- what the routes that evaluate the reference's tensor
-        composition read: ``rel_triplets`` targets are MATERIALISED here (egtr_amd.targets.unpack_relations), N N R floats
+        composition read: ``rel_triplets`` targets are MATERIALISED here (egtr_amd.targets.unpack_relations; above 64
+        predicates from the step's wide words when ``forward`` packed them, else straight from the triplets), N N R floats
         per image on ``device``; targets that carry ``rel`` pass through untouched."""
         if rel_targets.has_dense(targets):
             return targets
-        bits = (self._rel_bits(targets, device)
-                if not any("rel" in t for t in targets) and self.num_rel_labels <= rel_targets.MAX_REL_LABELS else None)
+        bits = None
+        if not any("rel" in t for t in targets):
+            bits = (self._rel_bits(targets, device) if self.num_rel_labels <= rel_targets.MAX_REL_LABELS
+                    else self._cached_bits(targets, device))
         return rel_targets.dense_targets(targets, self.num_object_queries, self.num_rel_labels, device, bits)
 
     @torch.no_grad()
@@ -475,7 +491,7 @@ class SceneGraphGenerationLoss(nn.Module):
         # subject and object are both matched; no dense target is built.
         num, den = [], []
         bits = None
-        if self.num_rel_labels > rel_targets.MAX_REL_LABELS:   # no packed words above 64 predicates: dense targets
+        if self._dense_first(targets):   # no packed words above 256 predicates: dense targets
             targets = self._dense_targets(targets, matching_costs[0].device)
         elif not any("rel" in t for t in targets):
             bits = self._rel_bits(targets, matching_costs[0].device)
@@ -485,8 +501,12 @@ class SceneGraphGenerationLoss(nn.Module):
             if bits is not None:
                 tidx = index[1].to(bits.device)
                 shifts = torch.arange(self.num_rel_labels, dtype=torch.int64, device=bits.device)
-                words = bits[b][tidx][:, tidx]                                              # [T, T]
-                cnt = ((words.unsqueeze(-1) >> shifts) & 1).sum(-1).to(matching_cost.dtype)
+                words = bits[b][tidx][:, tidx]                                              # [T, T] or, wide, [T, T, W]
+                if bits.dim() == 4:   # over the pair's W words; bits at positions >= R are zero
+                    shifts = torch.arange(64, dtype=torch.int64, device=bits.device)
+                    cnt = ((words.unsqueeze(-1) >> shifts) & 1).sum((-1, -2)).to(matching_cost.dtype)
+                else:
+                    cnt = ((words.unsqueeze(-1) >> shifts) & 1).sum(-1).to(matching_cost.dtype)
             else:
                 tidx = index[1].to(target["rel"].device)
                 cnt = (target["rel"][tidx][:, tidx] != 0).sum(-1).to(matching_cost.dtype)   # [T, T]
@@ -523,9 +543,9 @@ class SceneGraphGenerationLoss(nn.Module):
     def loss_relations(self, outputs, targets, indices, matching_costs, num_boxes):
         """egtr:754-815.  Index tensors are moved to the logits' device once per image (the reference indexes
         device tensors with CPU index tensors, egtr:761-785; same values)."""
-        if self.num_rel_labels > rel_targets.MAX_REL_LABELS:
-            # a word holds 64 predicates: above that ``rel_triplets`` targets are materialised densely (once per step by
-            # ``forward``, here when the term is called on its own) and take the dense loss entries, generic in R
+        if self._dense_first(targets):
+            # the wide words hold 256 predicates: above that ``rel_triplets`` targets are materialised densely (once per step
+            # by ``forward``, here when the term is called on its own) and take the dense loss entries, generic in R
             targets = self._dense_targets(targets, outputs["pred_rel"].device)
         dense = rel_targets.has_dense(targets)
         packed = not dense and not any("rel" in t for t in targets)   # every target carries ``rel_triplets`` only
@@ -730,13 +750,12 @@ class SceneGraphGenerationLoss(nn.Module):
         """``_forward`` with the words of ``rel_triplets`` targets packed ONCE for the step (egtr_amd.targets.pack_relations)
         and shared by the terms that read relation targets."""
         if (any(name in self.losses for name in ("relations", "uncertainty")) and "pred_rel" in outputs
-                and self.num_rel_labels > rel_targets.MAX_REL_LABELS):
-            targets = self._dense_targets(targets, outputs["pred_rel"].device)   # no words above 64 predicates
+                and self._dense_first(targets)):
+            targets = self._dense_targets(targets, outputs["pred_rel"].device)   # no words above 256 predicates
         elif (any(name in self.losses for name in ("relations", "uncertainty")) and "pred_rel" in outputs
                 and not any("rel" in t for t in targets)):
-            dev = outputs["pred_rel"].device
-            self._rel_bits_cache = (targets, dev, rel_targets.pack_relations(
-                targets, self.num_object_queries, self.num_rel_labels, dev))
+            dev = outputs["pred_rel"].device   # (no cache yet: ``_rel_bits`` packs, wide above 64 predicates)
+            self._rel_bits_cache = (targets, dev, self._rel_bits(targets, dev))
         try:
             return self._forward(outputs, targets, matched)
         finally:

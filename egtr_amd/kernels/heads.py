@@ -12,7 +12,8 @@ from .linear import _split3_bf16
 __all__ = ["rel_head_split_weights", "rel_head_streams", "relation_head_split_bf16", "relation_head_train_forward",
            "REL_HEAD_MAX_REL", "REL_HEAD_NARROW_MAX_REL", "rel_head_streams_wide", "relation_head_split_bf16_wide", "hungarian_match",
            "hungarian_match_route", "HUNGARIAN_MAX_SIDE", "HUNGARIAN_LARGE_MAX_TARGETS", "HUNGARIAN_LARGE_MAX_QUERIES",
-           "pack_detection_targets", "pack_relation_bits", "relation_loss_launch", "relation_loss_all_launch"]
+           "pack_detection_targets", "pack_relation_bits", "pack_relation_bits_wide", "relation_loss_launch",
+           "relation_loss_all_launch"]
 
 
 def _rel_head_pieces(w, terms):
@@ -322,15 +323,41 @@ def pack_relation_bits(triplets, offsets, batch, total, num_query, num_rel):
     return bits
 
 
+def pack_relation_bits_wide(triplets, offsets, batch, total, num_query, num_rel):
+    """egtr_pack_relations_wide_u64: the same operands -> the words int64 [batch, N, N, W], W = ceil(num_rel / 64), for up to
+    256 predicates (bit p & 63 of word (s, o, p >> 6)).  ``egtr_amd.targets.pack_relations_wide`` is the public route."""
+    _chk(triplets, "triplets", torch.int64)
+    _chk(offsets, "offsets", torch.int32)
+    bits = torch.empty(batch, num_query, num_query, (int(num_rel) + 63) // 64, dtype=torch.int64, device=triplets.device)
+    _lib.launch("egtr_pack_relations_wide_u64", triplets.data_ptr(), offsets.data_ptr(), int(batch), int(total),
+                int(num_query), int(num_rel), bits.data_ptr())
+    return bits
+
+
+def _packed_suffix(target, packed, B, N, R):
+    """The entry suffix for ``target``: "f32" (pointer table), "bits_f32" (words [B, N, N]) or "wide_bits_f32" (words
+    [B, N, N, W], W = ceil(R / 64)) -- the rank of the words selects the entry."""
+    if not packed:
+        return "f32"
+    _chk(target, "rel_bits", torch.int64)
+    if target.dim() == 4:
+        if tuple(target.shape) != (B, N, N, (R + 63) // 64):
+            raise RuntimeError(f"wide rel_bits must have shape {(B, N, N, (R + 63) // 64)}, got {tuple(target.shape)}")
+        return "wide_bits_f32"
+    if tuple(target.shape) != (B, N, N):
+        raise RuntimeError(f"rel_bits must have shape {(B, N, N)}, got {tuple(target.shape)}")
+    return "bits_f32"
+
+
 def relation_loss_launch(pred_rel, pred_conn, target, packed, pred_idx, tgt_idx, match_cost, out_off, nonmatching_cost,
                          sample_negatives, sample_nonmatching, deterministic=False):
     """egtr_relation_loss_f32 (``target``: the device table of per-image pointers to dense fp32 targets) or, with
-    ``packed``, egtr_relation_loss_bits_f32 (``target``: the words int64 [B, N, N]).  Returns (loss [2], grad_rel, grad_conn).
+    ``packed``, egtr_relation_loss_bits_f32 (``target``: the words int64 [B, N, N]) / egtr_relation_loss_wide_bits_f32 (the
+    words int64 [B, N, N, ceil(R / 64)]).  Returns (loss [2], grad_rel, grad_conn).
     ``deterministic``: the egtr_relation_loss_det_* forms (ties at the selection threshold taken lowest flat index first)."""
     B, N, _, R = pred_rel.shape
     dev = pred_rel.device
-    if packed and tuple(_chk(target, "rel_bits", torch.int64).shape) != (B, N, N):
-        raise RuntimeError(f"rel_bits must have shape {(B, N, N)}, got {tuple(target.shape)}")
+    suffix = _packed_suffix(target, packed, B, N, R)
     loss = torch.empty(2, dtype=torch.float32, device=dev)
     grad_rel = torch.empty_like(pred_rel)
     grad_conn = torch.empty_like(pred_conn)
@@ -339,7 +366,7 @@ def relation_loss_launch(pred_rel, pred_conn, target, packed, pred_idx, tgt_idx,
     else:
         nbytes, entry = _lib.lib().egtr_relation_loss_workspace_bytes(B, N), "egtr_relation_loss_"
     ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
-    _lib.launch(entry + ("bits_f32" if packed else "f32"), pred_rel.data_ptr(),
+    _lib.launch(entry + suffix, pred_rel.data_ptr(),
                 pred_conn.data_ptr(), target.data_ptr(), pred_idx.data_ptr(), tgt_idx.data_ptr(), match_cost.data_ptr(),
                 out_off.data_ptr(), B, N, R, float(nonmatching_cost), int(sample_negatives), int(sample_nonmatching),
                 loss.data_ptr(), grad_rel.data_ptr(), grad_conn.data_ptr(), ws.data_ptr())
@@ -348,18 +375,18 @@ def relation_loss_launch(pred_rel, pred_conn, target, packed, pred_idx, tgt_idx,
 
 def relation_loss_all_launch(pred_rel, pred_conn, target, packed, pred_idx, tgt_idx, match_cost, out_off, nonmatching_cost,
                              want_grad=True):
-    """egtr_relation_loss_all_f32 / (``packed``) egtr_relation_loss_all_bits_f32: the un-sampled relation loss -- BCE over all
+    """egtr_relation_loss_all_f32 / (``packed``) egtr_relation_loss_all_bits_f32 or, for 4-D words,
+    egtr_relation_loss_all_wide_bits_f32: the un-sampled relation loss -- BCE over all
     N N R elements -- and the connectivity loss; ``target`` as in ``relation_loss_launch``.  Returns (loss [2], grad_rel,
     grad_conn); ``want_grad=False`` is the value-only launch: no gradient buffer is allocated or written, both come back None."""
     B, N, _, R = pred_rel.shape
     dev = pred_rel.device
-    if packed and tuple(_chk(target, "rel_bits", torch.int64).shape) != (B, N, N):
-        raise RuntimeError(f"rel_bits must have shape {(B, N, N)}, got {tuple(target.shape)}")
+    suffix = _packed_suffix(target, packed, B, N, R)
     loss = torch.empty(2, dtype=torch.float32, device=dev)
     grad_rel = torch.empty_like(pred_rel) if want_grad else None
     grad_conn = torch.empty_like(pred_conn) if want_grad else None
     ws = torch.empty(int(_lib.lib().egtr_relation_loss_all_workspace_bytes(B, N)), dtype=torch.uint8, device=dev)
-    _lib.launch("egtr_relation_loss_all_" + ("bits_f32" if packed else "f32"), pred_rel.data_ptr(), pred_conn.data_ptr(),
+    _lib.launch("egtr_relation_loss_all_" + suffix, pred_rel.data_ptr(), pred_conn.data_ptr(),
                 target.data_ptr(), pred_idx.data_ptr(), tgt_idx.data_ptr(), match_cost.data_ptr(), out_off.data_ptr(), B, N, R,
                 float(nonmatching_cost), loss.data_ptr(), _lib.ptr(grad_rel), _lib.ptr(grad_conn), ws.data_ptr())
     return loss, grad_rel, grad_conn

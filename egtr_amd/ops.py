@@ -1546,7 +1546,8 @@ def _relation_head(gate_q, gate_k, uq, uk, b1, w2r, b2r, w3r, b3r, w2c, b2c, w3c
 class RelationLossFunction(Function):
     """loss_rel / loss_connectivity of the SGG criterion (training mode, largest-score sampling) with their gradients
     from one pass over the logits (csrc/loss.hip, egtr_relation_loss_f32; egtr_relation_loss_bits_f32 when ``packed``:
-    ``target`` is then the words [B, N, N] instead of the pointer table); backward only scales the stored gradients."""
+    ``target`` is then the words [B, N, N] instead of the pointer table, or the wide words [B, N, N, ceil(R / 64)], which take
+    egtr_relation_loss_wide_bits_f32); backward only scales the stored gradients."""
 
     @staticmethod
     def forward(ctx, pred_rel, pred_conn, target, pred_idx, tgt_idx, match_cost, out_off, nonmatching_cost,
@@ -1572,7 +1573,7 @@ RELATION_LOSS_ALL = True   # module attribute (tests patch it for the switch-off
 class RelationLossAllFunction(Function):
     """loss_rel / loss_connectivity of the SGG criterion WITHOUT sampling -- evaluation mode (validation_loss) and training with
     both ``rel_sample_*`` None: BCE over all N N R elements (csrc/loss.hip, egtr_relation_loss_all_f32; ``packed``:
-    egtr_relation_loss_all_bits_f32).  ``want_grad``: None = when ``pred_rel`` or ``pred_conn`` requires grad; False is the
+    egtr_relation_loss_all_bits_f32, or _all_wide_bits_f32 for 4-D words).  ``want_grad``: None = when ``pred_rel`` or ``pred_conn`` requires grad; False is the
     value-only launch -- no gradient buffer exists.  Backward only scales the stored gradients."""
 
     @staticmethod
@@ -1691,7 +1692,8 @@ def relation_losses(pred_rel, pred_conn, targets, indices, matching_costs, nonma
                     sample_nonmatching, rel_bits=None):
     """(loss_rel, loss_connectivity) for device tensors: see RelationLossFunction.  ``indices`` / ``matching_costs``: the
     matcher's per-image device tensors; ``targets[b]["rel"]``: dense fp32 [N, N, R] on the device.  Targets that carry
-    ``"rel_triplets"`` and no ``"rel"`` take the packed entry: ``rel_bits`` (``egtr_amd.targets.pack_relations``) when the
+    ``"rel_triplets"`` and no ``"rel"`` take the packed entry: ``rel_bits`` (``egtr_amd.targets.pack_relations``, or
+    ``pack_relations_wide`` for 65 .. 256 predicates: 4-D words take the wide entries) when the
     caller packed the batch already, else packed here -- no dense target exists on that route.
     ``sample_negatives`` and ``sample_nonmatching`` both None: the un-sampled loss over all elements
     (RelationLossAllFunction; value-only when nothing requires grad).  Exactly one None is not a kernel route (the criterion
@@ -1705,8 +1707,10 @@ def relation_losses(pred_rel, pred_conn, targets, indices, matching_costs, nonma
         if any("rel" in t for t in targets):
             raise ValueError('a batch mixes dense "rel" targets and "rel_triplets" targets: convert one kind '
                              "(egtr_amd.targets.dense_targets)")
-        if rel_bits is None:
-            rel_bits = rel_targets.pack_relations(targets, pred_rel.shape[1], pred_rel.shape[3], dev)
+        if rel_bits is None:   # up to 64 predicates one word per pair, up to 256 the wide words (their rank selects the entry)
+            wide = rel_targets.MAX_REL_LABELS < pred_rel.shape[3] <= rel_targets.MAX_PACKED_REL_LABELS
+            rel_bits = (rel_targets.pack_relations_wide if wide else rel_targets.pack_relations)(
+                targets, pred_rel.shape[1], pred_rel.shape[3], dev)
         target = rel_bits
     else:
         rels = [_chk(t["rel"] if t["rel"].is_contiguous() else t["rel"].contiguous(), "target rel", torch.float32)

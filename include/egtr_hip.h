@@ -576,6 +576,32 @@ int egtr_relation_loss_all_bits_f32(egtr_stream_t stream, const float* pred_rel,
                                     float nonmatching_cost, float* loss_out, float* grad_rel, float* grad_conn,
                                     void* workspace);
 
+/* Packed words for up to 256 predicates: rel_bits [batch, N, N, W] uint64 with W = ceil(num_rel / 64); bit p & 63 of word
+ * (s, o, p >> 6) of image b set iff (s, o, p) is one of the image's triplets, bits at positions >= num_rel zero (W = 1: the
+ * memory of the [batch, N, N] words above).  egtr_pack_relations_wide_u64: the contract of egtr_pack_relations_u64 (one
+ * memset + one launch, rel_bits fully overwritten, a row with an index out of range dropped, a duplicate counted once).  The
+ * three loss entries take the argument lists and workspaces of their _bits_ siblings and run the same passes in the same
+ * order: each returns the bits of the dense entry on the dense form of the same target; a target is one bit of ONE word
+ * (r >> 6), the block count a popcount over T T W words.  num_rel > 256: EGTR_E_UNSUPPORTED; every other limit is the dense
+ * entries'. */
+int egtr_pack_relations_wide_u64(egtr_stream_t stream, const int64_t* triplets, const int* offsets, int batch, int total,
+                                 int num_query, int num_rel, uint64_t* rel_bits);
+int egtr_relation_loss_wide_bits_f32(egtr_stream_t stream, const float* pred_rel, const float* pred_conn,
+                                     const uint64_t* rel_bits, const int64_t* pred_idx, const int64_t* tgt_idx,
+                                     const float* match_cost, const int* out_offsets, int batch, int num_query, int num_rel,
+                                     float nonmatching_cost, int sample_negatives, int sample_nonmatching, float* loss_out,
+                                     float* grad_rel, float* grad_conn, void* workspace);
+int egtr_relation_loss_det_wide_bits_f32(egtr_stream_t stream, const float* pred_rel, const float* pred_conn,
+                                         const uint64_t* rel_bits, const int64_t* pred_idx, const int64_t* tgt_idx,
+                                         const float* match_cost, const int* out_offsets, int batch, int num_query,
+                                         int num_rel, float nonmatching_cost, int sample_negatives, int sample_nonmatching,
+                                         float* loss_out, float* grad_rel, float* grad_conn, void* workspace);
+int egtr_relation_loss_all_wide_bits_f32(egtr_stream_t stream, const float* pred_rel, const float* pred_conn,
+                                         const uint64_t* rel_bits, const int64_t* pred_idx, const int64_t* tgt_idx,
+                                         const float* match_cost, const int* out_offsets, int batch, int num_query,
+                                         int num_rel, float nonmatching_cost, float* loss_out, float* grad_rel,
+                                         float* grad_conn, void* workspace);
+
 /* IoU matrix of the reference's native evaluator routine, lib/fpn/box_intersections_cpu/bbox.pyx: mode 0 =
  * bbox_overlaps (:21-61), mode 1 = bbox_intersections (:64-108).  boxes [num_boxes, 4], query_boxes [num_query, 4]
  * (x0, y0, x1, y1), float64 like the reference (DTYPE = np.float), "+1 pixel" convention; out [num_boxes, num_query],
