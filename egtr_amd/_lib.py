@@ -131,6 +131,13 @@ SIGNATURES = {
     "egtr_relation_loss_det_wide_bits_f32": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, ctypes.c_float, _I, _I, _P, _P, _P,
                                              _P],
     "egtr_relation_loss_all_wide_bits_f32": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, ctypes.c_float, _P, _P, _P, _P],
+    # the policy entries: the sibling's arguments + policy_neg, policy_nm, seed, rng_stream, deterministic
+    "egtr_relation_loss_policy_f32": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, ctypes.c_float, _I, _I, _P, _P, _P, _P,
+                                      _I, _I, ctypes.c_longlong, ctypes.c_longlong, _I],
+    "egtr_relation_loss_policy_bits_f32": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, ctypes.c_float, _I, _I, _P, _P, _P, _P,
+                                           _I, _I, ctypes.c_longlong, ctypes.c_longlong, _I],
+    "egtr_relation_loss_policy_wide_bits_f32": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, ctypes.c_float, _I, _I, _P, _P, _P,
+                                                _P, _I, _I, ctypes.c_longlong, ctypes.c_longlong, _I],
     "egtr_rel_head_forward_bf16w": [_P] * 16 + [_I] * 6 + [_P] * 3,
     "egtr_ffn_layernorm_bf16": [_P] * 7 + [ctypes.c_float, _P, _I, _P, _P, _I, _I, _I],
     "egtr_ffn_pack_weights_bf16": [_P, _P, _P, _I, _I, _P],

@@ -24,6 +24,7 @@
 #include <stdint.h>
 
 #include "common.h"
+#include "rel_sample_key.h"
 
 namespace {
 
@@ -43,8 +44,10 @@ struct ImgState {
   int need[2];      // elements equal to thr to take
   int ticket[2];    // tickets handed out to elements equal to thr
   int n_sel;        // n_true + k[0] + k[1]
-  int pad[4];
+  int pad[4];       // policy entries: the random key words (ka, kb) of problem 0, then of problem 1; zero otherwise
 };
+// sampling policy of a class (egtr_relation_loss_policy_*): the k largest logits | a uniform k-subset | the whole class
+constexpr int kPolLargest = 0, kPolRandom = 1, kPolAll = 2;
 static_assert(sizeof(ImgState) == 80, "layout");
 
 __device__ __forceinline__ unsigned key_of(float x) {   // order-preserving: larger float <-> larger unsigned
@@ -193,14 +196,19 @@ __device__ __forceinline__ int rel_prep_maps(const int64_t* __restrict__ pred_id
   return T;
 }
 
-template <class Tgt>
+// POL (the policy entries): pol0 / pol1 = the policy of the block's false candidates / of the elements outside the block.  A
+// class taken whole has k = its size whatever n_true is (the reference skips its sampling block, egtr:848, 878) and nothing to
+// select (krem = 0: the histogram / find passes skip it); a random class gets its key words from (seed, stream, image, class).
+template <class Tgt, bool POL = false>
 __global__ __launch_bounds__(kPrepT) void rel_loss_prep(const int64_t* __restrict__ pred_idx,
                                                      const int64_t* __restrict__ tgt_idx,
                                                      const float* __restrict__ match_cost,
                                                      const int* __restrict__ out_off,
                                                      const Tgt target_rel, int N, int R,
                                                      float nonmatching_cost, int k_neg, int k_nm, ImgState* st,
-                                                     int* tq, float* wq, unsigned char* mq, int* total_sel) {
+                                                     int* tq, float* wq, unsigned char* mq, int* total_sel,
+                                                     int pol0, int pol1, unsigned seed_lo, unsigned seed_hi,
+                                                     unsigned stream_lo, unsigned stream_hi) {
   __shared__ int s_cnt[2];
   const int b = blockIdx.x, tid = threadIdx.x;
   const int o0 = out_off[b];
@@ -221,14 +229,35 @@ __global__ __launch_bounds__(kPrepT) void rel_loss_prep(const int64_t* __restric
     const long long want0 = (long long)s.n_true * k_neg, want1 = (long long)s.n_true * k_nm;
     s.k[0] = s.n_true > 0 ? (int)(want0 < s.n_false ? want0 : s.n_false) : 0;       // egtr:852-858 min(n_true * k, #cands)
     s.k[1] = s.n_true > 0 ? (int)(want1 < n_nm ? want1 : n_nm) : 0;
+    if constexpr (POL) {
+      if (pol0 == kPolAll) s.k[0] = s.n_false;
+      if (pol1 == kPolAll) s.k[1] = (int)n_nm;   // < 2^31: checked by the entry
+    }
     s.krem[0] = s.k[0];
     s.krem[1] = s.k[1];
+    if constexpr (POL) {
+      if (pol0 == kPolAll) s.krem[0] = 0;
+      if (pol1 == kPolAll) s.krem[1] = 0;
+    }
     s.prefix[0] = s.prefix[1] = 0u;
     s.thr[0] = s.thr[1] = 0u;
     s.need[0] = s.need[1] = 0;
     s.ticket[0] = s.ticket[1] = 0;
     s.n_sel = s.n_true + s.k[0] + s.k[1];
     s.pad[0] = s.pad[1] = s.pad[2] = s.pad[3] = 0;
+    if constexpr (POL) {
+      uint32_t w[4];
+      if (pol0 == kPolRandom) {
+        egtr_philox4x32_10((uint32_t)b, 0u, stream_lo, stream_hi, seed_lo, seed_hi, w);
+        s.pad[0] = (int)w[0];
+        s.pad[1] = (int)w[1];
+      }
+      if (pol1 == kPolRandom) {
+        egtr_philox4x32_10((uint32_t)b, 1u, stream_lo, stream_hi, seed_lo, seed_hi, w);
+        s.pad[2] = (int)w[0];
+        s.pad[3] = (int)w[1];
+      }
+    }
     st[b] = s;
     atomicAdd(total_sel, s.n_sel);
   }
@@ -244,11 +273,13 @@ __global__ __launch_bounds__(kPrepT) void rel_all_prep(const int64_t* __restrict
 }
 
 // ---- histogram pass: digit PASS (0: bits 31..21, 1: bits 20..10, 2: bits 9..0) of the candidates under the prefix --------
-template <int PASS, class Tgt>
+// POL: a random class ranks its candidates by egtr_rel_sample_key(flat index) instead of key_of(logit); the select is the same.
+template <int PASS, class Tgt, bool POL = false>
 __global__ __launch_bounds__(kLT) void rel_loss_hist(const float* __restrict__ pred_rel,
                                                      const Tgt target_rel, int N, int R,
                                                      const ImgState* __restrict__ st, const int* __restrict__ tq,
-                                                     const unsigned char* __restrict__ mq, unsigned* __restrict__ hist) {
+                                                     const unsigned char* __restrict__ mq, unsigned* __restrict__ hist,
+                                                     int pol0, int pol1) {
   __shared__ unsigned s_h[2][kBins];
   const int b = blockIdx.y, tid = threadIdx.x;
   const ImgState s = st[b];
@@ -282,7 +313,16 @@ __global__ __launch_bounds__(kLT) void rel_loss_hist(const float* __restrict__ p
         if (s.krem[1] <= 0) continue;
         prob = 1;
       }
-      const unsigned key = key_of(pr[(size_t)qa * NR + e]);
+      unsigned key;
+      if constexpr (POL) {
+        if ((prob ? pol1 : pol0) == kPolRandom)
+          key = egtr_rel_sample_key((unsigned)qa * (unsigned)NR + (unsigned)e, (unsigned)(prob ? s.pad[2] : s.pad[0]),
+                                    (unsigned)(prob ? s.pad[3] : s.pad[1]));
+        else
+          key = key_of(pr[(size_t)qa * NR + e]);
+      } else {
+        key = key_of(pr[(size_t)qa * NR + e]);
+      }
       const unsigned pref = prob ? s.prefix[1] : s.prefix[0];   // a select: indexing the local copy by `prob` put it in scratch
       if (PASS == 1 && (key >> 21) != (pref >> 21)) continue;
       if (PASS == 2 && (key >> 10) != (pref >> 10)) continue;
@@ -346,10 +386,12 @@ __global__ __launch_bounds__(kLT) void rel_loss_find(ImgState* st, const unsigne
 // ---- deterministic route, tie count: candidates EQUAL to the threshold key per (image, query row, problem) --------------------
 // The final pass of that route takes the need[prob] tied candidates with the LOWEST flat index (qa N + qb) R + r: the counts of
 // the rows in front of a row are the rank its first tied candidate starts at.  Integer counts: order-free.
-template <class Tgt>
+// POL: only a `largest` class has ties; a random or whole class counts nothing.
+template <class Tgt, bool POL = false>
 __global__ __launch_bounds__(kLT) void rel_loss_tie_count(const float* __restrict__ pred_rel, const Tgt target_rel, int N, int R,
                                                           const ImgState* __restrict__ st, const int* __restrict__ tq,
-                                                          const unsigned char* __restrict__ mq, int* __restrict__ tiecnt) {
+                                                          const unsigned char* __restrict__ mq, int* __restrict__ tiecnt,
+                                                          int pol0, int pol1) {
   __shared__ int s_c[2];
   const int b = blockIdx.y, tid = threadIdx.x;
   const ImgState s = st[b];
@@ -372,6 +414,9 @@ __global__ __launch_bounds__(kLT) void rel_loss_tie_count(const float* __restric
       const bool blk = ma && mq_b[qb];
       const int prob = blk ? 0 : 1;
       if (s.k[prob] <= 0) continue;
+      if constexpr (POL) {
+        if ((blk ? pol0 : pol1) != kPolLargest) continue;
+      }
       if (blk && !(rel.pair(trow + tq_b[qb]).at(e - qb * R) != 1.0f)) continue;
       const bool tie = key_of(pr[(size_t)qa * NR + e]) == s.thr[prob];
       c0 += (tie && blk) ? 1 : 0;
@@ -389,14 +434,16 @@ __global__ __launch_bounds__(kLT) void rel_loss_tie_count(const float* __restric
 // DET (deterministic route): candidates equal to the threshold key are taken by their rank in flat-index order -- the tied
 // candidates of the rows in front (tiecnt), of the earlier kLT-wide steps of this row (a running base: a step covers kLT
 // consecutive indices) and of the lower threads of this step (ballot + popcount) -- instead of by ticket; no ticket is drawn.
-template <class Tgt, bool DET = false>
+// POL: per class -- whole: every candidate is taken; random: the candidates whose egtr_rel_sample_key is at least the
+// threshold (tie-free: exactly k, no ticket, no tie rank); largest: as without POL.
+template <class Tgt, bool DET = false, bool POL = false>
 __global__ __launch_bounds__(kLT) void rel_loss_final(const float* __restrict__ pred_rel,
                                                       const Tgt target_rel, int N, int R,
                                                       ImgState* st, const int* __restrict__ tq,
                                                       const float* __restrict__ wq, const unsigned char* __restrict__ mq,
                                                       const int* __restrict__ total_sel, float* __restrict__ grad_rel,
                                                       unsigned char* __restrict__ pairflag, double* __restrict__ partial,
-                                                      const int* __restrict__ tiecnt) {
+                                                      const int* __restrict__ tiecnt, int pol0, int pol1) {
   __shared__ double s_red[kLT / 64];
   __shared__ int s_wc[DET ? 2 : 1][kLT / 64][2];   // DET: tied candidates per wave of a step, double-buffered
   __shared__ int s_base[2];                        // DET: tied candidates of the rows in front of this one
@@ -448,9 +495,26 @@ __global__ __launch_bounds__(kLT) void rel_loss_final(const float* __restrict__ 
           const int prob = blk ? 0 : 1;
           if (blk && t != 0.f) mult = 1;
           if ((!blk || t != 1.0f) && s.k[prob] > 0) {
-            const unsigned key = key_of(x);
-            if (key > s.thr[prob]) mult += 1;
-            else tie = key == s.thr[prob];
+            if constexpr (POL) {
+              const int pol = blk ? pol0 : pol1;
+              const unsigned thr = blk ? s.thr[0] : s.thr[1];
+              if (pol == kPolAll) {
+                mult += 1;
+              } else if (pol == kPolRandom) {
+                const unsigned key = egtr_rel_sample_key((unsigned)qa * (unsigned)NR + (unsigned)e,
+                                                         (unsigned)(blk ? s.pad[0] : s.pad[2]),
+                                                         (unsigned)(blk ? s.pad[1] : s.pad[3]));
+                if (key >= thr) mult += 1;
+              } else {
+                const unsigned key = key_of(x);
+                if (key > thr) mult += 1;
+                else tie = key == thr;
+              }
+            } else {
+              const unsigned key = key_of(x);
+              if (key > s.thr[prob]) mult += 1;
+              else tie = key == s.thr[prob];
+            }
           }
         }
         const unsigned long long m0 = __ballot(tie && blk), m1 = __ballot(tie && !blk);
@@ -491,9 +555,26 @@ __global__ __launch_bounds__(kLT) void rel_loss_final(const float* __restrict__ 
       const int prob = blk ? 0 : 1;
       if (blk && t != 0.f) mult = 1;                   // true relation of the matched block (egtr:838)
       if ((!blk || t != 1.0f) && s.k[prob] > 0) {      // sampled by score (egtr:852-895)
-        const unsigned key = key_of(x);
-        if (key > s.thr[prob]) mult += 1;
-        else if (key == s.thr[prob] && atomicAdd(&st[b].ticket[prob], 1) < s.need[prob]) mult += 1;
+        if constexpr (POL) {
+          const int pol = blk ? pol0 : pol1;
+          const unsigned thr = blk ? s.thr[0] : s.thr[1];
+          if (pol == kPolAll) {
+            mult += 1;
+          } else if (pol == kPolRandom) {
+            const unsigned key = egtr_rel_sample_key((unsigned)qa * (unsigned)NR + (unsigned)e,
+                                                     (unsigned)(blk ? s.pad[0] : s.pad[2]),
+                                                     (unsigned)(blk ? s.pad[1] : s.pad[3]));
+            if (key >= thr) mult += 1;
+          } else {
+            const unsigned key = key_of(x);
+            if (key > thr) mult += 1;
+            else if (key == thr && atomicAdd(&st[b].ticket[prob], 1) < (blk ? s.need[0] : s.need[1])) mult += 1;
+          }
+        } else {
+          const unsigned key = key_of(x);
+          if (key > s.thr[prob]) mult += 1;
+          else if (key == s.thr[prob] && atomicAdd(&st[b].ticket[prob], 1) < s.need[prob]) mult += 1;
+        }
       }
       float g = 0.f;
       if (mult) {
@@ -678,17 +759,31 @@ extern "C" long long egtr_relation_loss_det_workspace_bytes(int batch, int num_q
 // The launches of both entries.  pred_idx / tgt_idx / match_cost / out_offsets: the matcher's packed outputs
 // (egtr_hungarian_match_f32).  workspace: device, egtr_relation_loss_workspace_bytes() bytes, contents irrelevant (zeroed
 // here).  loss_out[0] = loss_rel, loss_out[1] = loss_connectivity; grad_rel [B,N,N,R] / grad_conn [B,N,N] = d loss / d logits.
-template <class Tgt>
+// POL: the policy entries (pol_neg / pol_nm per class, seed / stream of the random keys); without it the launches, arguments
+// and code paths of the entries above are what they were.
+template <class Tgt, bool POL = false>
 static int relation_loss_launch(egtr_stream_t stream, const float* pred_rel, const float* pred_conn, const Tgt target_rel,
                                 const int64_t* pred_idx, const int64_t* tgt_idx, const float* match_cost,
                                 const int* out_offsets, int batch, int num_query, int num_rel, float nonmatching_cost,
                                 int sample_negatives, int sample_nonmatching, float* loss_out, float* grad_rel,
-                                float* grad_conn, void* workspace, bool det = false) {
+                                float* grad_conn, void* workspace, bool det = false, int pol_neg = kPolLargest,
+                                int pol_nm = kPolLargest, long long seed = 0, long long rng_stream = 0) {
   if (!pred_rel || !pred_conn || !pred_idx || !tgt_idx || !match_cost || !out_offsets || !loss_out || !grad_rel ||
       !grad_conn || !workspace)
     return EGTR_E_ARG;
   if (batch <= 0 || num_query <= 0 || num_rel <= 0 || sample_negatives < 0 || sample_nonmatching < 0) return EGTR_E_ARG;
   if ((long long)num_query * num_rel >= (1 << 22) || num_query > 4096) return EGTR_E_UNSUPPORTED;
+  bool select = true, ties = det;
+  if constexpr (POL) {
+    const long long per_image = (long long)num_query * num_query * num_rel;
+    const bool any_random = pol_neg == kPolRandom || pol_nm == kPolRandom;
+    const bool any_all = pol_neg == kPolAll || pol_nm == kPolAll;
+    if (any_random && per_image >= (1ll << 32)) return EGTR_E_UNSUPPORTED;   // the flat index is the 32-bit input of the key
+    // a whole class counts every element: the per-image k and the batch's total_sel are 32-bit ints
+    if (any_all && per_image * batch >= (1ll << 31)) return EGTR_E_UNSUPPORTED;
+    select = pol_neg != kPolAll || pol_nm != kPolAll;                       // a class taken whole needs no select passes
+    ties = det && (pol_neg == kPolLargest || pol_nm == kPolLargest);        // ... and only a `largest` class has ties
+  }
   hipStream_t st = static_cast<hipStream_t>(stream);
   const long long B = batch, N = num_query;
   const int rows = (int)((N + kRowsPerWg - 1) / kRowsPerWg);
@@ -715,27 +810,31 @@ static int relation_loss_launch(egtr_stream_t stream, const float* pred_rel, con
   p = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(p) + 7) & ~(uintptr_t)7);
   double* partial_rel = reinterpret_cast<double*>(p);
   double* partial_conn = partial_rel + B * rows;
-  hipLaunchKernelGGL(rel_loss_prep<Tgt>, dim3(batch), dim3(kPrepT), 0, st, pred_idx, tgt_idx, match_cost, out_offsets,
+  const unsigned long long useed = (unsigned long long)seed, ustream = (unsigned long long)rng_stream;
+  hipLaunchKernelGGL((rel_loss_prep<Tgt, POL>), dim3(batch), dim3(kPrepT), 0, st, pred_idx, tgt_idx, match_cost, out_offsets,
                      target_rel, num_query, num_rel, nonmatching_cost, sample_negatives, sample_nonmatching, state, tq, wq,
-                     mq, total_sel);
+                     mq, total_sel, pol_neg, pol_nm, (unsigned)useed, (unsigned)(useed >> 32), (unsigned)ustream,
+                     (unsigned)(ustream >> 32));
   const dim3 gh(rows, batch), gf(2, batch);
-  hipLaunchKernelGGL((rel_loss_hist<0, Tgt>), gh, dim3(kLT), 0, st, pred_rel, target_rel, num_query, num_rel, state, tq, mq,
-                     hist);
-  hipLaunchKernelGGL(rel_loss_find<0>, gf, dim3(kLT), 0, st, state, hist);
-  hipLaunchKernelGGL((rel_loss_hist<1, Tgt>), gh, dim3(kLT), 0, st, pred_rel, target_rel, num_query, num_rel, state, tq, mq,
-                     hist);
-  hipLaunchKernelGGL(rel_loss_find<1>, gf, dim3(kLT), 0, st, state, hist);
-  hipLaunchKernelGGL((rel_loss_hist<2, Tgt>), gh, dim3(kLT), 0, st, pred_rel, target_rel, num_query, num_rel, state, tq, mq,
-                     hist);
-  hipLaunchKernelGGL(rel_loss_find<2>, gf, dim3(kLT), 0, st, state, hist);
-  if (det) {
-    hipLaunchKernelGGL(rel_loss_tie_count<Tgt>, gh, dim3(kLT), 0, st, pred_rel, target_rel, num_query, num_rel, state, tq, mq,
-                       tiecnt);
-    hipLaunchKernelGGL((rel_loss_final<Tgt, true>), gh, dim3(kLT), 0, st, pred_rel, target_rel, num_query, num_rel, state, tq,
-                       wq, mq, total_sel, grad_rel, pairflag, partial_rel, (const int*)tiecnt);
+  if (select) {
+    hipLaunchKernelGGL((rel_loss_hist<0, Tgt, POL>), gh, dim3(kLT), 0, st, pred_rel, target_rel, num_query, num_rel, state, tq,
+                       mq, hist, pol_neg, pol_nm);
+    hipLaunchKernelGGL(rel_loss_find<0>, gf, dim3(kLT), 0, st, state, hist);
+    hipLaunchKernelGGL((rel_loss_hist<1, Tgt, POL>), gh, dim3(kLT), 0, st, pred_rel, target_rel, num_query, num_rel, state, tq,
+                       mq, hist, pol_neg, pol_nm);
+    hipLaunchKernelGGL(rel_loss_find<1>, gf, dim3(kLT), 0, st, state, hist);
+    hipLaunchKernelGGL((rel_loss_hist<2, Tgt, POL>), gh, dim3(kLT), 0, st, pred_rel, target_rel, num_query, num_rel, state, tq,
+                       mq, hist, pol_neg, pol_nm);
+    hipLaunchKernelGGL(rel_loss_find<2>, gf, dim3(kLT), 0, st, state, hist);
+  }
+  if (ties) {
+    hipLaunchKernelGGL((rel_loss_tie_count<Tgt, POL>), gh, dim3(kLT), 0, st, pred_rel, target_rel, num_query, num_rel, state,
+                       tq, mq, tiecnt, pol_neg, pol_nm);
+    hipLaunchKernelGGL((rel_loss_final<Tgt, true, POL>), gh, dim3(kLT), 0, st, pred_rel, target_rel, num_query, num_rel, state,
+                       tq, wq, mq, total_sel, grad_rel, pairflag, partial_rel, (const int*)tiecnt, pol_neg, pol_nm);
   } else {
-    hipLaunchKernelGGL(rel_loss_final<Tgt>, gh, dim3(kLT), 0, st, pred_rel, target_rel, num_query, num_rel, state, tq, wq, mq,
-                       total_sel, grad_rel, pairflag, partial_rel, (const int*)nullptr);
+    hipLaunchKernelGGL((rel_loss_final<Tgt, false, POL>), gh, dim3(kLT), 0, st, pred_rel, target_rel, num_query, num_rel, state,
+                       tq, wq, mq, total_sel, grad_rel, pairflag, partial_rel, (const int*)nullptr, pol_neg, pol_nm);
   }
   const long long n_pairs = B * N * N;
   const int cblocks = (int)std::min<long long>((n_pairs + kLT - 1) / kLT, 1024);
@@ -940,6 +1039,60 @@ extern "C" int egtr_relation_loss_all_wide_bits_f32(egtr_stream_t stream, const 
                                   PackedTargetWide{reinterpret_cast<const unsigned long long*>(rel_bits)}, pred_idx, tgt_idx,
                                   match_cost, out_offsets, batch, num_query, num_rel, nonmatching_cost, loss_out, grad_rel,
                                   grad_conn, workspace);
+}
+
+// ---- policy entries: one sampling policy per class --------------------------------------------------------
+// The arguments of egtr_relation_loss_f32 / _bits_f32 / _wide_bits_f32, then policy_neg / policy_nm (0: the `count n_true`
+// largest logits, 1: a uniform random subset of that size, 2: the whole class -- its count is ignored), the seed and stream of
+// the random keys (rel_sample_key.h) and `deterministic` (the lowest-index tie rule for a `largest` class).  workspace:
+// egtr_relation_loss_det_workspace_bytes() bytes under either tie rule.
+namespace {
+inline bool bad_policy(int p) { return p != kPolLargest && p != kPolRandom && p != kPolAll; }
+}
+
+extern "C" int egtr_relation_loss_policy_f32(egtr_stream_t stream, const float* pred_rel, const float* pred_conn,
+                                             const float* const* target_rel, const int64_t* pred_idx, const int64_t* tgt_idx,
+                                             const float* match_cost, const int* out_offsets, int batch, int num_query,
+                                             int num_rel, float nonmatching_cost, int sample_negatives, int sample_nonmatching,
+                                             float* loss_out, float* grad_rel, float* grad_conn, void* workspace,
+                                             int policy_neg, int policy_nm, long long seed, long long rng_stream,
+                                             int deterministic) {
+  if (!target_rel || bad_policy(policy_neg) || bad_policy(policy_nm)) return EGTR_E_ARG;
+  return relation_loss_launch<DenseTarget, true>(stream, pred_rel, pred_conn, DenseTarget{target_rel}, pred_idx, tgt_idx,
+                                                 match_cost, out_offsets, batch, num_query, num_rel, nonmatching_cost,
+                                                 sample_negatives, sample_nonmatching, loss_out, grad_rel, grad_conn, workspace,
+                                                 deterministic != 0, policy_neg, policy_nm, seed, rng_stream);
+}
+
+extern "C" int egtr_relation_loss_policy_bits_f32(egtr_stream_t stream, const float* pred_rel, const float* pred_conn,
+                                                  const uint64_t* rel_bits, const int64_t* pred_idx, const int64_t* tgt_idx,
+                                                  const float* match_cost, const int* out_offsets, int batch, int num_query,
+                                                  int num_rel, float nonmatching_cost, int sample_negatives,
+                                                  int sample_nonmatching, float* loss_out, float* grad_rel, float* grad_conn,
+                                                  void* workspace, int policy_neg, int policy_nm, long long seed,
+                                                  long long rng_stream, int deterministic) {
+  if (!rel_bits || bad_policy(policy_neg) || bad_policy(policy_nm)) return EGTR_E_ARG;
+  if (num_rel > 64) return EGTR_E_UNSUPPORTED;
+  return relation_loss_launch<PackedTarget, true>(
+      stream, pred_rel, pred_conn, PackedTarget{reinterpret_cast<const unsigned long long*>(rel_bits)}, pred_idx, tgt_idx,
+      match_cost, out_offsets, batch, num_query, num_rel, nonmatching_cost, sample_negatives, sample_nonmatching, loss_out,
+      grad_rel, grad_conn, workspace, deterministic != 0, policy_neg, policy_nm, seed, rng_stream);
+}
+
+extern "C" int egtr_relation_loss_policy_wide_bits_f32(egtr_stream_t stream, const float* pred_rel, const float* pred_conn,
+                                                       const uint64_t* rel_bits, const int64_t* pred_idx,
+                                                       const int64_t* tgt_idx, const float* match_cost, const int* out_offsets,
+                                                       int batch, int num_query, int num_rel, float nonmatching_cost,
+                                                       int sample_negatives, int sample_nonmatching, float* loss_out,
+                                                       float* grad_rel, float* grad_conn, void* workspace, int policy_neg,
+                                                       int policy_nm, long long seed, long long rng_stream,
+                                                       int deterministic) {
+  if (!rel_bits || bad_policy(policy_neg) || bad_policy(policy_nm)) return EGTR_E_ARG;
+  if (num_rel > kWideMaxRel) return EGTR_E_UNSUPPORTED;
+  return relation_loss_launch<PackedTargetWide, true>(
+      stream, pred_rel, pred_conn, PackedTargetWide{reinterpret_cast<const unsigned long long*>(rel_bits)}, pred_idx, tgt_idx,
+      match_cost, out_offsets, batch, num_query, num_rel, nonmatching_cost, sample_negatives, sample_nonmatching, loss_out,
+      grad_rel, grad_conn, workspace, deterministic != 0, policy_neg, policy_nm, seed, rng_stream);
 }
 
 // ---- detection losses of one output set (labels / boxes / cardinality, egtr:611-659, 661-670, 692-712) ------------------

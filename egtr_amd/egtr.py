@@ -570,6 +570,18 @@ class SceneGraphGenerationLoss(nn.Module):
                 None if unsampled else self.rel_sample_nonmatching,
                 rel_bits=self._rel_bits(targets, outputs["pred_rel"].device) if packed else None)
             return {"loss_rel": loss_rel, "loss_connectivity": loss_conn}
+        policies = self._sampling_policies(B_, N_, R_)
+        if (policies is not None and not sampled and outputs["pred_rel"].is_cuda
+                and outputs["pred_rel"].dtype == torch.float32 and not self.force_device_relations
+                and ((dense and all(t["rel"].is_cuda and t["rel"].dtype == torch.float32 for t in targets))
+                     or packed)):
+            # every other training configuration with a sample count -- a class taken whole (its count None) next to a sampled
+            # one, a random class under the device sampler -- as one policy per class in the same HIP pipeline: no host sync
+            loss_rel, loss_conn = ops.relation_losses_sampled(
+                outputs["pred_rel"], outputs["pred_connectivity"], targets, indices, matching_costs,
+                float(self.nonmatching_cost), policies[0], policies[1],
+                rel_bits=self._rel_bits(targets, outputs["pred_rel"].device) if packed else None)
+            return {"loss_rel": loss_rel, "loss_connectivity": loss_conn}
         # every other route evaluates the reference's tensor composition on the dense target: ``rel_triplets`` targets are
         # materialised per image (see _dense_targets) -- the reference's values
         targets = self._dense_targets(targets, outputs["pred_rel"].device)
@@ -605,6 +617,25 @@ class SceneGraphGenerationLoss(nn.Module):
                 loss = self._loss_relations(pred_rel, target_rel, full_matching_cost, None, None)
             losses.append(loss)
         return {"loss_rel": torch.cat(losses).mean(), "loss_connectivity": torch.stack(connect_losses).mean()}
+
+    def _sampling_policies(self, B, N, R):
+        """((policy, count) of the block's false candidates, of the non-matching elements) when the policy kernels
+        (ops.relation_losses_sampled) serve the configuration, else None: training mode, at least one count set, every random
+        class (``*_largest=False``) under ``ops.relation_sampler() == "device"`` -- under the default "python" sampler a random
+        class keeps the reference's composition and its ``random.sample`` draws -- and the entries' shape limits."""
+        if not self.model_training or (self.rel_sample_negatives is None and self.rel_sample_nonmatching is None):
+            return None
+        policies = []
+        for count, largest in ((self.rel_sample_negatives, self.rel_sample_negatives_largest),
+                               (self.rel_sample_nonmatching, self.rel_sample_nonmatching_largest)):
+            policies.append(("all", None) if count is None else ("largest" if largest else "random", int(count)))
+        names = [p[0] for p in policies]
+        if "random" in names and ops.relation_sampler() != "device":
+            return None
+        if N * R >= (1 << 22) or N > 4096 or ("random" in names and N * N * R >= (1 << 32)) or (
+                "all" in names and B * N * N * R >= (1 << 31)):
+            return None
+        return tuple(policies)
 
     def _loss_relations_device(self, outputs, targets, indices, matching_costs):
         """Training-mode relation / connectivity losses (egtr:754-923 with ``*_largest`` sampling) without the

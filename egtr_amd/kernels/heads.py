@@ -13,7 +13,7 @@ __all__ = ["rel_head_split_weights", "rel_head_streams", "relation_head_split_bf
            "REL_HEAD_MAX_REL", "REL_HEAD_NARROW_MAX_REL", "rel_head_streams_wide", "relation_head_split_bf16_wide", "hungarian_match",
            "hungarian_match_route", "HUNGARIAN_MAX_SIDE", "HUNGARIAN_LARGE_MAX_TARGETS", "HUNGARIAN_LARGE_MAX_QUERIES",
            "pack_detection_targets", "pack_relation_bits", "pack_relation_bits_wide", "relation_loss_launch",
-           "relation_loss_all_launch"]
+           "relation_loss_all_launch", "relation_loss_policy_launch", "RELATION_POLICIES"]
 
 
 def _rel_head_pieces(w, terms):
@@ -389,4 +389,40 @@ def relation_loss_all_launch(pred_rel, pred_conn, target, packed, pred_idx, tgt_
     _lib.launch("egtr_relation_loss_all_" + suffix, pred_rel.data_ptr(), pred_conn.data_ptr(),
                 target.data_ptr(), pred_idx.data_ptr(), tgt_idx.data_ptr(), match_cost.data_ptr(), out_off.data_ptr(), B, N, R,
                 float(nonmatching_cost), loss.data_ptr(), _lib.ptr(grad_rel), _lib.ptr(grad_conn), ws.data_ptr())
+    return loss, grad_rel, grad_conn
+
+
+RELATION_POLICIES = {"largest": 0, "random": 1, "all": 2}   # the policy codes of the egtr_relation_loss_policy_* entries
+
+
+def relation_loss_policy_launch(pred_rel, pred_conn, target, packed, pred_idx, tgt_idx, match_cost, out_off, nonmatching_cost,
+                                negatives, nonmatching, seed=0, stream=0, deterministic=False):
+    """egtr_relation_loss_policy_f32 / (``packed``) _policy_bits_f32 or, for 4-D words, _policy_wide_bits_f32: one sampling
+    policy per candidate class.  ``negatives`` / ``nonmatching``: (policy, count) with policy "largest" | "random" | "all" (the
+    count of "all" is ignored; None there).  ``seed`` / ``stream``: the 64-bit words of a random class's keys, reduced modulo
+    2^64.  ``target`` as in ``relation_loss_launch``.  Returns (loss [2], grad_rel, grad_conn)."""
+    B, N, _, R = pred_rel.shape
+    dev = pred_rel.device
+    suffix = _packed_suffix(target, packed, B, N, R)
+    codes, counts = [], []
+    for name, (policy, count) in (("negatives", negatives), ("nonmatching", nonmatching)):
+        if policy not in RELATION_POLICIES:
+            raise ValueError(f"{name}: policy must be one of {tuple(RELATION_POLICIES)}, got {policy!r}")
+        if policy != "all" and (count is None or int(count) < 0):
+            raise ValueError(f"{name}: a {policy!r} class takes a count >= 0, got {count!r}")
+        codes.append(RELATION_POLICIES[policy])
+        counts.append(0 if policy == "all" else int(count))
+
+    def s64(v):   # any Python int -> the signed 64-bit value with the same low 64 bits
+        v = int(v) & 0xFFFFFFFFFFFFFFFF
+        return v - (1 << 64) if v >= (1 << 63) else v
+
+    loss = torch.empty(2, dtype=torch.float32, device=dev)
+    grad_rel = torch.empty_like(pred_rel)
+    grad_conn = torch.empty_like(pred_conn)
+    ws = torch.empty(int(_lib.lib().egtr_relation_loss_det_workspace_bytes(B, N)), dtype=torch.uint8, device=dev)
+    _lib.launch("egtr_relation_loss_policy_" + suffix, pred_rel.data_ptr(), pred_conn.data_ptr(), target.data_ptr(),
+                pred_idx.data_ptr(), tgt_idx.data_ptr(), match_cost.data_ptr(), out_off.data_ptr(), B, N, R,
+                float(nonmatching_cost), counts[0], counts[1], loss.data_ptr(), grad_rel.data_ptr(), grad_conn.data_ptr(),
+                ws.data_ptr(), codes[0], codes[1], s64(seed), s64(stream), 1 if deterministic else 0)
     return loss, grad_rel, grad_conn

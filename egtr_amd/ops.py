@@ -990,6 +990,81 @@ class matmul_precision_mode:
         return False
 
 
+# ---- relation sampler: who draws a RANDOM candidate class of the relation loss ------------------------------
+# The criterion's `rel_sample_*_largest=False` ablation takes a uniform random subset of a candidate class instead of its largest
+# logits.  "python" (the default): the reference's composition -- nonzero() index lists and `random.sample` on the host; Python's
+# `random` stream is consumed exactly as the reference consumes it.  "device" (opt-in): the subset is the k candidates with the
+# largest keyed hash of their flat index (egtr_relation_loss_policy_*): no host wait, and a function of (seed, stream) alone --
+# the same distribution, other bits, and Python's `random` stream is left alone.  Every launch with a random class uses the
+# current `stream` and advances it by one, so auxiliary output sets and successive steps draw independently; (seed, stream) is
+# the whole state (relation_sampler_state / set_relation_sampler_state: checkpoint and resume).  No environment switch.
+_RELATION_SAMPLERS = ("python", "device")
+RELATION_SAMPLER = "python"
+_RELATION_SAMPLER_SEED = None     # None: torch.initial_seed(), read when the first key is needed
+_RELATION_SAMPLER_STREAM = 0
+
+
+def _checked_relation_sampler(name):
+    if name not in _RELATION_SAMPLERS:
+        raise ValueError(f"relation sampler must be one of {_RELATION_SAMPLERS}, got {name!r}")
+    return name
+
+
+def set_relation_sampler(name, seed=None):
+    """"python" (random.sample on the host, the reference's draws) or "device" (the keyed selection of the policy kernels) for a
+    random candidate class of the relation loss; process-wide, returns the previous setting.  ``seed`` (any int) also restarts
+    the stream at 0; ``seed=None`` keeps the current seed and stream (initially ``torch.initial_seed()``, stream 0)."""
+    global RELATION_SAMPLER, _RELATION_SAMPLER_SEED, _RELATION_SAMPLER_STREAM
+    prev = RELATION_SAMPLER
+    RELATION_SAMPLER = _checked_relation_sampler(name)
+    if seed is not None:
+        _RELATION_SAMPLER_SEED, _RELATION_SAMPLER_STREAM = int(seed), 0
+    return prev
+
+
+def relation_sampler():
+    """The current setting: "python" or "device"."""
+    return RELATION_SAMPLER
+
+
+def relation_sampler_state():
+    """(seed, stream) of the device sampler: what the NEXT launch with a random class uses."""
+    global _RELATION_SAMPLER_SEED
+    if _RELATION_SAMPLER_SEED is None:
+        _RELATION_SAMPLER_SEED = int(torch.initial_seed())
+    return _RELATION_SAMPLER_SEED, _RELATION_SAMPLER_STREAM
+
+
+def set_relation_sampler_state(seed, stream):
+    """Resume: the next launch with a random class uses (seed, stream)."""
+    global _RELATION_SAMPLER_SEED, _RELATION_SAMPLER_STREAM
+    _RELATION_SAMPLER_SEED, _RELATION_SAMPLER_STREAM = int(seed), int(stream)
+
+
+def _next_relation_stream():
+    """(seed, stream) for one launch with a random class; the stream advances by one."""
+    global _RELATION_SAMPLER_STREAM
+    seed, stream = relation_sampler_state()
+    _RELATION_SAMPLER_STREAM = stream + 1
+    return seed, stream
+
+
+class relation_sampler_mode:
+    """``with ops.relation_sampler_mode("device", seed=5):`` -- the sampler for a block; restores the previous NAME on exit, on
+    an exception too (the stream keeps counting: draws inside the block are not repeated after it)."""
+
+    def __init__(self, name, seed=None):
+        self.name, self.seed = _checked_relation_sampler(name), seed
+
+    def __enter__(self):
+        self.prev = set_relation_sampler(self.name, self.seed)
+        return self
+
+    def __exit__(self, *exc):
+        set_relation_sampler(self.prev)
+        return False
+
+
 def _gemm_terms():
     """Products per element of a training token GEMM under the current setting (the ``terms`` of the kernels.linear bindings)."""
     return 1 if MATMUL_PRECISION == "bf16" else 6
@@ -1567,6 +1642,30 @@ class RelationLossFunction(Function):
         return grad_rel * g_rel, grad_conn * g_conn, None, None, None, None, None, None, None, None, None
 
 
+class RelationLossPolicyFunction(Function):
+    """loss_rel / loss_connectivity with one sampling policy per candidate class -- ``negatives`` / ``nonmatching`` =
+    (policy, count), policy "largest" | "random" | "all" (csrc/loss.hip, egtr_relation_loss_policy_f32 / _policy_bits_f32 /
+    _policy_wide_bits_f32 by the form of ``target``, as in RelationLossFunction).  ``seed`` / ``stream``: the words of a random
+    class's keys.  Backward only scales the stored gradients."""
+
+    @staticmethod
+    def forward(ctx, pred_rel, pred_conn, target, pred_idx, tgt_idx, match_cost, out_off, nonmatching_cost, negatives,
+                nonmatching, seed, stream, packed=False):
+        pr = _chk(pred_rel.detach().contiguous(), "pred_rel", torch.float32)
+        pc = _chk(pred_conn.detach().contiguous(), "pred_connectivity", torch.float32)
+        loss, grad_rel, grad_conn = relation_loss_policy_launch(pr, pc, target, packed, pred_idx, tgt_idx, match_cost, out_off,
+                                                                nonmatching_cost, negatives, nonmatching, seed, stream,
+                                                                deterministic=is_deterministic())
+        ctx.save_for_backward(grad_rel, grad_conn)
+        return loss[0], loss[1]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_rel, g_conn):
+        grad_rel, grad_conn = ctx.saved_tensors
+        return (grad_rel * g_rel, grad_conn * g_conn) + (None,) * 11
+
+
 RELATION_LOSS_ALL = True   # module attribute (tests patch it for the switch-off twin); no environment switch
 
 
@@ -1688,19 +1787,10 @@ def detection_losses(logits, pred_boxes, flat_match, packed_targets, focal_alpha
             "cardinality_error": (card - lengths).abs().mean()}
 
 
-def relation_losses(pred_rel, pred_conn, targets, indices, matching_costs, nonmatching_cost, sample_negatives,
-                    sample_nonmatching, rel_bits=None):
-    """(loss_rel, loss_connectivity) for device tensors: see RelationLossFunction.  ``indices`` / ``matching_costs``: the
-    matcher's per-image device tensors; ``targets[b]["rel"]``: dense fp32 [N, N, R] on the device.  Targets that carry
-    ``"rel_triplets"`` and no ``"rel"`` take the packed entry: ``rel_bits`` (``egtr_amd.targets.pack_relations``, or
-    ``pack_relations_wide`` for 65 .. 256 predicates: 4-D words take the wide entries) when the
-    caller packed the batch already, else packed here -- no dense target exists on that route.
-    ``sample_negatives`` and ``sample_nonmatching`` both None: the un-sampled loss over all elements
-    (RelationLossAllFunction; value-only when nothing requires grad).  Exactly one None is not a kernel route (the criterion
-    keeps that configuration on its tensor composition): ValueError."""
-    if (sample_negatives is None) != (sample_nonmatching is None):
-        raise ValueError("relation_losses takes both sample counts or neither: with exactly one of sample_negatives / "
-                         "sample_nonmatching None the criterion's tensor route (_loss_relations_device) evaluates the loss")
+def _relation_operands(pred_rel, targets, indices, matching_costs, rel_bits):
+    """What the relation-loss entries read besides the logits: (target, packed, rels, pred_idx, tgt_idx, match_cost, out_off).
+    ``target``: the pointer table of the dense targets (``rels`` keeps their contiguous forms alive until the launches are
+    enqueued) or, for ``rel_triplets`` targets, the packed words."""
     dev = pred_rel.device
     packed = not rel_targets.has_dense(targets)
     if packed:
@@ -1727,6 +1817,25 @@ def relation_losses(pred_rel, pred_conn, targets, indices, matching_costs, nonma
         pi = torch.zeros(1, dtype=torch.int64, device=dev)
         ti = torch.zeros(1, dtype=torch.int64, device=dev)
         mc = torch.zeros(1, dtype=torch.float32, device=dev)
+    if not packed:
+        return target, packed, rels, pi, ti, mc, out_off
+    return target, packed, None, pi, ti, mc, out_off
+
+
+def relation_losses(pred_rel, pred_conn, targets, indices, matching_costs, nonmatching_cost, sample_negatives,
+                    sample_nonmatching, rel_bits=None):
+    """(loss_rel, loss_connectivity) for device tensors: see RelationLossFunction.  ``indices`` / ``matching_costs``: the
+    matcher's per-image device tensors; ``targets[b]["rel"]``: dense fp32 [N, N, R] on the device.  Targets that carry
+    ``"rel_triplets"`` and no ``"rel"`` take the packed entry: ``rel_bits`` (``egtr_amd.targets.pack_relations``, or
+    ``pack_relations_wide`` for 65 .. 256 predicates: 4-D words take the wide entries) when the
+    caller packed the batch already, else packed here -- no dense target exists on that route.
+    ``sample_negatives`` and ``sample_nonmatching`` both None: the un-sampled loss over all elements
+    (RelationLossAllFunction; value-only when nothing requires grad).  Exactly one None is not a kernel route (the criterion
+    keeps that configuration on its tensor composition): ValueError."""
+    if (sample_negatives is None) != (sample_nonmatching is None):
+        raise ValueError("relation_losses takes both sample counts or neither: with exactly one of sample_negatives / "
+                         "sample_nonmatching None the criterion's tensor route (_loss_relations_device) evaluates the loss")
+    target, packed, rels, pi, ti, mc, out_off = _relation_operands(pred_rel, targets, indices, matching_costs, rel_bits)
     if sample_negatives is None:
         want_grad = torch.is_grad_enabled() and (pred_rel.requires_grad or pred_conn.requires_grad)
         out = RelationLossAllFunction.apply(pred_rel, pred_conn, target, pi, ti, mc, out_off, nonmatching_cost, packed,
@@ -1734,6 +1843,27 @@ def relation_losses(pred_rel, pred_conn, targets, indices, matching_costs, nonma
     else:
         out = RelationLossFunction.apply(pred_rel, pred_conn, target, pi, ti, mc, out_off, nonmatching_cost,
                                          sample_negatives, sample_nonmatching, packed)
-    if not packed:
-        del rels   # (kept alive until the launches were enqueued; the caller's targets own the storage)
+    del rels   # (kept alive until the launches were enqueued; the caller's targets own the storage)
+    return out
+
+
+def relation_losses_sampled(pred_rel, pred_conn, targets, indices, matching_costs, nonmatching_cost, negatives, nonmatching,
+                            rel_bits=None, seed=None, stream=None):
+    """(loss_rel, loss_connectivity) with one sampling policy per candidate class (RelationLossPolicyFunction): ``negatives`` --
+    the false candidates of the matched block -- and ``nonmatching`` -- the elements with an unmatched subject or object -- are
+    (policy, count) with policy "largest" (the count n_true largest logits), "random" (a uniform subset of that size) or "all"
+    (the whole class; count ignored).  The other arguments as in ``relation_losses``.  ``seed`` / ``stream``: the words of the
+    random keys; None takes the sampler state (``relation_sampler_state``), and a launch with a random class then advances the
+    stream by one -- whichever sampler is SET: calling this function is asking for the device's selection."""
+    target, packed, rels, pi, ti, mc, out_off = _relation_operands(pred_rel, targets, indices, matching_costs, rel_bits)
+    random_class = "random" in (negatives[0], nonmatching[0])
+    if stream is None:   # the sampler's own stream: consumed by a launch that draws
+        cur_seed, stream = _next_relation_stream() if random_class else relation_sampler_state()
+    else:
+        cur_seed = relation_sampler_state()[0]
+    if seed is None:
+        seed = cur_seed
+    out = RelationLossPolicyFunction.apply(pred_rel, pred_conn, target, pi, ti, mc, out_off, nonmatching_cost,
+                                           tuple(negatives), tuple(nonmatching), int(seed), int(stream), packed)
+    del rels
     return out

@@ -324,7 +324,8 @@ class DataParallelTrainer:
     clip-grad-norm 0.1 and AdamW.  ``num_boxes`` stays per-rank (model/egtr.py:976-980)."""
 
     def __init__(self, model, optimizer=None, accumulate=2, clip=0.1, bucket_cap_mb=25, graph=False, force_ddp=False,
-                 grad_compression=None, deterministic=False, matmul_precision=None):
+                 grad_compression=None, deterministic=False, matmul_precision=None, relation_sampler=None,
+                 relation_sampler_seed=None):
         """graph=True (single process, GPU, fixed image size): the static-shape part of the step -- backbone, encoder,
         decoder, detection + relation heads, forward AND backward -- is captured once into two HIP graphs
         (torch.cuda.make_graphed_callables over ``model.forward_tensors``) and replayed; the Hungarian matcher and the
@@ -348,8 +349,20 @@ class DataParallelTrainer:
         ``ops.set_matmul_precision``), "fp32" or "bf16": every step runs inside ``ops.matmul_precision_mode(..)``.  "bf16": the
         token-sized products of the encoder layers and of the decoder's value projections round each operand once to bf16
         (fp32 accumulation; weights, gradients and the optimizer stay fp32; no loss scaling) -- DESIGN.md 4.12b.  Part of the
-        captured step's key like the deterministic mode, and it combines freely with it: the two touch different kernels."""
+        captured step's key like the deterministic mode, and it combines freely with it: the two touch different kernels.
+
+        ``relation_sampler``: None (follow ``ops.relation_sampler()``), "python" or "device": every step runs inside
+        ``ops.relation_sampler_mode(..)``.  It matters for a criterion with ``rel_sample_*_largest=False`` only: "device" draws the
+        random candidate classes in the loss kernels (no host wait), "python" with the reference's
+        ``random.sample``.  ``relation_sampler_seed``: the device sampler's seed (None: the current one, initially
+        ``torch.initial_seed()``); the rank is added, so replicas draw independently.  The loss is eager in the graphed step
+        too, so the sampler is no part of a captured step's key."""
         from . import ops
+        self.relation_sampler = None if relation_sampler is None else ops._checked_relation_sampler(relation_sampler)
+        rank = dist.get_rank() if dist.is_initialized() else 0
+        if relation_sampler_seed is not None or (self.relation_sampler == "device" and rank):
+            seed = ops.relation_sampler_state()[0] if relation_sampler_seed is None else int(relation_sampler_seed)
+            ops.set_relation_sampler_state(seed + rank, 0)
         self.matmul_precision = None if matmul_precision is None else ops._checked_matmul_precision(matmul_precision)
         self.deterministic = bool(deterministic)
         if self.deterministic:
@@ -456,7 +469,9 @@ class DataParallelTrainer:
         from . import ops
         mode = ops.deterministic(True) if self.deterministic else contextlib.nullcontext()
         prec = ops.matmul_precision_mode(self.matmul_precision) if self.matmul_precision is not None else contextlib.nullcontext()
-        with ctx, mode, prec:
+        sampler = (ops.relation_sampler_mode(self.relation_sampler) if self.relation_sampler is not None
+                   else contextlib.nullcontext())
+        with ctx, mode, prec, sampler:
             loss, loss_dict = self.common_step(batch)
             (loss / self.accumulate).backward()
         if boundary:

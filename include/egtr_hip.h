@@ -602,6 +602,44 @@ int egtr_relation_loss_all_wide_bits_f32(egtr_stream_t stream, const float* pred
                                          int num_rel, float nonmatching_cost, float* loss_out, float* grad_rel,
                                          float* grad_conn, void* workspace);
 
+/* One sampling POLICY per candidate class (policy_neg: the false candidates of the matched block; policy_nm: the elements with
+ * an unmatched subject or object), per image with n_true / n_class as above:
+ *   0 largest: the k = min(count n_true, n_class) largest logits (0 when n_true = 0) -- what the entries above do for both;
+ *   1 random:  a uniform random subset of that size;
+ *   2 all:     the whole class, k = n_class whatever n_true is; its count argument is ignored.
+ * Selected = the true relations of the block U the k chosen of each class; loss, gradient, weights and the connectivity loss
+ * are those of egtr_relation_loss_f32.  (0, 0) selects what the sampled entries select, (2, 2) the elements of the _all_ entries.
+ * The random choice: the k candidates with the largest KEY, key(flat) = lb32(lb32(flat ^ ka) + kb) over the 32-bit flat index
+ * flat = (qa N + qb) R + r in query order, lb32(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16,
+ * and (ka, kb) = the first two words of Philox4x32-10(counter = (image, class, lo32(stream), hi32(stream)), key = (lo32(seed),
+ * hi32(seed))), class 0 = block, 1 = outside.  Every step is a bijection of 32 bits: distinct elements have distinct keys, so a
+ * random class has no ties, draws no ticket and is a function of (seed, rng_stream, image, shape, matching) alone.
+ * deterministic != 0: the lowest-flat-index tie rule of the _det_ entries for a `largest` class.
+ * The three entries take the arguments of egtr_relation_loss_f32 / _bits_f32 / _wide_bits_f32 first and return the same bits
+ * on the same targets.  workspace: egtr_relation_loss_det_workspace_bytes() bytes (under either tie rule).
+ * EGTR_E_ARG: a policy outside 0 .. 2 (before any HIP call).  EGTR_E_UNSUPPORTED: N N R >= 2^32 with a random class (the
+ * flat index is the key's 32-bit input); batch N N R >= 2^31 with a whole class (the selected count is a 32-bit int);
+ * otherwise the limits of the sibling entry. */
+int egtr_relation_loss_policy_f32(egtr_stream_t stream, const float* pred_rel, const float* pred_conn,
+                                  const float* const* target_rel, const int64_t* pred_idx, const int64_t* tgt_idx,
+                                  const float* match_cost, const int* out_offsets, int batch, int num_query, int num_rel,
+                                  float nonmatching_cost, int sample_negatives, int sample_nonmatching, float* loss_out,
+                                  float* grad_rel, float* grad_conn, void* workspace, int policy_neg, int policy_nm,
+                                  long long seed, long long rng_stream, int deterministic);
+int egtr_relation_loss_policy_bits_f32(egtr_stream_t stream, const float* pred_rel, const float* pred_conn,
+                                       const uint64_t* rel_bits, const int64_t* pred_idx, const int64_t* tgt_idx,
+                                       const float* match_cost, const int* out_offsets, int batch, int num_query, int num_rel,
+                                       float nonmatching_cost, int sample_negatives, int sample_nonmatching, float* loss_out,
+                                       float* grad_rel, float* grad_conn, void* workspace, int policy_neg, int policy_nm,
+                                       long long seed, long long rng_stream, int deterministic);
+int egtr_relation_loss_policy_wide_bits_f32(egtr_stream_t stream, const float* pred_rel, const float* pred_conn,
+                                            const uint64_t* rel_bits, const int64_t* pred_idx, const int64_t* tgt_idx,
+                                            const float* match_cost, const int* out_offsets, int batch, int num_query,
+                                            int num_rel, float nonmatching_cost, int sample_negatives, int sample_nonmatching,
+                                            float* loss_out, float* grad_rel, float* grad_conn, void* workspace,
+                                            int policy_neg, int policy_nm, long long seed, long long rng_stream,
+                                            int deterministic);
+
 /* IoU matrix of the reference's native evaluator routine, lib/fpn/box_intersections_cpu/bbox.pyx: mode 0 =
  * bbox_overlaps (:21-61), mode 1 = bbox_intersections (:64-108).  boxes [num_boxes, 4], query_boxes [num_query, 4]
  * (x0, y0, x1, y1), float64 like the reference (DTYPE = np.float), "+1 pixel" convention; out [num_boxes, num_query],
