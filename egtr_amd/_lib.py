@@ -116,6 +116,9 @@ SIGNATURES = {
     "egtr_clamp_if_flag_f32": [_P, _P, _P, ctypes.c_longlong, _P, ctypes.c_float, _I],
     "egtr_detection_loss_f32": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, ctypes.c_float, ctypes.c_float, _P, _P,
                                 _P, _P],
+    "egtr_detection_loss_large_workspace_bytes": [_I, _I, _I],
+    "egtr_detection_loss_large_f32": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, ctypes.c_float, ctypes.c_float, _P,
+                                      _P, _P, _P, _P],
     "egtr_relation_loss_f32": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, ctypes.c_float, _I, _I, _P, _P, _P, _P],
     "egtr_relation_loss_workspace_bytes": [_I, _I],
     "egtr_relation_loss_bits_f32": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, ctypes.c_float, _I, _I, _P, _P, _P, _P],
@@ -198,6 +201,7 @@ _RESTYPES = {"egtr_status_string": ctypes.c_char_p, "egtr_last_hip_error": ctype
              "egtr_input_proj_groupnorm_token_slabs_workspace_floats": ctypes.c_longlong,
              "egtr_msda_backward_bf16_workspace_floats": ctypes.c_longlong,
              "egtr_msda_backward_det_workspace_bytes": ctypes.c_longlong,
+             "egtr_detection_loss_large_workspace_bytes": ctypes.c_longlong,
              "egtr_relation_loss_det_workspace_bytes": ctypes.c_longlong,
              "egtr_relation_loss_all_workspace_bytes": ctypes.c_longlong,
              "egtr_hungarian_match_scratch_doubles": ctypes.c_longlong,

@@ -1108,6 +1108,54 @@ constexpr int kDetMaxN = 2048;
 
 __device__ __forceinline__ float softplusf(float z) { return fmaxf(z, 0.f) + log1pf(expf(-fabsf(z))); }
 
+// One element of the sigmoid focal loss, gamma = 2 (egtr:647-656, dd:2687-2722): the term of logit x whose target is t, and
+// in `grad` its derivative d f / d x (not yet times 1 / num_boxes).  alpha < 0: no alpha weighting.
+__device__ __forceinline__ float focal_term(float x, bool t, float alpha, float& grad) {
+  const float p = 1.f / (1.f + expf(-x));
+  const float ce = softplusf(t ? -x : x);                       // = -log p_t
+  const float pt = t ? p : 1.f - p;
+  const float om = 1.f - pt;
+  const float a = alpha >= 0.f ? (t ? alpha : 1.f - alpha) : 1.f;
+  const float g = a * om * om * (2.f * pt * (-ce) - om);         // d f / d x up to the sign of dp_t/dx
+  grad = t ? g : -g;
+  return a * om * om * ce;
+}
+
+// One matched pair, boxes as (cx, cy, w, h) (egtr:692-712, dd util generalized_box_iou): adds |s - t|_1 to l1sum and
+// 1 - GIoU(s, t) to gsum; g_l1 / g_giou: their derivatives w.r.t. s, times inv_num_boxes.
+__device__ __forceinline__ void box_term(const float4 s, const float4 t, float inv_num_boxes, float& l1sum, float& gsum,
+                                         float4& g_l1, float4& g_giou) {
+  l1sum += fabsf(s.x - t.x) + fabsf(s.y - t.y) + fabsf(s.z - t.z) + fabsf(s.w - t.w);
+  auto sgn = [](float d) { return d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f); };
+  g_l1 = make_float4(sgn(s.x - t.x) * inv_num_boxes, sgn(s.y - t.y) * inv_num_boxes, sgn(s.z - t.z) * inv_num_boxes,
+                     sgn(s.w - t.w) * inv_num_boxes);
+  // corners
+  const float x0 = s.x - 0.5f * s.z, y0 = s.y - 0.5f * s.w, x1 = s.x + 0.5f * s.z, y1 = s.y + 0.5f * s.w;
+  const float u0 = t.x - 0.5f * t.z, v0 = t.y - 0.5f * t.w, u1 = t.x + 0.5f * t.z, v1 = t.y + 0.5f * t.w;
+  const float as = (x1 - x0) * (y1 - y0), at = (u1 - u0) * (v1 - v0);
+  const float iwr = fminf(x1, u1) - fmaxf(x0, u0), ihr = fminf(y1, v1) - fmaxf(y0, v0);
+  const float iw = fmaxf(iwr, 0.f), ih = fmaxf(ihr, 0.f);
+  const float inter = iw * ih, uni = as + at - inter;
+  const float ew = fmaxf(fmaxf(x1, u1) - fminf(x0, u0), 0.f), eh = fmaxf(fmaxf(y1, v1) - fminf(y0, v0), 0.f);
+  const float ea = ew * eh;
+  const float giou = inter / uni - (ea - uni) / ea;
+  gsum += 1.f - giou;
+  // d(iw) / d(x0, x1), d(ew) / d(x0, x1) and the same for y
+  const float iw_x1 = (iwr > 0.f && x1 < u1) ? 1.f : 0.f, iw_x0 = (iwr > 0.f && x0 > u0) ? -1.f : 0.f;
+  const float ih_y1 = (ihr > 0.f && y1 < v1) ? 1.f : 0.f, ih_y0 = (ihr > 0.f && y0 > v0) ? -1.f : 0.f;
+  const float ew_x1 = x1 > u1 ? 1.f : 0.f, ew_x0 = x0 < u0 ? -1.f : 0.f;
+  const float eh_y1 = y1 > v1 ? 1.f : 0.f, eh_y0 = y0 < v0 ? -1.f : 0.f;
+  auto dgiou = [&](float d_as, float d_inter, float d_ea) {
+    const float d_uni = d_as - d_inter;
+    return (d_inter * uni - inter * d_uni) / (uni * uni) + (d_uni * ea - uni * d_ea) / (ea * ea);
+  };
+  const float g_x0 = dgiou(-(y1 - y0), iw_x0 * ih, ew_x0 * eh), g_x1 = dgiou((y1 - y0), iw_x1 * ih, ew_x1 * eh);
+  const float g_y0 = dgiou(-(x1 - x0), iw * ih_y0, ew * eh_y0), g_y1 = dgiou((x1 - x0), iw * ih_y1, ew * eh_y1);
+  // loss = 1 - giou; corners -> (cx, cy, w, h)
+  g_giou = make_float4(-(g_x0 + g_x1) * inv_num_boxes, -(g_y0 + g_y1) * inv_num_boxes,
+                       -0.5f * (g_x1 - g_x0) * inv_num_boxes, -0.5f * (g_y1 - g_y0) * inv_num_boxes);
+}
+
 __global__ __launch_bounds__(kDT) void det_loss_f32(
     const float* __restrict__ logits, const float* __restrict__ boxes, const long long* __restrict__ pred_idx,
     const long long* __restrict__ tgt_idx, const int* __restrict__ moff, const long long* __restrict__ tlabels,
@@ -1140,16 +1188,9 @@ __global__ __launch_bounds__(kDT) void det_loss_f32(
   float* dl = d_logits + (size_t)b * N * C;
   for (int e = tid; e < N * C; e += kDT) {
     const int n = e / C, c = e - n * C;
-    const float x = lg[e];
-    const bool t = s_cls[n] == c;
-    const float p = 1.f / (1.f + expf(-x));
-    const float ce = t ? softplusf(-x) : softplusf(x);            // = -log p_t
-    const float pt = t ? p : 1.f - p;
-    const float om = 1.f - pt;
-    const float a = alpha >= 0.f ? (t ? alpha : 1.f - alpha) : 1.f;
-    fsum += a * om * om * ce;
-    const float g = a * om * om * (2.f * pt * (-ce) - om);         // d f / d x up to the sign of dp_t/dx
-    dl[e] = (t ? g : -g) * inv_num_boxes;
+    float g;
+    fsum += focal_term(lg[e], s_cls[n] == c, alpha, g);
+    dl[e] = g * inv_num_boxes;
   }
 
   // ---- cardinality (egtr:661-670): rows whose argmax is not the LAST class; first maximum on ties, like torch.argmax ---
@@ -1178,37 +1219,10 @@ __global__ __launch_bounds__(kDT) void det_loss_f32(
     const int n = (int)pred_idx[k];
     const float4 s = *reinterpret_cast<const float4*>(boxes + ((size_t)b * N + n) * 4);
     const float4 t = *reinterpret_cast<const float4*>(tboxes + (size_t)(t0 + (int)tgt_idx[k]) * 4);
-    l1sum += fabsf(s.x - t.x) + fabsf(s.y - t.y) + fabsf(s.z - t.z) + fabsf(s.w - t.w);
-    auto sgn = [](float d) { return d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f); };
-    *reinterpret_cast<float4*>(d_l1 + ((size_t)b * N + n) * 4) =
-        make_float4(sgn(s.x - t.x) * inv_num_boxes, sgn(s.y - t.y) * inv_num_boxes, sgn(s.z - t.z) * inv_num_boxes,
-                    sgn(s.w - t.w) * inv_num_boxes);
-    // corners
-    const float x0 = s.x - 0.5f * s.z, y0 = s.y - 0.5f * s.w, x1 = s.x + 0.5f * s.z, y1 = s.y + 0.5f * s.w;
-    const float u0 = t.x - 0.5f * t.z, v0 = t.y - 0.5f * t.w, u1 = t.x + 0.5f * t.z, v1 = t.y + 0.5f * t.w;
-    const float as = (x1 - x0) * (y1 - y0), at = (u1 - u0) * (v1 - v0);
-    const float iwr = fminf(x1, u1) - fmaxf(x0, u0), ihr = fminf(y1, v1) - fmaxf(y0, v0);
-    const float iw = fmaxf(iwr, 0.f), ih = fmaxf(ihr, 0.f);
-    const float inter = iw * ih, uni = as + at - inter;
-    const float ew = fmaxf(fmaxf(x1, u1) - fminf(x0, u0), 0.f), eh = fmaxf(fmaxf(y1, v1) - fminf(y0, v0), 0.f);
-    const float ea = ew * eh;
-    const float giou = inter / uni - (ea - uni) / ea;
-    gsum += 1.f - giou;
-    // d(iw) / d(x0, x1), d(ew) / d(x0, x1) and the same for y
-    const float iw_x1 = (iwr > 0.f && x1 < u1) ? 1.f : 0.f, iw_x0 = (iwr > 0.f && x0 > u0) ? -1.f : 0.f;
-    const float ih_y1 = (ihr > 0.f && y1 < v1) ? 1.f : 0.f, ih_y0 = (ihr > 0.f && y0 > v0) ? -1.f : 0.f;
-    const float ew_x1 = x1 > u1 ? 1.f : 0.f, ew_x0 = x0 < u0 ? -1.f : 0.f;
-    const float eh_y1 = y1 > v1 ? 1.f : 0.f, eh_y0 = y0 < v0 ? -1.f : 0.f;
-    auto dgiou = [&](float d_as, float d_inter, float d_ea) {
-      const float d_uni = d_as - d_inter;
-      return (d_inter * uni - inter * d_uni) / (uni * uni) + (d_uni * ea - uni * d_ea) / (ea * ea);
-    };
-    const float g_x0 = dgiou(-(y1 - y0), iw_x0 * ih, ew_x0 * eh), g_x1 = dgiou((y1 - y0), iw_x1 * ih, ew_x1 * eh);
-    const float g_y0 = dgiou(-(x1 - x0), iw * ih_y0, ew * eh_y0), g_y1 = dgiou((x1 - x0), iw * ih_y1, ew * eh_y1);
-    // loss = 1 - giou; corners -> (cx, cy, w, h)
-    *reinterpret_cast<float4*>(d_giou + ((size_t)b * N + n) * 4) =
-        make_float4(-(g_x0 + g_x1) * inv_num_boxes, -(g_y0 + g_y1) * inv_num_boxes,
-                    -0.5f * (g_x1 - g_x0) * inv_num_boxes, -0.5f * (g_y1 - g_y0) * inv_num_boxes);
+    float4 g_l1, g_giou;
+    box_term(s, t, inv_num_boxes, l1sum, gsum, g_l1, g_giou);
+    *reinterpret_cast<float4*>(d_l1 + ((size_t)b * N + n) * 4) = g_l1;
+    *reinterpret_cast<float4*>(d_giou + ((size_t)b * N + n) * 4) = g_giou;
   }
   // fixed order: the lanes of a wave (butterfly), then the waves in index order
   double fd = (double)fsum, ld = (double)l1sum, gd = (double)gsum;
@@ -1235,7 +1249,184 @@ __global__ __launch_bounds__(kDT) void det_loss_f32(
   }
 }
 
+// ---- the same losses for proposal-sized output sets (two-stage: one proposal per encoder token, N up to 65 536) --------
+// Grid (row chunks, B): a workgroup owns kDetLargeRows consecutive query rows of one image and does everything for them --
+// their class map in LDS (the image's match list scanned for entries in its range), the box terms of those matches, the
+// zero-fill of its rows of the two box gradients, and one wave per row for the focal term, its gradient and the argmax from
+// ONE read of the logits.  Every store goes to a row the workgroup owns: no atomics, no workgroup waits for another.  The
+// partial sums of a workgroup (three doubles, one int) go to the workspace; det_loss_large_sum adds them per image in a
+// fixed order.  kGrad = false: values only, no gradient pointer is touched.
+// Every workgroup of an image scans the image's WHOLE match list (196 workgroups over at most 93 entries at the training
+// shape): the reads grow as chunks x matches, which is nothing for proposal sets against tens of targets and would want a
+// list sorted by query for a set with thousands of matches per image.
+// A row without a finite maximum (all -inf, or NaN) keeps the index C and counts as "not the last class", as in det_loss_f32;
+// torch.argmax answers 0 there, which differs only at C = 1.
+constexpr int kDLT = 256;             // four waves
+constexpr int kDetLargeRows = 32;     // rows per workgroup (DETECTION_LOSS_LARGE_ROWS of the binding)
+constexpr int kDetLargeMaxN = 65536;  // the large matcher's bound
+constexpr int kDetLargeMaxB = 65535;  // grid.y
+template <bool kGrad>
+__global__ __launch_bounds__(kDLT) void det_loss_large_f32(
+    const float* __restrict__ logits, const float* __restrict__ boxes, const long long* __restrict__ pred_idx,
+    const long long* __restrict__ tgt_idx, const int* __restrict__ moff, const long long* __restrict__ tlabels,
+    const float* __restrict__ tboxes, const int* __restrict__ toff, int N, int C, float alpha, float inv_num_boxes,
+    float* __restrict__ d_logits, float* __restrict__ d_l1, float* __restrict__ d_giou, double* __restrict__ ws_sum,
+    int* __restrict__ ws_cnt) {
+  __shared__ int s_cls[kDetLargeRows];
+  __shared__ double s_red[3][kDLT / 64];
+  __shared__ int s_cnt[kDLT / 64];
+  const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int r0 = blockIdx.x * kDetLargeRows, rows = min(kDetLargeRows, N - r0);
+  const int m0 = moff[b], m1 = moff[b + 1], t0 = toff[b], nt_img = toff[b + 1] - t0;
+  if (tid < rows) {
+    s_cls[tid] = C;                                                // "no object" (egtr:640-642)
+    if (kGrad) {
+      *reinterpret_cast<float4*>(d_l1 + ((size_t)b * N + r0 + tid) * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+      *reinterpret_cast<float4*>(d_giou + ((size_t)b * N + r0 + tid) * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+  }
+  __syncthreads();
+  // the image's matches that land in this workgroup's rows; invalid entries are skipped, never dereferenced
+  float l1sum = 0.f, gsum = 0.f;
+  for (int k = m0 + tid; k < m1; k += kDLT) {
+    const long long n = pred_idx[k], g = tgt_idx[k];
+    if (n < r0 || n >= r0 + rows || g < 0 || g >= nt_img) continue;
+    const int cls = tlabels ? (int)tlabels[t0 + (int)g] : 0;      // no labels: class-agnostic targets
+    s_cls[(int)n - r0] = (cls >= 0 && cls < C) ? cls : C;
+    const float4 s = *reinterpret_cast<const float4*>(boxes + ((size_t)b * N + (int)n) * 4);
+    const float4 t = *reinterpret_cast<const float4*>(tboxes + (size_t)(t0 + (int)g) * 4);
+    float4 g_l1, g_giou;
+    box_term(s, t, inv_num_boxes, l1sum, gsum, g_l1, g_giou);
+    if (kGrad) {
+      *reinterpret_cast<float4*>(d_l1 + ((size_t)b * N + (int)n) * 4) = g_l1;
+      *reinterpret_cast<float4*>(d_giou + ((size_t)b * N + (int)n) * 4) = g_giou;
+    }
+  }
+  __syncthreads();
+
+  // a wave per row: focal term + gradient and the running first maximum of the same element
+  float fsum = 0.f;
+  int cnt = 0;
+  for (int r = wave; r < rows; r += kDLT / 64) {
+    const size_t base = ((size_t)b * N + r0 + r) * C;
+    const int cls = s_cls[r];
+    float best = -INFINITY;
+    int bi = C;
+    for (int c = lane; c < C; c += 64) {
+      const float x = logits[base + c];
+      float g;
+      fsum += focal_term(x, cls == c, alpha, g);
+      if (kGrad) d_logits[base + c] = g * inv_num_boxes;
+      if (x > best) { best = x; bi = c; }
+    }
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const float ov = __shfl_xor(best, o);
+      const int oi = __shfl_xor(bi, o);
+      if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
+    }
+    cnt += (bi != C - 1) ? 1 : 0;
+  }
+  if (lane == 0) s_cnt[wave] = cnt;
+  // fixed order: the lanes of a wave (butterfly), then the waves in index order
+  double fd = (double)fsum, ld = (double)l1sum, gd = (double)gsum;
+  for (int o = 32; o > 0; o >>= 1) {
+    fd += __shfl_xor(fd, o);
+    ld += __shfl_xor(ld, o);
+    gd += __shfl_xor(gd, o);
+  }
+  if (lane == 0) {
+    s_red[0][wave] = fd;
+    s_red[1][wave] = ld;
+    s_red[2][wave] = gd;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double f = 0.0, l = 0.0, g = 0.0;
+    int c = 0;
+    for (int i = 0; i < kDLT / 64; ++i) { f += s_red[0][i]; l += s_red[1][i]; g += s_red[2][i]; c += s_cnt[i]; }
+    const size_t w = (size_t)b * gridDim.x + blockIdx.x;
+    ws_sum[w * 3 + 0] = f;
+    ws_sum[w * 3 + 1] = l;
+    ws_sum[w * 3 + 2] = g;
+    ws_cnt[w] = c;
+  }
+}
+
+// one wave per image: lane i adds chunks i, i + 64, ... in that order, then the lanes (butterfly)
+__global__ __launch_bounds__(64) void det_loss_large_sum(const double* __restrict__ ws_sum, const int* __restrict__ ws_cnt,
+                                                          int chunks, float inv_num_boxes, float* __restrict__ out) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  double f = 0.0, l = 0.0, g = 0.0;
+  int c = 0;
+  for (int i = lane; i < chunks; i += 64) {
+    const size_t w = (size_t)b * chunks + i;
+    f += ws_sum[w * 3 + 0];
+    l += ws_sum[w * 3 + 1];
+    g += ws_sum[w * 3 + 2];
+    c += ws_cnt[w];
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    f += __shfl_xor(f, o);
+    l += __shfl_xor(l, o);
+    g += __shfl_xor(g, o);
+    c += __shfl_xor(c, o);
+  }
+  if (lane == 0) {
+    out[b * 4 + 0] = (float)(f * inv_num_boxes);
+    out[b * 4 + 1] = (float)(l * inv_num_boxes);
+    out[b * 4 + 2] = (float)(g * inv_num_boxes);
+    out[b * 4 + 3] = (float)c;
+  }
+}
+
+inline bool det_large_served(int batch, int num_query, int num_classes) {
+  return batch >= 1 && batch <= kDetLargeMaxB && num_query >= 1 && num_query <= kDetLargeMaxN && num_classes >= 1 &&
+         (long long)num_query * num_classes < (1LL << 31);
+}
+
 }  // namespace
+
+extern "C" long long egtr_detection_loss_large_workspace_bytes(int batch, int num_query, int num_classes) {
+  if (!det_large_served(batch, num_query, num_classes)) return 0;
+  const long long chunks = (num_query + kDetLargeRows - 1) / kDetLargeRows;
+  return (long long)batch * chunks * (3 * (long long)sizeof(double) + (long long)sizeof(int));
+}
+
+extern "C" int egtr_detection_loss_large_f32(egtr_stream_t stream, const float* logits, const float* pred_boxes,
+                                             const int64_t* pred_idx, const int64_t* tgt_idx, const int* match_offsets,
+                                             const int64_t* target_labels, const float* target_boxes,
+                                             const int* target_offsets, int batch, int num_query, int num_classes,
+                                             float focal_alpha, float num_boxes, float* grad_logits,
+                                             float* grad_boxes_l1, float* grad_boxes_giou, float* out, void* workspace) {
+  if (!logits || !pred_boxes || !pred_idx || !tgt_idx || !match_offsets || !target_boxes || !target_offsets || !out ||
+      !workspace)
+    return EGTR_E_ARG;
+  const int n_grad = (grad_logits ? 1 : 0) + (grad_boxes_l1 ? 1 : 0) + (grad_boxes_giou ? 1 : 0);
+  if (n_grad != 0 && n_grad != 3) return EGTR_E_ARG;
+  if (batch <= 0 || num_query <= 0 || num_classes <= 0 || !(num_boxes > 0.f)) return EGTR_E_ARG;
+  if (!det_large_served(batch, num_query, num_classes)) return EGTR_E_UNSUPPORTED;
+  const int chunks = (num_query + kDetLargeRows - 1) / kDetLargeRows;
+  double* ws_sum = static_cast<double*>(workspace);
+  int* ws_cnt = reinterpret_cast<int*>(ws_sum + (size_t)batch * chunks * 3);
+  const dim3 grid(chunks, batch);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const long long* pi = reinterpret_cast<const long long*>(pred_idx);
+  const long long* ti = reinterpret_cast<const long long*>(tgt_idx);
+  const long long* tl = reinterpret_cast<const long long*>(target_labels);
+  if (n_grad)
+    hipLaunchKernelGGL(det_loss_large_f32<true>, grid, dim3(kDLT), 0, s, logits, pred_boxes, pi, ti, match_offsets, tl,
+                       target_boxes, target_offsets, num_query, num_classes, focal_alpha, 1.0f / num_boxes, grad_logits,
+                       grad_boxes_l1, grad_boxes_giou, ws_sum, ws_cnt);
+  else
+    hipLaunchKernelGGL(det_loss_large_f32<false>, grid, dim3(kDLT), 0, s, logits, pred_boxes, pi, ti, match_offsets, tl,
+                       target_boxes, target_offsets, num_query, num_classes, focal_alpha, 1.0f / num_boxes, grad_logits,
+                       grad_boxes_l1, grad_boxes_giou, ws_sum, ws_cnt);
+  int st = egtr_check_launch();
+  if (st != 0) return st;
+  hipLaunchKernelGGL(det_loss_large_sum, dim3(batch), dim3(64), 0, s, ws_sum, ws_cnt, chunks, 1.0f / num_boxes, out);
+  return egtr_check_launch();
+}
 
 extern "C" int egtr_detection_loss_f32(egtr_stream_t stream, const float* logits, const float* pred_boxes,
                                        const int64_t* pred_idx, const int64_t* tgt_idx, const int* match_offsets,

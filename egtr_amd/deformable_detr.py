@@ -1784,8 +1784,9 @@ def _detection_heads(config, class_embed, bbox_embed, hidden_states, init_refere
 class DeformableDetrLoss(nn.Module):
     """Criterion of DeformableDetrForObjectDetection (dd:2650-2861): Hungarian assignment, sigmoid focal classification
     loss, L1 + generalised-IoU box losses, the cardinality error; repeated per auxiliary output set.  On GPU tensors the
-    three losses of an output set are ONE HIP launch with their gradients (``ops.detection_losses``, csrc/loss.hip) and the
-    assignment runs on the device (csrc/matcher.hip); CPU tensors take the reference's composition."""
+    three losses of an output set are ONE HIP launch with their gradients (``ops.detection_losses``, csrc/loss.hip; beyond 2048
+    queries -- the two-stage variant's per-token proposal set -- ``ops.detection_losses_large``) and the assignment runs on the
+    device (csrc/matcher.hip); CPU tensors take the reference's composition."""
 
     def __init__(self, matcher, num_classes, eos_coef, losses, focal_alpha=0.25):
         super().__init__()
@@ -1794,8 +1795,9 @@ class DeformableDetrLoss(nn.Module):
         self.losses = losses
         self.focal_alpha = focal_alpha
 
-    # ---- the three terms on ANY device (output sets the fused launch does not take: CPU tensors, the two-stage variant's
-    # per-token proposal set), written over the list of matched (image, query, target) triples.  Same values as dd:2683-2800.
+    # ---- the three terms on ANY device (output sets the fused launches do not take: CPU tensors, 16-bit logits, host-matched
+    # indices, more than 65 536 queries), written over the list of matched (image, query, target) triples.  Same values as
+    # dd:2683-2800.
     @staticmethod
     def _matched_pairs(targets, indices, device):
         """(image index, query index, target class, target box) of every assignment, images concatenated."""
@@ -1842,14 +1844,28 @@ class DeformableDetrLoss(nn.Module):
             raise ValueError(f"Loss {loss} not supported")
         return loss_map[loss](outputs, targets, indices, num_boxes)
 
-    def _set_losses(self, out, targets, num_boxes, suffix, packed):
+    def _set_losses(self, out, targets, num_boxes, suffix, packed, real_targets=None):
+        """The terms of one output set.  ``packed``: a one-element list holding the step's packed targets once some set
+        needed them.  ``real_targets``: given for the class-agnostic proposal set -- ``targets`` are then the zero-label
+        copies the matcher reads, and a set the large entry serves reads the step's own packed targets class-agnostically
+        instead of packing the copies."""
         indices, _ = self.matcher(out, targets)
         lg = out["logits"]
-        fused = (all(k in self.losses for k in ("labels", "cardinality", "boxes"))
-                 and getattr(indices, "flat", None) is not None and lg.is_cuda and lg.dtype == torch.float32
-                 and out["pred_boxes"].dtype == torch.float32 and lg.shape[1] <= 2048)
+        one_launch = (all(k in self.losses for k in ("labels", "cardinality", "boxes"))
+                      and getattr(indices, "flat", None) is not None and lg.is_cuda and lg.dtype == torch.float32
+                      and out["pred_boxes"].dtype == torch.float32)
+        large = one_launch and lg.shape[1] > 2048 and ops.detection_loss_large_route(lg.shape[1])
+        fused = one_launch and (large or lg.shape[1] <= 2048)
         losses = {}
-        if fused:
+        if large:
+            if packed[0] is None:
+                packed[0] = ops.pack_detection_targets(real_targets if real_targets is not None else targets, lg.device)
+            d = ops.detection_losses_large(lg, out["pred_boxes"], indices.flat, packed[0], self.focal_alpha, num_boxes,
+                                           class_agnostic=real_targets is not None)
+            losses.update({k + suffix: v for k, v in d.items()})
+        elif fused:
+            if real_targets is not None:     # the one-workgroup entry reads labels: the zero-label copies, packed apart
+                packed = [None]
             if packed[0] is None:
                 packed[0] = ops.pack_detection_targets(targets, lg.device)
             d = ops.detection_losses(lg, out["pred_boxes"], indices.flat, packed[0], self.focal_alpha, num_boxes)
@@ -1873,7 +1889,7 @@ class DeformableDetrLoss(nn.Module):
                 losses.update(self._set_losses(auxiliary_outputs, targets, num_boxes, f"_{i}", packed))
         if "enc_outputs" in outputs:   # two-stage proposals: class-agnostic targets (dd:2847-2858)
             bin_targets = [dict(t, class_labels=torch.zeros_like(t["class_labels"])) for t in targets]
-            losses.update(self._set_losses(outputs["enc_outputs"], bin_targets, num_boxes, "_enc", [None]))
+            losses.update(self._set_losses(outputs["enc_outputs"], bin_targets, num_boxes, "_enc", packed, targets))
         return losses
 
 

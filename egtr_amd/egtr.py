@@ -804,11 +804,16 @@ class SceneGraphGenerationLoss(nn.Module):
         fused = ("labels", "cardinality", "boxes")
         packed = None
 
-        def fused_ok(out, idx):
+        def fused_ok(out, idx, max_queries=2048):
             lg = out.get("logits")
             return (all(k in self.losses for k in fused) and getattr(idx, "flat", None) is not None and lg is not None
                     and lg.is_cuda and lg.dtype == torch.float32 and out["pred_boxes"].dtype == torch.float32
-                    and lg.shape[1] <= 2048)
+                    and lg.shape[1] <= max_queries)
+
+        def large_ok(out, idx):
+            lg = out.get("logits")
+            return (lg is not None and ops.detection_loss_large_route(lg.shape[1])
+                    and fused_ok(out, idx, ops.DETECTION_LOSS_LARGE_MAX_QUERIES))
 
         def detection(out, idx):
             nonlocal packed
@@ -849,8 +854,16 @@ class SceneGraphGenerationLoss(nn.Module):
             bin_targets = [dict(t, class_labels=torch.zeros_like(t["class_labels"])) for t in targets]
             indices, matching_costs = self.matcher(enc_outputs, bin_targets)
             enc = {}
+            # the proposal set (one per encoder token) through the large entry, class-agnostic on the step's packed targets
+            enc_fused = large_ok(enc_outputs, indices)
+            if enc_fused:
+                if packed is None:
+                    packed = ops.pack_detection_targets(targets, enc_outputs["logits"].device)
+                l_dict = ops.detection_losses_large(enc_outputs["logits"], enc_outputs["pred_boxes"], indices.flat, packed,
+                                                    self.focal_alpha, num_boxes, class_agnostic=True)
+                enc.update({k + "_enc": v for k, v in l_dict.items()})
             for loss in self.losses:
-                if loss in ["masks", "relations", "uncertainty"]:
+                if loss in ["masks", "relations", "uncertainty"] or (enc_fused and loss in fused):
                     continue
                 l_dict = self.get_loss(loss, enc_outputs, bin_targets, indices, matching_costs, num_boxes)
                 enc.update({k + "_enc": v for k, v in l_dict.items()})

@@ -1,8 +1,9 @@
 """Bindings of the relation-head forward kernels and their weight packers (csrc/rel_head*.hip), the device matcher
 (csrc/matcher.hip), the target packing of the loss kernels and the relation loss on dense / bit-packed targets (csrc/loss.hip,
 csrc/rel_targets.hip).  No routing decisions here -- ``egtr_amd.ops`` decides and
-re-exports every name below -- but one: which of the matcher's two entries serves a shape (``hungarian_match_route``, the
-limits of csrc/matcher.hip; ``hungarian_match`` and ``DeformableDetrHungarianMatcher.prepare`` both ask it)."""
+re-exports every name below -- but the entries' own size limits: which of the matcher's two entries serves a shape
+(``hungarian_match_route``, the limits of csrc/matcher.hip; ``hungarian_match`` and ``DeformableDetrHungarianMatcher.prepare``
+both ask it) and whether the large detection-loss entry serves a query count (``detection_loss_large_route``)."""
 import torch
 
 from .. import _lib
@@ -12,7 +13,8 @@ from .linear import _split3_bf16
 __all__ = ["rel_head_split_weights", "rel_head_streams", "relation_head_split_bf16", "relation_head_train_forward",
            "REL_HEAD_MAX_REL", "REL_HEAD_NARROW_MAX_REL", "rel_head_streams_wide", "relation_head_split_bf16_wide", "hungarian_match",
            "hungarian_match_route", "HUNGARIAN_MAX_SIDE", "HUNGARIAN_LARGE_MAX_TARGETS", "HUNGARIAN_LARGE_MAX_QUERIES",
-           "pack_detection_targets", "pack_relation_bits", "pack_relation_bits_wide", "relation_loss_launch",
+           "pack_detection_targets", "detection_loss_large_launch", "detection_loss_large_route", "DETECTION_LOSS_LARGE_ROWS",
+           "DETECTION_LOSS_LARGE_MAX_QUERIES", "pack_relation_bits", "pack_relation_bits_wide", "relation_loss_launch",
            "relation_loss_all_launch", "relation_loss_policy_launch", "RELATION_POLICIES"]
 
 
@@ -309,6 +311,41 @@ def pack_detection_targets(targets, device):
     toff = torch.tensor(offs, dtype=torch.int32).to(device, non_blocking=True)
     lengths = torch.tensor(sizes, dtype=torch.float32).to(device, non_blocking=True)
     return labels, boxes, toff, lengths
+
+
+DETECTION_LOSS_LARGE_ROWS = 32             # loss.hip: kDetLargeRows, the query rows one workgroup owns
+DETECTION_LOSS_LARGE_MAX_QUERIES = 65536   # loss.hip: kDetLargeMaxN (= HUNGARIAN_LARGE_MAX_QUERIES)
+
+
+def detection_loss_large_route(num_query):
+    """Whether an output set of ``num_query`` queries may take egtr_detection_loss_large_f32 (the entry's own bound; the
+    criteria ask it at call time, so an A/B run can take the decision away)."""
+    return 1 <= num_query <= DETECTION_LOSS_LARGE_MAX_QUERIES
+
+
+def detection_loss_large_launch(logits, pred_boxes, pred_idx, tgt_idx, match_off, tgt_labels, tgt_boxes, tgt_off,
+                                focal_alpha, num_boxes, want_grad=True):
+    """egtr_detection_loss_large_f32 on an output set of up to 65 536 queries.  ``tgt_labels`` None: class-agnostic targets
+    (every matched query's class is 0).  Returns (out [B, 4], grad_logits, grad_boxes_l1, grad_boxes_giou); with
+    ``want_grad=False`` the value-only launch, the three gradients None and never allocated."""
+    B, N, C = logits.shape
+    lg = _chk(logits, "logits", torch.float32)
+    bx = _chk(pred_boxes, "pred_boxes", torch.float32)
+    n_ws = _lib.lib().egtr_detection_loss_large_workspace_bytes(B, N, C)
+    if n_ws <= 0:
+        raise _lib.EgtrHipError(f"egtr_detection_loss_large_f32 serves 1 <= N <= {DETECTION_LOSS_LARGE_MAX_QUERIES}, "
+                                f"C >= 1, N * C < 2^31; got B = {B}, N = {N}, C = {C}")
+    dev = lg.device
+    workspace = torch.empty((n_ws + 7) // 8, dtype=torch.float64, device=dev)
+    out = torch.empty(B, 4, dtype=torch.float32, device=dev)
+    d_logits = torch.empty_like(lg) if want_grad else None
+    d_l1 = torch.empty_like(bx) if want_grad else None
+    d_giou = torch.empty_like(bx) if want_grad else None
+    _lib.launch("egtr_detection_loss_large_f32", lg.data_ptr(), bx.data_ptr(), pred_idx.data_ptr(), tgt_idx.data_ptr(),
+                match_off.data_ptr(), _lib.ptr(tgt_labels), tgt_boxes.data_ptr(), tgt_off.data_ptr(), B, N, C,
+                float(focal_alpha), float(num_boxes), _lib.ptr(d_logits), _lib.ptr(d_l1), _lib.ptr(d_giou), out.data_ptr(),
+                workspace.data_ptr())
+    return out, d_logits, d_l1, d_giou
 
 
 def pack_relation_bits(triplets, offsets, batch, total, num_query, num_rel):

@@ -1787,6 +1787,59 @@ def detection_losses(logits, pred_boxes, flat_match, packed_targets, focal_alpha
             "cardinality_error": (card - lengths).abs().mean()}
 
 
+class DetectionLossLargeFunction(Function):
+    """``DetectionLossFunction`` for proposal-sized output sets (csrc/loss.hip, egtr_detection_loss_large_f32: up to 65 536
+    queries).  ``tgt_labels`` None: class-agnostic targets."""
+
+    @staticmethod
+    def forward(ctx, logits, boxes, pred_idx, tgt_idx, match_off, tgt_labels, tgt_boxes, tgt_off, focal_alpha,
+                num_boxes):
+        out, d_logits, d_l1, d_giou = detection_loss_large_launch(
+            logits.detach().contiguous(), boxes.detach().contiguous(), pred_idx, tgt_idx, match_off, tgt_labels, tgt_boxes,
+            tgt_off, focal_alpha, num_boxes, want_grad=True)
+        ctx.save_for_backward(d_logits, d_l1, d_giou)
+        sums = out.sum(0)
+        card = out[:, 3]
+        ctx.mark_non_differentiable(card)
+        return sums[0], sums[1], sums[2], card
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_ce, g_bbox, g_giou, g_card):
+        d_logits, d_l1, d_giou = ctx.saved_tensors
+        return (d_logits * g_ce, d_l1 * g_bbox + d_giou * g_giou, None, None, None, None, None, None, None, None)
+
+
+def detection_losses_large(logits, pred_boxes, flat_match, packed_targets, focal_alpha, num_boxes, class_agnostic=False):
+    """``detection_losses`` for an output set of up to 65 536 queries (the two-stage variant's per-token proposals): the
+    same four terms from egtr_detection_loss_large_f32.  ``class_agnostic``: every target's class is 0, whatever labels
+    ``packed_targets`` holds (the ``*_enc`` terms score the proposals against class-agnostic copies of the step's targets,
+    so the step's own packed targets serve).  When no gradient can be asked for (grad mode off, or neither input requires
+    one) the value-only launch runs and no gradient buffer is allocated."""
+    pred_idx, tgt_idx, n_out = flat_match
+    labels, boxes, toff, lengths = packed_targets
+    offs = [0]
+    for n in n_out:
+        offs.append(offs[-1] + int(n))
+    moff = torch.tensor(offs, dtype=torch.int32).to(logits.device, non_blocking=True)
+    if pred_idx.numel() == 0:
+        pred_idx = torch.zeros(1, dtype=torch.int64, device=logits.device)
+        tgt_idx = torch.zeros(1, dtype=torch.int64, device=logits.device)
+    if class_agnostic:
+        labels = None
+    if torch.is_grad_enabled() and (logits.requires_grad or pred_boxes.requires_grad):
+        ce, bbox, giou, card = DetectionLossLargeFunction.apply(logits, pred_boxes, pred_idx, tgt_idx, moff, labels, boxes,
+                                                                toff, focal_alpha, num_boxes)
+    else:
+        out, _, _, _ = detection_loss_large_launch(logits.detach().contiguous(), pred_boxes.detach().contiguous(), pred_idx,
+                                                   tgt_idx, moff, labels, boxes, toff, focal_alpha, num_boxes,
+                                                   want_grad=False)
+        sums = out.sum(0)
+        ce, bbox, giou, card = sums[0], sums[1], sums[2], out[:, 3]
+    return {"loss_ce": ce, "loss_bbox": bbox, "loss_giou": giou,
+            "cardinality_error": (card - lengths).abs().mean()}
+
+
 def _relation_operands(pred_rel, targets, indices, matching_costs, rel_bits):
     """What the relation-loss entries read besides the logits: (target, packed, rels, pred_idx, tgt_idx, match_cost, out_off).
     ``target``: the pointer table of the dense targets (``rels`` keeps their contiguous forms alive until the launches are

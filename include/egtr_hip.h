@@ -1277,6 +1277,25 @@ int egtr_detection_loss_f32(egtr_stream_t stream, const float* logits, const flo
                             int num_classes, float focal_alpha, float num_boxes, float* grad_logits,
                             float* grad_boxes_l1, float* grad_boxes_giou, float* out);
 
+/* The same losses, same values and semantics, for proposal-sized output sets (the two-stage variant scores every encoder
+ * token: 12 537 proposals per image at 600 x 1000): 1 <= num_query <= 65 536 (the bound of
+ * egtr_hungarian_match_large_f32), num_classes >= 1, num_query * num_classes < 2^31, batch <= 65 535, any number of
+ * matches per image; anything else is EGTR_E_UNSUPPORTED before any launch, nothing written.  The arguments of
+ * egtr_detection_loss_f32, then workspace: egtr_detection_loss_large_workspace_bytes(batch, num_query, num_classes)
+ * bytes, 8-byte aligned (the query returns 0 for a shape that is not served).  target_labels may be NULL: class-agnostic
+ * targets, every matched query's class is 0.  grad_logits, grad_boxes_l1 and grad_boxes_giou may ALL be NULL: values
+ * only, nothing but out (and the workspace) is written; some but not all NULL is EGTR_E_ARG.  A match entry whose query
+ * or target index is out of range (the -1 of an image the matcher refused) is skipped, never dereferenced; the box
+ * gradient rows of unmatched queries are written as zeros.  Two launches (a workgroup per 32 query rows of an image, then
+ * the per-image sums), no atomics, sums in a fixed order: bit-reproducible. */
+long long egtr_detection_loss_large_workspace_bytes(int batch, int num_query, int num_classes);
+int egtr_detection_loss_large_f32(egtr_stream_t stream, const float* logits, const float* pred_boxes,
+                                  const int64_t* pred_idx, const int64_t* tgt_idx, const int* match_offsets,
+                                  const int64_t* target_labels, const float* target_boxes, const int* target_offsets,
+                                  int batch, int num_query, int num_classes, float focal_alpha, float num_boxes,
+                                  float* grad_logits, float* grad_boxes_l1, float* grad_boxes_giou, float* out,
+                                  void* workspace);
+
 /* "Clamp the encoder states iff any element is inf / nan" (model/deformable_detr.py:1346-1351) without the reference's
  * host branch: egtr_any_nonfinite_f32 raises *flag (int, zero before the call) if x [n] holds a non-finite value;
  * egtr_clamp_if_flag_f32 then clamps t [n] to +-clamp_value in place (mask_gradient = 0; NaN stays NaN), or zeroes the
