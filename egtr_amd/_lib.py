@@ -16,7 +16,7 @@ LIB_PATH = os.environ.get("EGTR_HIP_LIBRARY") or os.path.join(_HERE, "libegtr_hi
 
 _P = ctypes.c_void_p
 _I = ctypes.c_int
-ABI_VERSION = 6   # include/egtr_hip.h: EGTR_ABI_VERSION of the header these signatures were written against
+ABI_VERSION = 7   # include/egtr_hip.h: EGTR_ABI_VERSION of the header these signatures were written against
 
 # name -> argtypes (restype is always int status unless listed in _RESTYPES)
 SIGNATURES = {
@@ -119,28 +119,14 @@ SIGNATURES = {
     "egtr_detection_loss_large_workspace_bytes": [_I, _I, _I],
     "egtr_detection_loss_large_f32": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, ctypes.c_float, ctypes.c_float, _P,
                                       _P, _P, _P, _P],
-    "egtr_relation_loss_f32": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, ctypes.c_float, _I, _I, _P, _P, _P, _P],
+    # target, target_format after the logits; the sampled entry ends in policy_neg, policy_nm, seed, rng_stream, deterministic
     "egtr_relation_loss_workspace_bytes": [_I, _I],
-    "egtr_relation_loss_bits_f32": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, ctypes.c_float, _I, _I, _P, _P, _P, _P],
-    "egtr_relation_loss_det_workspace_bytes": [_I, _I],
-    "egtr_relation_loss_det_f32": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, ctypes.c_float, _I, _I, _P, _P, _P, _P],
-    "egtr_relation_loss_det_bits_f32": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, ctypes.c_float, _I, _I, _P, _P, _P, _P],
+    "egtr_relation_loss_f32": [_P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, ctypes.c_float, _I, _I, _P, _P, _P, _P,
+                               _I, _I, ctypes.c_longlong, ctypes.c_longlong, _I],
     "egtr_relation_loss_all_workspace_bytes": [_I, _I],
-    "egtr_relation_loss_all_f32": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, ctypes.c_float, _P, _P, _P, _P],
-    "egtr_relation_loss_all_bits_f32": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, ctypes.c_float, _P, _P, _P, _P],
+    "egtr_relation_loss_all_f32": [_P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, ctypes.c_float, _P, _P, _P, _P],
     "egtr_pack_relations_u64": [_P, _P, _P, _I, _I, _I, _I, _P],
     "egtr_pack_relations_wide_u64": [_P, _P, _P, _I, _I, _I, _I, _P],
-    "egtr_relation_loss_wide_bits_f32": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, ctypes.c_float, _I, _I, _P, _P, _P, _P],
-    "egtr_relation_loss_det_wide_bits_f32": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, ctypes.c_float, _I, _I, _P, _P, _P,
-                                             _P],
-    "egtr_relation_loss_all_wide_bits_f32": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, ctypes.c_float, _P, _P, _P, _P],
-    # the policy entries: the sibling's arguments + policy_neg, policy_nm, seed, rng_stream, deterministic
-    "egtr_relation_loss_policy_f32": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, ctypes.c_float, _I, _I, _P, _P, _P, _P,
-                                      _I, _I, ctypes.c_longlong, ctypes.c_longlong, _I],
-    "egtr_relation_loss_policy_bits_f32": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, ctypes.c_float, _I, _I, _P, _P, _P, _P,
-                                           _I, _I, ctypes.c_longlong, ctypes.c_longlong, _I],
-    "egtr_relation_loss_policy_wide_bits_f32": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, ctypes.c_float, _I, _I, _P, _P, _P,
-                                                _P, _I, _I, ctypes.c_longlong, ctypes.c_longlong, _I],
     "egtr_rel_head_forward_bf16w": [_P] * 16 + [_I] * 6 + [_P] * 3,
     "egtr_ffn_layernorm_bf16": [_P] * 7 + [ctypes.c_float, _P, _I, _P, _P, _I, _I, _I],
     "egtr_ffn_pack_weights_bf16": [_P, _P, _P, _I, _I, _P],
@@ -202,7 +188,6 @@ _RESTYPES = {"egtr_status_string": ctypes.c_char_p, "egtr_last_hip_error": ctype
              "egtr_msda_backward_bf16_workspace_floats": ctypes.c_longlong,
              "egtr_msda_backward_det_workspace_bytes": ctypes.c_longlong,
              "egtr_detection_loss_large_workspace_bytes": ctypes.c_longlong,
-             "egtr_relation_loss_det_workspace_bytes": ctypes.c_longlong,
              "egtr_relation_loss_all_workspace_bytes": ctypes.c_longlong,
              "egtr_hungarian_match_scratch_doubles": ctypes.c_longlong,
              "egtr_hungarian_match_large_workspace_bytes": ctypes.c_longlong,

@@ -14,10 +14,10 @@
 // is reached (ties have equal logits; which of them the reference's topk returns is unspecified too).
 // Launches: prep | 3 x (histogram, find) | final (loss terms, dense d loss / d pred_rel, pair flags) | connectivity.
 // All counts stay on the device; the only inputs from the host are tensor shapes.
-// The passes that read the target are templates on a target accessor: dense fp32 [N, N, R] per image (the reference's format,
-// egtr_relation_loss_f32), one 64-bit word per (subject, object) pair (egtr_relation_loss_bits_f32) or, for 65 to
-// 256 predicates, ceil(R / 64) words per pair (egtr_relation_loss_wide_bits_f32).
-// Evaluation mode (and training with both sample counts None) selects nothing: BCE over all elements, egtr_relation_loss_all_*:
+// The passes that read the target are templates on a target accessor, the entry's target_format: dense fp32 [N, N, R] per image
+// (the reference's format), one 64-bit word per (subject, object) pair or, for 65 to 256 predicates,
+// ceil(R / 64) words per pair.
+// Evaluation mode (and training with both sample counts None) selects nothing: BCE over all elements, egtr_relation_loss_all_f32:
 // maps | all-elements pass | connectivity | finalize.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -44,9 +44,9 @@ struct ImgState {
   int need[2];      // elements equal to thr to take
   int ticket[2];    // tickets handed out to elements equal to thr
   int n_sel;        // n_true + k[0] + k[1]
-  int pad[4];       // policy entries: the random key words (ka, kb) of problem 0, then of problem 1; zero otherwise
+  int pad[4];       // POL kernels: the random key words (ka, kb) of problem 0, then of problem 1; zero otherwise
 };
-// sampling policy of a class (egtr_relation_loss_policy_*): the k largest logits | a uniform k-subset | the whole class
+// sampling policy of a class (policy_neg / policy_nm of egtr_relation_loss_f32): the k largest logits | a uniform k-subset | the whole class
 constexpr int kPolLargest = 0, kPolRandom = 1, kPolAll = 2;
 static_assert(sizeof(ImgState) == 80, "layout");
 
@@ -196,7 +196,7 @@ __device__ __forceinline__ int rel_prep_maps(const int64_t* __restrict__ pred_id
   return T;
 }
 
-// POL (the policy entries): pol0 / pol1 = the policy of the block's false candidates / of the elements outside the block.  A
+// POL (a policy other than `largest`): pol0 / pol1 = the policy of the block's false candidates / of the elements outside the block.  A
 // class taken whole has k = its size whatever n_true is (the reference skips its sampling block, egtr:848, 878) and nothing to
 // select (krem = 0: the histogram / find passes skip it); a random class gets its key words from (seed, stream, image, class).
 template <class Tgt, bool POL = false>
@@ -735,7 +735,7 @@ __global__ __launch_bounds__(kLT) void conn_loss(const float* __restrict__ pred_
 
 }  // namespace
 
-extern "C" long long egtr_relation_loss_workspace_bytes(int batch, int num_query) {
+static long long rel_loss_layout_bytes(int batch, int num_query) {
   if (batch <= 0 || num_query <= 0) return 0;
   const long long B = batch, N = num_query;
   const long long rows = (N + kRowsPerWg - 1) / kRowsPerWg;
@@ -749,18 +749,18 @@ extern "C" long long egtr_relation_loss_workspace_bytes(int batch, int num_query
   return bytes + 256;
 }
 
-// deterministic route: the same layout, followed by the tie counts int32 [batch, N, 2]
-extern "C" long long egtr_relation_loss_det_workspace_bytes(int batch, int num_query) {
-  const long long base = egtr_relation_loss_workspace_bytes(batch, num_query);
+// the layout, followed by the tie counts int32 [batch, N, 2] of the deterministic tie rule
+extern "C" long long egtr_relation_loss_workspace_bytes(int batch, int num_query) {
+  const long long base = rel_loss_layout_bytes(batch, num_query);
   if (base <= 0) return 0;
   return ((base + 15) / 16) * 16 + (long long)batch * num_query * 2 * 4;
 }
 
-// The launches of both entries.  pred_idx / tgt_idx / match_cost / out_offsets: the matcher's packed outputs
+// The launches of the sampled entry.  pred_idx / tgt_idx / match_cost / out_offsets: the matcher's packed outputs
 // (egtr_hungarian_match_f32).  workspace: device, egtr_relation_loss_workspace_bytes() bytes, contents irrelevant (zeroed
 // here).  loss_out[0] = loss_rel, loss_out[1] = loss_connectivity; grad_rel [B,N,N,R] / grad_conn [B,N,N] = d loss / d logits.
-// POL: the policy entries (pol_neg / pol_nm per class, seed / stream of the random keys); without it the launches, arguments
-// and code paths of the entries above are what they were.
+// POL: a policy other than `largest` in either class (pol_neg / pol_nm per class, seed / stream of the random keys); without
+// it the kernels carry no policy code.
 template <class Tgt, bool POL = false>
 static int relation_loss_launch(egtr_stream_t stream, const float* pred_rel, const float* pred_conn, const Tgt target_rel,
                                 const int64_t* pred_idx, const int64_t* tgt_idx, const float* match_cost,
@@ -787,8 +787,8 @@ static int relation_loss_launch(egtr_stream_t stream, const float* pred_rel, con
   hipStream_t st = static_cast<hipStream_t>(stream);
   const long long B = batch, N = num_query;
   const int rows = (int)((N + kRowsPerWg - 1) / kRowsPerWg);
-  const long long wsb = egtr_relation_loss_workspace_bytes(batch, num_query);
-  const long long wsb_all = det ? egtr_relation_loss_det_workspace_bytes(batch, num_query) : wsb;
+  const long long wsb = rel_loss_layout_bytes(batch, num_query);
+  const long long wsb_all = det ? egtr_relation_loss_workspace_bytes(batch, num_query) : wsb;   // the tie counts: det only
   if (hipMemsetAsync(workspace, 0, (size_t)wsb_all, st) != hipSuccess) return EGTR_E_LAUNCH;
   int* tiecnt = reinterpret_cast<int*>(static_cast<char*>(workspace) + ((wsb + 15) / 16) * 16);   // det only
   char* p = static_cast<char*>(workspace);
@@ -843,64 +843,54 @@ static int relation_loss_launch(egtr_stream_t stream, const float* pred_rel, con
   return egtr_check_launch();
 }
 
-// target_rel: DEVICE array of `batch` device pointers (image b's dense [N, N, R] target).
-extern "C" int egtr_relation_loss_f32(egtr_stream_t stream, const float* pred_rel, const float* pred_conn,
-                                      const float* const* target_rel, const int64_t* pred_idx, const int64_t* tgt_idx,
-                                      const float* match_cost, const int* out_offsets, int batch, int num_query,
-                                      int num_rel, float nonmatching_cost, int sample_negatives, int sample_nonmatching,
-                                      float* loss_out, float* grad_rel, float* grad_conn, void* workspace) {
-  if (!target_rel) return EGTR_E_ARG;
-  return relation_loss_launch(stream, pred_rel, pred_conn, DenseTarget{target_rel}, pred_idx, tgt_idx, match_cost,
-                              out_offsets, batch, num_query, num_rel, nonmatching_cost, sample_negatives,
-                              sample_nonmatching, loss_out, grad_rel, grad_conn, workspace);
+// ---- the target form of both C entries ----------------------------------------------------------------------------------------
+// (target, target_format, num_rel) -> f(the accessor of that form).  The three accessors run the same kernel templates -- the same
+// passes, order and arithmetic -- so on the dense form of the same target every format returns the same bits; the packed forms
+// load one 8-byte word per (subject, object) pair where the dense accessor gathers one float per logit.
+namespace {
+constexpr int kWideMaxRel = 256;
+inline bool bad_policy(int p) { return p != kPolLargest && p != kPolRandom && p != kPolAll; }
+
+template <class F>
+int with_target(const void* target, int target_format, int num_rel, F&& f) {
+  if (!target) return EGTR_E_ARG;
+  const auto* words = static_cast<const unsigned long long*>(target);
+  switch (target_format) {
+    case EGTR_REL_TARGET_DENSE: return f(DenseTarget{static_cast<const float* const*>(target)});
+    case EGTR_REL_TARGET_WORDS: return num_rel > 64 ? EGTR_E_UNSUPPORTED : f(PackedTarget{words});
+    case EGTR_REL_TARGET_WIDE: return num_rel > kWideMaxRel ? EGTR_E_UNSUPPORTED : f(PackedTargetWide{words});
+    default: return EGTR_E_ARG;
+  }
+}
+}  // namespace
+
+// One sampling policy per class: policy_neg / policy_nm 0: the `count n_true` largest logits, 1: a uniform
+// random subset of that size, 2: the whole class -- its count is ignored; seed / rng_stream: the words of the random keys
+// (rel_sample_key.h).  (largest, largest) -- what the criterion trains with -- runs the kernels without the policy code.
+// deterministic: among the candidates equal to the threshold key of an (image, problem) of a `largest` class the `need` ones with
+// the lowest flat index (qa N + qb) R + r are taken (query order), one extra pass over pred_rel.
+extern "C" int egtr_relation_loss_f32(egtr_stream_t stream, const float* pred_rel, const float* pred_conn, const void* target,
+                                      int target_format, const int64_t* pred_idx, const int64_t* tgt_idx,
+                                      const float* match_cost, const int* out_offsets, int batch, int num_query, int num_rel,
+                                      float nonmatching_cost, int sample_negatives, int sample_nonmatching, float* loss_out,
+                                      float* grad_rel, float* grad_conn, void* workspace, int policy_neg, int policy_nm,
+                                      long long seed, long long rng_stream, int deterministic) {
+  if (bad_policy(policy_neg) || bad_policy(policy_nm)) return EGTR_E_ARG;
+  const bool det = deterministic != 0;
+  return with_target(target, target_format, num_rel, [&](auto tgt) {
+    using Tgt = decltype(tgt);
+    if (policy_neg != kPolLargest || policy_nm != kPolLargest)
+      return relation_loss_launch<Tgt, true>(stream, pred_rel, pred_conn, tgt, pred_idx, tgt_idx, match_cost, out_offsets,
+                                             batch, num_query, num_rel, nonmatching_cost, sample_negatives,
+                                             sample_nonmatching, loss_out, grad_rel, grad_conn, workspace, det, policy_neg,
+                                             policy_nm, seed, rng_stream);
+    return relation_loss_launch<Tgt, false>(stream, pred_rel, pred_conn, tgt, pred_idx, tgt_idx, match_cost, out_offsets,
+                                            batch, num_query, num_rel, nonmatching_cost, sample_negatives,
+                                            sample_nonmatching, loss_out, grad_rel, grad_conn, workspace, det);
+  });
 }
 
-// rel_bits: [batch, N, N] 64-bit words (egtr_pack_relations_u64), bit r of word (s, o) = the target of predicate r.  The same
-// passes, order and arithmetic as egtr_relation_loss_f32 on the dense form of the same target -- the results are bit-identical --
-// with one 8-byte load per (subject, object) pair where the dense accessor gathers one float per logit.
-extern "C" int egtr_relation_loss_bits_f32(egtr_stream_t stream, const float* pred_rel, const float* pred_conn,
-                                           const uint64_t* rel_bits, const int64_t* pred_idx, const int64_t* tgt_idx,
-                                           const float* match_cost, const int* out_offsets, int batch, int num_query,
-                                           int num_rel, float nonmatching_cost, int sample_negatives,
-                                           int sample_nonmatching, float* loss_out, float* grad_rel, float* grad_conn,
-                                           void* workspace) {
-  if (!rel_bits) return EGTR_E_ARG;
-  if (num_rel > 64) return EGTR_E_UNSUPPORTED;
-  return relation_loss_launch(stream, pred_rel, pred_conn,
-                              PackedTarget{reinterpret_cast<const unsigned long long*>(rel_bits)}, pred_idx, tgt_idx,
-                              match_cost, out_offsets, batch, num_query, num_rel, nonmatching_cost, sample_negatives,
-                              sample_nonmatching, loss_out, grad_rel, grad_conn, workspace);
-}
-
-// ---- deterministic entries: the same arguments, workspace of egtr_relation_loss_det_workspace_bytes().  Among the candidates
-// equal to the threshold key of an (image, problem) the `need` ones with the lowest flat index (qa N + qb) R + r are taken
-// (query order), one extra pass over pred_rel; everything else is the code of the entries above.
-extern "C" int egtr_relation_loss_det_f32(egtr_stream_t stream, const float* pred_rel, const float* pred_conn,
-                                          const float* const* target_rel, const int64_t* pred_idx, const int64_t* tgt_idx,
-                                          const float* match_cost, const int* out_offsets, int batch, int num_query,
-                                          int num_rel, float nonmatching_cost, int sample_negatives, int sample_nonmatching,
-                                          float* loss_out, float* grad_rel, float* grad_conn, void* workspace) {
-  if (!target_rel) return EGTR_E_ARG;
-  return relation_loss_launch(stream, pred_rel, pred_conn, DenseTarget{target_rel}, pred_idx, tgt_idx, match_cost,
-                              out_offsets, batch, num_query, num_rel, nonmatching_cost, sample_negatives,
-                              sample_nonmatching, loss_out, grad_rel, grad_conn, workspace, true);
-}
-
-extern "C" int egtr_relation_loss_det_bits_f32(egtr_stream_t stream, const float* pred_rel, const float* pred_conn,
-                                               const uint64_t* rel_bits, const int64_t* pred_idx, const int64_t* tgt_idx,
-                                               const float* match_cost, const int* out_offsets, int batch, int num_query,
-                                               int num_rel, float nonmatching_cost, int sample_negatives,
-                                               int sample_nonmatching, float* loss_out, float* grad_rel, float* grad_conn,
-                                               void* workspace) {
-  if (!rel_bits) return EGTR_E_ARG;
-  if (num_rel > 64) return EGTR_E_UNSUPPORTED;
-  return relation_loss_launch(stream, pred_rel, pred_conn,
-                              PackedTarget{reinterpret_cast<const unsigned long long*>(rel_bits)}, pred_idx, tgt_idx,
-                              match_cost, out_offsets, batch, num_query, num_rel, nonmatching_cost, sample_negatives,
-                              sample_nonmatching, loss_out, grad_rel, grad_conn, workspace, true);
-}
-
-// ---- un-sampled entries (evaluation mode / both sample counts None): BCE over every element, see rel_loss_all ------------
+// ---- the un-sampled entry (evaluation mode / both sample counts None): BCE over every element, see rel_loss_all ------------
 // Launches: maps | all-elements pass | connectivity | finalize.  Deterministic by construction (no atomics on values, no tickets).
 // workspace layout: tq, wq [B, N] | mq [B N] | pair flags [B N N] | partial sums: B N of the relations, kAllConnBlocks of the connectivity
 namespace {
@@ -966,133 +956,29 @@ static int relation_loss_all_launch(egtr_stream_t stream, const float* pred_rel,
   return egtr_check_launch();
 }
 
-// The arguments of egtr_relation_loss_f32 without the two sample counts.  grad_rel / grad_conn: both device buffers, or both
-// NULL for the value alone (nothing of their size is written).
+// The instantiations, in the order their kernels have always had in the code object (the order in which the forms arrived), so
+// that the device assembly of two builds can be compared line by line.  A new form or policy template appends its lines.
+template decltype(relation_loss_launch<DenseTarget, false>) relation_loss_launch<DenseTarget, false>;
+template decltype(relation_loss_launch<PackedTarget, false>) relation_loss_launch<PackedTarget, false>;
+template decltype(relation_loss_all_launch<DenseTarget>) relation_loss_all_launch<DenseTarget>;
+template decltype(relation_loss_all_launch<PackedTarget>) relation_loss_all_launch<PackedTarget>;
+template decltype(relation_loss_launch<PackedTargetWide, false>) relation_loss_launch<PackedTargetWide, false>;
+template decltype(relation_loss_all_launch<PackedTargetWide>) relation_loss_all_launch<PackedTargetWide>;
+template decltype(relation_loss_launch<DenseTarget, true>) relation_loss_launch<DenseTarget, true>;
+template decltype(relation_loss_launch<PackedTarget, true>) relation_loss_launch<PackedTarget, true>;
+template decltype(relation_loss_launch<PackedTargetWide, true>) relation_loss_launch<PackedTargetWide, true>;
+
+// The arguments of egtr_relation_loss_f32 without the sample counts and policies.  grad_rel / grad_conn: both device buffers, or
+// both NULL for the value alone (nothing of their size is written).
 extern "C" int egtr_relation_loss_all_f32(egtr_stream_t stream, const float* pred_rel, const float* pred_conn,
-                                          const float* const* target_rel, const int64_t* pred_idx, const int64_t* tgt_idx,
-                                          const float* match_cost, const int* out_offsets, int batch, int num_query,
-                                          int num_rel, float nonmatching_cost, float* loss_out, float* grad_rel,
+                                          const void* target, int target_format, const int64_t* pred_idx,
+                                          const int64_t* tgt_idx, const float* match_cost, const int* out_offsets, int batch,
+                                          int num_query, int num_rel, float nonmatching_cost, float* loss_out, float* grad_rel,
                                           float* grad_conn, void* workspace) {
-  if (!target_rel) return EGTR_E_ARG;
-  return relation_loss_all_launch(stream, pred_rel, pred_conn, DenseTarget{target_rel}, pred_idx, tgt_idx, match_cost,
-                                  out_offsets, batch, num_query, num_rel, nonmatching_cost, loss_out, grad_rel, grad_conn,
-                                  workspace);
-}
-
-// packed words: the same passes, order and arithmetic -- the same bits as the dense entry on the dense form of the same target
-extern "C" int egtr_relation_loss_all_bits_f32(egtr_stream_t stream, const float* pred_rel, const float* pred_conn,
-                                               const uint64_t* rel_bits, const int64_t* pred_idx, const int64_t* tgt_idx,
-                                               const float* match_cost, const int* out_offsets, int batch, int num_query,
-                                               int num_rel, float nonmatching_cost, float* loss_out, float* grad_rel,
-                                               float* grad_conn, void* workspace) {
-  if (!rel_bits) return EGTR_E_ARG;
-  if (num_rel > 64) return EGTR_E_UNSUPPORTED;
-  return relation_loss_all_launch(stream, pred_rel, pred_conn,
-                                  PackedTarget{reinterpret_cast<const unsigned long long*>(rel_bits)}, pred_idx, tgt_idx,
-                                  match_cost, out_offsets, batch, num_query, num_rel, nonmatching_cost, loss_out, grad_rel,
-                                  grad_conn, workspace);
-}
-
-// ---- wide packed words: rel_bits [batch, N, N, W], W = ceil(num_rel / 64), num_rel <= 256 (egtr_pack_relations_wide_u64) ------
-// The argument lists and workspaces of the _bits_ entries; the same kernel templates through PackedTargetWide, so each returns the
-// bits of the dense entry on the dense form of the same target.  With W = 1 the memory is that of the [batch, N, N] words.
-namespace {
-constexpr int kWideMaxRel = 256;
-}
-
-extern "C" int egtr_relation_loss_wide_bits_f32(egtr_stream_t stream, const float* pred_rel, const float* pred_conn,
-                                                const uint64_t* rel_bits, const int64_t* pred_idx, const int64_t* tgt_idx,
-                                                const float* match_cost, const int* out_offsets, int batch, int num_query,
-                                                int num_rel, float nonmatching_cost, int sample_negatives,
-                                                int sample_nonmatching, float* loss_out, float* grad_rel, float* grad_conn,
-                                                void* workspace) {
-  if (!rel_bits) return EGTR_E_ARG;
-  if (num_rel > kWideMaxRel) return EGTR_E_UNSUPPORTED;
-  return relation_loss_launch(stream, pred_rel, pred_conn,
-                              PackedTargetWide{reinterpret_cast<const unsigned long long*>(rel_bits)}, pred_idx, tgt_idx,
-                              match_cost, out_offsets, batch, num_query, num_rel, nonmatching_cost, sample_negatives,
-                              sample_nonmatching, loss_out, grad_rel, grad_conn, workspace);
-}
-
-extern "C" int egtr_relation_loss_det_wide_bits_f32(egtr_stream_t stream, const float* pred_rel, const float* pred_conn,
-                                                    const uint64_t* rel_bits, const int64_t* pred_idx, const int64_t* tgt_idx,
-                                                    const float* match_cost, const int* out_offsets, int batch, int num_query,
-                                                    int num_rel, float nonmatching_cost, int sample_negatives,
-                                                    int sample_nonmatching, float* loss_out, float* grad_rel,
-                                                    float* grad_conn, void* workspace) {
-  if (!rel_bits) return EGTR_E_ARG;
-  if (num_rel > kWideMaxRel) return EGTR_E_UNSUPPORTED;
-  return relation_loss_launch(stream, pred_rel, pred_conn,
-                              PackedTargetWide{reinterpret_cast<const unsigned long long*>(rel_bits)}, pred_idx, tgt_idx,
-                              match_cost, out_offsets, batch, num_query, num_rel, nonmatching_cost, sample_negatives,
-                              sample_nonmatching, loss_out, grad_rel, grad_conn, workspace, true);
-}
-
-extern "C" int egtr_relation_loss_all_wide_bits_f32(egtr_stream_t stream, const float* pred_rel, const float* pred_conn,
-                                                    const uint64_t* rel_bits, const int64_t* pred_idx, const int64_t* tgt_idx,
-                                                    const float* match_cost, const int* out_offsets, int batch, int num_query,
-                                                    int num_rel, float nonmatching_cost, float* loss_out, float* grad_rel,
-                                                    float* grad_conn, void* workspace) {
-  if (!rel_bits) return EGTR_E_ARG;
-  if (num_rel > kWideMaxRel) return EGTR_E_UNSUPPORTED;
-  return relation_loss_all_launch(stream, pred_rel, pred_conn,
-                                  PackedTargetWide{reinterpret_cast<const unsigned long long*>(rel_bits)}, pred_idx, tgt_idx,
-                                  match_cost, out_offsets, batch, num_query, num_rel, nonmatching_cost, loss_out, grad_rel,
-                                  grad_conn, workspace);
-}
-
-// ---- policy entries: one sampling policy per class --------------------------------------------------------
-// The arguments of egtr_relation_loss_f32 / _bits_f32 / _wide_bits_f32, then policy_neg / policy_nm (0: the `count n_true`
-// largest logits, 1: a uniform random subset of that size, 2: the whole class -- its count is ignored), the seed and stream of
-// the random keys (rel_sample_key.h) and `deterministic` (the lowest-index tie rule for a `largest` class).  workspace:
-// egtr_relation_loss_det_workspace_bytes() bytes under either tie rule.
-namespace {
-inline bool bad_policy(int p) { return p != kPolLargest && p != kPolRandom && p != kPolAll; }
-}
-
-extern "C" int egtr_relation_loss_policy_f32(egtr_stream_t stream, const float* pred_rel, const float* pred_conn,
-                                             const float* const* target_rel, const int64_t* pred_idx, const int64_t* tgt_idx,
-                                             const float* match_cost, const int* out_offsets, int batch, int num_query,
-                                             int num_rel, float nonmatching_cost, int sample_negatives, int sample_nonmatching,
-                                             float* loss_out, float* grad_rel, float* grad_conn, void* workspace,
-                                             int policy_neg, int policy_nm, long long seed, long long rng_stream,
-                                             int deterministic) {
-  if (!target_rel || bad_policy(policy_neg) || bad_policy(policy_nm)) return EGTR_E_ARG;
-  return relation_loss_launch<DenseTarget, true>(stream, pred_rel, pred_conn, DenseTarget{target_rel}, pred_idx, tgt_idx,
-                                                 match_cost, out_offsets, batch, num_query, num_rel, nonmatching_cost,
-                                                 sample_negatives, sample_nonmatching, loss_out, grad_rel, grad_conn, workspace,
-                                                 deterministic != 0, policy_neg, policy_nm, seed, rng_stream);
-}
-
-extern "C" int egtr_relation_loss_policy_bits_f32(egtr_stream_t stream, const float* pred_rel, const float* pred_conn,
-                                                  const uint64_t* rel_bits, const int64_t* pred_idx, const int64_t* tgt_idx,
-                                                  const float* match_cost, const int* out_offsets, int batch, int num_query,
-                                                  int num_rel, float nonmatching_cost, int sample_negatives,
-                                                  int sample_nonmatching, float* loss_out, float* grad_rel, float* grad_conn,
-                                                  void* workspace, int policy_neg, int policy_nm, long long seed,
-                                                  long long rng_stream, int deterministic) {
-  if (!rel_bits || bad_policy(policy_neg) || bad_policy(policy_nm)) return EGTR_E_ARG;
-  if (num_rel > 64) return EGTR_E_UNSUPPORTED;
-  return relation_loss_launch<PackedTarget, true>(
-      stream, pred_rel, pred_conn, PackedTarget{reinterpret_cast<const unsigned long long*>(rel_bits)}, pred_idx, tgt_idx,
-      match_cost, out_offsets, batch, num_query, num_rel, nonmatching_cost, sample_negatives, sample_nonmatching, loss_out,
-      grad_rel, grad_conn, workspace, deterministic != 0, policy_neg, policy_nm, seed, rng_stream);
-}
-
-extern "C" int egtr_relation_loss_policy_wide_bits_f32(egtr_stream_t stream, const float* pred_rel, const float* pred_conn,
-                                                       const uint64_t* rel_bits, const int64_t* pred_idx,
-                                                       const int64_t* tgt_idx, const float* match_cost, const int* out_offsets,
-                                                       int batch, int num_query, int num_rel, float nonmatching_cost,
-                                                       int sample_negatives, int sample_nonmatching, float* loss_out,
-                                                       float* grad_rel, float* grad_conn, void* workspace, int policy_neg,
-                                                       int policy_nm, long long seed, long long rng_stream,
-                                                       int deterministic) {
-  if (!rel_bits || bad_policy(policy_neg) || bad_policy(policy_nm)) return EGTR_E_ARG;
-  if (num_rel > kWideMaxRel) return EGTR_E_UNSUPPORTED;
-  return relation_loss_launch<PackedTargetWide, true>(
-      stream, pred_rel, pred_conn, PackedTargetWide{reinterpret_cast<const unsigned long long*>(rel_bits)}, pred_idx, tgt_idx,
-      match_cost, out_offsets, batch, num_query, num_rel, nonmatching_cost, sample_negatives, sample_nonmatching, loss_out,
-      grad_rel, grad_conn, workspace, deterministic != 0, policy_neg, policy_nm, seed, rng_stream);
+  return with_target(target, target_format, num_rel, [&](auto tgt) {
+    return relation_loss_all_launch(stream, pred_rel, pred_conn, tgt, pred_idx, tgt_idx, match_cost, out_offsets, batch,
+                                    num_query, num_rel, nonmatching_cost, loss_out, grad_rel, grad_conn, workspace);
+  });
 }
 
 // ---- detection losses of one output set (labels / boxes / cardinality, egtr:611-659, 661-670, 692-712) ------------------

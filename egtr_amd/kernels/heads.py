@@ -371,76 +371,60 @@ def pack_relation_bits_wide(triplets, offsets, batch, total, num_query, num_rel)
     return bits
 
 
-def _packed_suffix(target, packed, B, N, R):
-    """The entry suffix for ``target``: "f32" (pointer table), "bits_f32" (words [B, N, N]) or "wide_bits_f32" (words
-    [B, N, N, W], W = ceil(R / 64)) -- the rank of the words selects the entry."""
+def _target_format(target, packed, B, N, R):
+    """The EGTR_REL_TARGET_* code of ``target``: 0 (pointer table), 1 (words [B, N, N]) or 2 (words [B, N, N, W],
+    W = ceil(R / 64)) -- the rank of the words selects the form."""
     if not packed:
-        return "f32"
+        return 0
     _chk(target, "rel_bits", torch.int64)
     if target.dim() == 4:
         if tuple(target.shape) != (B, N, N, (R + 63) // 64):
             raise RuntimeError(f"wide rel_bits must have shape {(B, N, N, (R + 63) // 64)}, got {tuple(target.shape)}")
-        return "wide_bits_f32"
+        return 2
     if tuple(target.shape) != (B, N, N):
         raise RuntimeError(f"rel_bits must have shape {(B, N, N)}, got {tuple(target.shape)}")
-    return "bits_f32"
+    return 1
 
 
 def relation_loss_launch(pred_rel, pred_conn, target, packed, pred_idx, tgt_idx, match_cost, out_off, nonmatching_cost,
                          sample_negatives, sample_nonmatching, deterministic=False):
-    """egtr_relation_loss_f32 (``target``: the device table of per-image pointers to dense fp32 targets) or, with
-    ``packed``, egtr_relation_loss_bits_f32 (``target``: the words int64 [B, N, N]) / egtr_relation_loss_wide_bits_f32 (the
-    words int64 [B, N, N, ceil(R / 64)]).  Returns (loss [2], grad_rel, grad_conn).
-    ``deterministic``: the egtr_relation_loss_det_* forms (ties at the selection threshold taken lowest flat index first)."""
-    B, N, _, R = pred_rel.shape
-    dev = pred_rel.device
-    suffix = _packed_suffix(target, packed, B, N, R)
-    loss = torch.empty(2, dtype=torch.float32, device=dev)
-    grad_rel = torch.empty_like(pred_rel)
-    grad_conn = torch.empty_like(pred_conn)
-    if deterministic:
-        nbytes, entry = _lib.lib().egtr_relation_loss_det_workspace_bytes(B, N), "egtr_relation_loss_det_"
-    else:
-        nbytes, entry = _lib.lib().egtr_relation_loss_workspace_bytes(B, N), "egtr_relation_loss_"
-    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
-    _lib.launch(entry + suffix, pred_rel.data_ptr(),
-                pred_conn.data_ptr(), target.data_ptr(), pred_idx.data_ptr(), tgt_idx.data_ptr(), match_cost.data_ptr(),
-                out_off.data_ptr(), B, N, R, float(nonmatching_cost), int(sample_negatives), int(sample_nonmatching),
-                loss.data_ptr(), grad_rel.data_ptr(), grad_conn.data_ptr(), ws.data_ptr())
-    return loss, grad_rel, grad_conn
+    """``relation_loss_policy_launch`` with the ``sample_*`` largest logits of both classes: what the criterion trains with."""
+    return relation_loss_policy_launch(pred_rel, pred_conn, target, packed, pred_idx, tgt_idx, match_cost, out_off,
+                                       nonmatching_cost, ("largest", sample_negatives), ("largest", sample_nonmatching),
+                                       deterministic=deterministic)
 
 
 def relation_loss_all_launch(pred_rel, pred_conn, target, packed, pred_idx, tgt_idx, match_cost, out_off, nonmatching_cost,
                              want_grad=True):
-    """egtr_relation_loss_all_f32 / (``packed``) egtr_relation_loss_all_bits_f32 or, for 4-D words,
-    egtr_relation_loss_all_wide_bits_f32: the un-sampled relation loss -- BCE over all
-    N N R elements -- and the connectivity loss; ``target`` as in ``relation_loss_launch``.  Returns (loss [2], grad_rel,
-    grad_conn); ``want_grad=False`` is the value-only launch: no gradient buffer is allocated or written, both come back None."""
+    """egtr_relation_loss_all_f32: the un-sampled relation loss -- BCE over all N N R elements -- and the connectivity loss;
+    ``target`` as in ``relation_loss_policy_launch``.  Returns (loss [2], grad_rel, grad_conn); ``want_grad=False`` is the
+    value-only launch: no gradient buffer is allocated or written, both come back None."""
     B, N, _, R = pred_rel.shape
     dev = pred_rel.device
-    suffix = _packed_suffix(target, packed, B, N, R)
+    fmt = _target_format(target, packed, B, N, R)
     loss = torch.empty(2, dtype=torch.float32, device=dev)
     grad_rel = torch.empty_like(pred_rel) if want_grad else None
     grad_conn = torch.empty_like(pred_conn) if want_grad else None
     ws = torch.empty(int(_lib.lib().egtr_relation_loss_all_workspace_bytes(B, N)), dtype=torch.uint8, device=dev)
-    _lib.launch("egtr_relation_loss_all_" + suffix, pred_rel.data_ptr(), pred_conn.data_ptr(),
-                target.data_ptr(), pred_idx.data_ptr(), tgt_idx.data_ptr(), match_cost.data_ptr(), out_off.data_ptr(), B, N, R,
+    _lib.launch("egtr_relation_loss_all_f32", pred_rel.data_ptr(), pred_conn.data_ptr(), target.data_ptr(), fmt,
+                pred_idx.data_ptr(), tgt_idx.data_ptr(), match_cost.data_ptr(), out_off.data_ptr(), B, N, R,
                 float(nonmatching_cost), loss.data_ptr(), _lib.ptr(grad_rel), _lib.ptr(grad_conn), ws.data_ptr())
     return loss, grad_rel, grad_conn
 
 
-RELATION_POLICIES = {"largest": 0, "random": 1, "all": 2}   # the policy codes of the egtr_relation_loss_policy_* entries
+RELATION_POLICIES = {"largest": 0, "random": 1, "all": 2}   # the policy codes of egtr_relation_loss_f32
 
 
 def relation_loss_policy_launch(pred_rel, pred_conn, target, packed, pred_idx, tgt_idx, match_cost, out_off, nonmatching_cost,
                                 negatives, nonmatching, seed=0, stream=0, deterministic=False):
-    """egtr_relation_loss_policy_f32 / (``packed``) _policy_bits_f32 or, for 4-D words, _policy_wide_bits_f32: one sampling
-    policy per candidate class.  ``negatives`` / ``nonmatching``: (policy, count) with policy "largest" | "random" | "all" (the
-    count of "all" is ignored; None there).  ``seed`` / ``stream``: the 64-bit words of a random class's keys, reduced modulo
-    2^64.  ``target`` as in ``relation_loss_launch``.  Returns (loss [2], grad_rel, grad_conn)."""
+    """egtr_relation_loss_f32: one sampling policy per candidate class.  ``target``: the device table of per-image pointers to
+    dense fp32 targets or, with ``packed``, the words int64 [B, N, N] / [B, N, N, ceil(R / 64)].  ``negatives`` /
+    ``nonmatching``: (policy, count) with policy "largest" | "random" | "all" (the count of "all" is ignored; None there).
+    ``seed`` / ``stream``: the 64-bit words of a random class's keys, reduced modulo 2^64.  ``deterministic``: ties at the
+    selection threshold of a "largest" class taken lowest flat index first.  Returns (loss [2], grad_rel, grad_conn)."""
     B, N, _, R = pred_rel.shape
     dev = pred_rel.device
-    suffix = _packed_suffix(target, packed, B, N, R)
+    fmt = _target_format(target, packed, B, N, R)
     codes, counts = [], []
     for name, (policy, count) in (("negatives", negatives), ("nonmatching", nonmatching)):
         if policy not in RELATION_POLICIES:
@@ -457,8 +441,8 @@ def relation_loss_policy_launch(pred_rel, pred_conn, target, packed, pred_idx, t
     loss = torch.empty(2, dtype=torch.float32, device=dev)
     grad_rel = torch.empty_like(pred_rel)
     grad_conn = torch.empty_like(pred_conn)
-    ws = torch.empty(int(_lib.lib().egtr_relation_loss_det_workspace_bytes(B, N)), dtype=torch.uint8, device=dev)
-    _lib.launch("egtr_relation_loss_policy_" + suffix, pred_rel.data_ptr(), pred_conn.data_ptr(), target.data_ptr(),
+    ws = torch.empty(int(_lib.lib().egtr_relation_loss_workspace_bytes(B, N)), dtype=torch.uint8, device=dev)
+    _lib.launch("egtr_relation_loss_f32", pred_rel.data_ptr(), pred_conn.data_ptr(), target.data_ptr(), fmt,
                 pred_idx.data_ptr(), tgt_idx.data_ptr(), match_cost.data_ptr(), out_off.data_ptr(), B, N, R,
                 float(nonmatching_cost), counts[0], counts[1], loss.data_ptr(), grad_rel.data_ptr(), grad_conn.data_ptr(),
                 ws.data_ptr(), codes[0], codes[1], s64(seed), s64(stream), 1 if deterministic else 0)

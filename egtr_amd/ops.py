@@ -897,7 +897,7 @@ ENV_ROUTE_SWITCHES = ("EGTR_DECODER_CLUSTER", "EGTR_GEMM_SPLIT_BF16", "EGTR_REL_
 # package's autograd Functions.  Three places on the training path depend on the order in which the hardware serves atomics; under
 # the mode each takes an order-free route, consulted AT CALL TIME (a route switch, not a fall-off: nothing is counted in FALLBACKS):
 #   MSDA backward, grad_value   fp32 atomics  ->  64-bit fixed point with integer atomics (egtr_msda_backward_det_*); float64 raises
-#   relation loss, tied logits  tickets       ->  lowest flat index first (egtr_relation_loss_det_*)
+#   relation loss, tied logits  tickets       ->  lowest flat index first (egtr_relation_loss_f32, deterministic = 1)
 #   rel_gate_{t} logging        fp32 atomics  ->  a torch reduction (fixed order); the model output never depended on it
 # Not covered: vendor kernels (MIOpen convolutions, rocBLAS GEMMs), ATen operations without a deterministic form, equality
 # across batch sizes / devices / builds, or between this route and the default one.  torch's own global switch
@@ -994,7 +994,7 @@ class matmul_precision_mode:
 # The criterion's `rel_sample_*_largest=False` ablation takes a uniform random subset of a candidate class instead of its largest
 # logits.  "python" (the default): the reference's composition -- nonzero() index lists and `random.sample` on the host; Python's
 # `random` stream is consumed exactly as the reference consumes it.  "device" (opt-in): the subset is the k candidates with the
-# largest keyed hash of their flat index (egtr_relation_loss_policy_*): no host wait, and a function of (seed, stream) alone --
+# largest keyed hash of their flat index (egtr_relation_loss_f32, policy 1): no host wait, and a function of (seed, stream) alone --
 # the same distribution, other bits, and Python's `random` stream is left alone.  Every launch with a random class uses the
 # current `stream` and advances it by one, so auxiliary output sets and successive steps draw independently; (seed, stream) is
 # the whole state (relation_sampler_state / set_relation_sampler_state: checkpoint and resume).  No environment switch.
@@ -1619,33 +1619,10 @@ def _relation_head(gate_q, gate_k, uq, uk, b1, w2r, b2r, w3r, b3r, w2c, b2c, w3c
 
 
 class RelationLossFunction(Function):
-    """loss_rel / loss_connectivity of the SGG criterion (training mode, largest-score sampling) with their gradients
-    from one pass over the logits (csrc/loss.hip, egtr_relation_loss_f32; egtr_relation_loss_bits_f32 when ``packed``:
-    ``target`` is then the words [B, N, N] instead of the pointer table, or the wide words [B, N, N, ceil(R / 64)], which take
-    egtr_relation_loss_wide_bits_f32); backward only scales the stored gradients."""
-
-    @staticmethod
-    def forward(ctx, pred_rel, pred_conn, target, pred_idx, tgt_idx, match_cost, out_off, nonmatching_cost,
-                sample_negatives, sample_nonmatching, packed=False):
-        pr = _chk(pred_rel.detach().contiguous(), "pred_rel", torch.float32)
-        pc = _chk(pred_conn.detach().contiguous(), "pred_connectivity", torch.float32)
-        loss, grad_rel, grad_conn = relation_loss_launch(pr, pc, target, packed, pred_idx, tgt_idx, match_cost, out_off,
-                                                         nonmatching_cost, sample_negatives, sample_nonmatching,
-                                                         deterministic=is_deterministic())
-        ctx.save_for_backward(grad_rel, grad_conn)
-        return loss[0], loss[1]
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, g_rel, g_conn):
-        grad_rel, grad_conn = ctx.saved_tensors
-        return grad_rel * g_rel, grad_conn * g_conn, None, None, None, None, None, None, None, None, None
-
-
-class RelationLossPolicyFunction(Function):
-    """loss_rel / loss_connectivity with one sampling policy per candidate class -- ``negatives`` / ``nonmatching`` =
-    (policy, count), policy "largest" | "random" | "all" (csrc/loss.hip, egtr_relation_loss_policy_f32 / _policy_bits_f32 /
-    _policy_wide_bits_f32 by the form of ``target``, as in RelationLossFunction).  ``seed`` / ``stream``: the words of a random
+    """loss_rel / loss_connectivity of the SGG criterion (training mode) with their gradients from one pass over the logits
+    (csrc/loss.hip, egtr_relation_loss_f32), one sampling policy per candidate class: ``negatives`` / ``nonmatching`` =
+    (policy, count), policy "largest" | "random" | "all".  ``target``: the pointer table of the dense targets or, when
+    ``packed``, the words [B, N, N] / the wide words [B, N, N, ceil(R / 64)].  ``seed`` / ``stream``: the words of a random
     class's keys.  Backward only scales the stored gradients."""
 
     @staticmethod
@@ -1671,8 +1648,8 @@ RELATION_LOSS_ALL = True   # module attribute (tests patch it for the switch-off
 
 class RelationLossAllFunction(Function):
     """loss_rel / loss_connectivity of the SGG criterion WITHOUT sampling -- evaluation mode (validation_loss) and training with
-    both ``rel_sample_*`` None: BCE over all N N R elements (csrc/loss.hip, egtr_relation_loss_all_f32; ``packed``:
-    egtr_relation_loss_all_bits_f32, or _all_wide_bits_f32 for 4-D words).  ``want_grad``: None = when ``pred_rel`` or ``pred_conn`` requires grad; False is the
+    both ``rel_sample_*`` None: BCE over all N N R elements (csrc/loss.hip, egtr_relation_loss_all_f32; ``target`` / ``packed``
+    as in RelationLossFunction).  ``want_grad``: None = when ``pred_rel`` or ``pred_conn`` requires grad; False is the
     value-only launch -- no gradient buffer exists.  Backward only scales the stored gradients."""
 
     @staticmethod
@@ -1877,10 +1854,11 @@ def _relation_operands(pred_rel, targets, indices, matching_costs, rel_bits):
 
 def relation_losses(pred_rel, pred_conn, targets, indices, matching_costs, nonmatching_cost, sample_negatives,
                     sample_nonmatching, rel_bits=None):
-    """(loss_rel, loss_connectivity) for device tensors: see RelationLossFunction.  ``indices`` / ``matching_costs``: the
+    """(loss_rel, loss_connectivity) for device tensors, the ``sample_*`` largest logits of both candidate classes: see
+    RelationLossFunction (the sampler state is neither read nor advanced).  ``indices`` / ``matching_costs``: the
     matcher's per-image device tensors; ``targets[b]["rel"]``: dense fp32 [N, N, R] on the device.  Targets that carry
-    ``"rel_triplets"`` and no ``"rel"`` take the packed entry: ``rel_bits`` (``egtr_amd.targets.pack_relations``, or
-    ``pack_relations_wide`` for 65 .. 256 predicates: 4-D words take the wide entries) when the
+    ``"rel_triplets"`` and no ``"rel"`` take a packed target format: ``rel_bits`` (``egtr_amd.targets.pack_relations``, or
+    ``pack_relations_wide`` for 65 .. 256 predicates: 4-D words are the wide format) when the
     caller packed the batch already, else packed here -- no dense target exists on that route.
     ``sample_negatives`` and ``sample_nonmatching`` both None: the un-sampled loss over all elements
     (RelationLossAllFunction; value-only when nothing requires grad).  Exactly one None is not a kernel route (the criterion
@@ -1895,14 +1873,14 @@ def relation_losses(pred_rel, pred_conn, targets, indices, matching_costs, nonma
                                             want_grad)
     else:
         out = RelationLossFunction.apply(pred_rel, pred_conn, target, pi, ti, mc, out_off, nonmatching_cost,
-                                         sample_negatives, sample_nonmatching, packed)
+                                         ("largest", sample_negatives), ("largest", sample_nonmatching), 0, 0, packed)
     del rels   # (kept alive until the launches were enqueued; the caller's targets own the storage)
     return out
 
 
 def relation_losses_sampled(pred_rel, pred_conn, targets, indices, matching_costs, nonmatching_cost, negatives, nonmatching,
                             rel_bits=None, seed=None, stream=None):
-    """(loss_rel, loss_connectivity) with one sampling policy per candidate class (RelationLossPolicyFunction): ``negatives`` --
+    """(loss_rel, loss_connectivity) with one sampling policy per candidate class (RelationLossFunction): ``negatives`` --
     the false candidates of the matched block -- and ``nonmatching`` -- the elements with an unmatched subject or object -- are
     (policy, count) with policy "largest" (the count n_true largest logits), "random" (a uniform subset of that size) or "all"
     (the whole class; count ignored).  The other arguments as in ``relation_losses``.  ``seed`` / ``stream``: the words of the
@@ -1916,7 +1894,7 @@ def relation_losses_sampled(pred_rel, pred_conn, targets, indices, matching_cost
         cur_seed = relation_sampler_state()[0]
     if seed is None:
         seed = cur_seed
-    out = RelationLossPolicyFunction.apply(pred_rel, pred_conn, target, pi, ti, mc, out_off, nonmatching_cost,
-                                           tuple(negatives), tuple(nonmatching), int(seed), int(stream), packed)
+    out = RelationLossFunction.apply(pred_rel, pred_conn, target, pi, ti, mc, out_off, nonmatching_cost,
+                                     tuple(negatives), tuple(nonmatching), int(seed), int(stream), packed)
     del rels
     return out

@@ -10,16 +10,16 @@ themselves instead:
 
 A dict that has ``"rel"`` is read as before, whatever else it carries.  Below the public interface the triplets become
 ``rel_bits``: int64 [B, N, N] read as unsigned, bit p of word [b, s, o] set iff (s, o, p) is a triplet of image b (a target
-value is 0 or 1).  The loss kernels read the words (csrc/loss.hip, egtr_relation_loss_bits_f32); ``unpack_relations`` gives the
+value is 0 or 1).  The loss kernels read the words (csrc/loss.hip, target format 1 of egtr_relation_loss_f32); ``unpack_relations`` gives the
 dense tensor back to the routes that evaluate the reference's tensor composition.
 
 A word holds 64 predicates.  A larger vocabulary (``MAX_REL_LABELS`` < ``num_rel_labels`` <= ``MAX_PACKED_REL_LABELS``, the
 relation head's 256) takes WIDE words (``pack_relations_wide``): int64 [B, N, N, W] with W = ceil(R / 64), bit p & 63 of word
 [b, s, o, p >> 6], bits at positions >= R zero; with W = 1 the memory is that of the [B, N, N] words.  The loss kernels read them
-through egtr_relation_loss_wide_bits_f32 and its deterministic and un-sampled siblings, so no dense target is built there
+as target format 2 of the sampled and the un-sampled loss entry under either tie rule, so no dense target is built there
 either (0.64 MB per image at N = 200, R = 100 where the dense tensor has 16 MB).  Beyond 256 predicates there are no words:
 ``dense_targets`` materialises the triplets as the dense tensor directly (``materialize_relations``) and the criterion takes the
-dense loss entries, which are generic in R."""
+dense target format, which is generic in R."""
 import torch
 
 from .kernels.heads import pack_relation_bits, pack_relation_bits_wide

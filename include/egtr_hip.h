@@ -48,7 +48,7 @@ enum {
  * library whose number differs from the one it was written against.  A purely additive change keeps the number (a caller
  * written against it stays valid); egtr_amd/_lib.py resolves every symbol it binds at load, so a library that lacks a newer
  * entry still fails loudly. */
-#define EGTR_ABI_VERSION 6
+#define EGTR_ABI_VERSION 7
 int egtr_abi_version(void);
 const char* egtr_status_string(int status);
 /* last HIP error string seen by this thread (for EGTR_E_LAUNCH) */
@@ -500,25 +500,6 @@ int egtr_hungarian_match_large_f32(egtr_stream_t stream, const float* logits, co
 long long egtr_hungarian_match_large_workspace_bytes(int batch, int num_query, int max_targets,
                                                      long long total_targets);
 
-/* Relation + connectivity losses of SceneGraphGenerationLoss in training mode (model/egtr.py:754-923 with
- * rel_sample_negatives / rel_sample_nonmatching set and *_largest = True), value AND gradient, without the reference's
- * per-image nonzero() index lists, host-side counts and gathers:
- *   loss_out[0] = loss_rel = mean over {true relations of the matched block} U {k1 highest-logit false candidates of the
- *                 block} U {k2 highest-logit elements with an unmatched subject or object} of
- *                 BCEWithLogits(pred_rel, target * w_a w_b),  w = 1 - sigmoid(matching cost), k = min(sample * n_true, #)
- *   loss_out[1] = loss_connectivity = mean BCEWithLogits(pred_conn, any_r target != 0)  over [batch, N, N]
- *   grad_rel [batch, N, N, R], grad_conn [batch, N, N] = d loss / d logits (dense, zeros where unselected).
- * pred_idx / tgt_idx / match_cost / out_offsets: the packed outputs of egtr_hungarian_match_f32 (out_offsets int32
- * [batch + 1], device); target_rel: DEVICE array of `batch` device pointers to the images' dense [N, N, R] targets;
- * nonmatching_cost: the criterion's constant (egtr:603-608).  workspace: egtr_relation_loss_workspace_bytes() bytes.
- * Elements tied with the k-th largest logit are taken in arrival order (the reference's topk leaves that unspecified). */
-int egtr_relation_loss_f32(egtr_stream_t stream, const float* pred_rel, const float* pred_conn,
-                           const float* const* target_rel, const int64_t* pred_idx, const int64_t* tgt_idx,
-                           const float* match_cost, const int* out_offsets, int batch, int num_query, int num_rel,
-                           float nonmatching_cost, int sample_negatives, int sample_nonmatching, float* loss_out,
-                           float* grad_rel, float* grad_conn, void* workspace);
-long long egtr_relation_loss_workspace_bytes(int batch, int num_query);
-
 /* Relation targets as bit-packed words: rel_bits [batch, N, N] uint64, bit p of word (s, o) of image b set iff (s, o, p) is
  * one of the image's relation triplets (the dense fp32 [N, N, R] target of the reference holds R <= 64 zeros / ones per
  * pair: 8 bytes instead of 4 R).  triplets int64 [total, 3] rows (subject, object, predicate), the images' rows
@@ -527,31 +508,59 @@ long long egtr_relation_loss_workspace_bytes(int batch, int num_query);
  * dropped, never written.  num_rel > 64: EGTR_E_UNSUPPORTED. */
 int egtr_pack_relations_u64(egtr_stream_t stream, const int64_t* triplets, const int* offsets, int batch, int total,
                             int num_query, int num_rel, uint64_t* rel_bits);
-/* egtr_relation_loss_f32 on packed targets (rel_bits as egtr_pack_relations_u64 writes them) instead of the pointer
- * table: the same passes, order, arithmetic and workspace; on the dense form of the same targets both entries return
- * the same bits.  The target passes load one word per (subject, object) pair.  num_rel > 64: EGTR_E_UNSUPPORTED. */
-int egtr_relation_loss_bits_f32(egtr_stream_t stream, const float* pred_rel, const float* pred_conn,
-                                const uint64_t* rel_bits, const int64_t* pred_idx, const int64_t* tgt_idx,
-                                const float* match_cost, const int* out_offsets, int batch, int num_query, int num_rel,
-                                float nonmatching_cost, int sample_negatives, int sample_nonmatching, float* loss_out,
-                                float* grad_rel, float* grad_conn, void* workspace);
 
-/* Deterministic forms of the two entries above: among the candidates whose logit equals the k-th largest of an (image,
- * problem), the ones with the LOWEST flat index (qa * N + qb) * R + r (query order) are taken instead of the first to arrive,
- * so the selected set -- and with it loss and gradient -- is a function of the inputs alone (the reference's topk leaves the
- * order among ties unspecified: any fixed rule conforms).  One more pass over pred_rel; workspace:
- * egtr_relation_loss_det_workspace_bytes() bytes.  The two det entries return the same bits on the same targets. */
-long long egtr_relation_loss_det_workspace_bytes(int batch, int num_query);
-int egtr_relation_loss_det_f32(egtr_stream_t stream, const float* pred_rel, const float* pred_conn,
-                               const float* const* target_rel, const int64_t* pred_idx, const int64_t* tgt_idx,
-                               const float* match_cost, const int* out_offsets, int batch, int num_query, int num_rel,
-                               float nonmatching_cost, int sample_negatives, int sample_nonmatching, float* loss_out,
-                               float* grad_rel, float* grad_conn, void* workspace);
-int egtr_relation_loss_det_bits_f32(egtr_stream_t stream, const float* pred_rel, const float* pred_conn,
-                                    const uint64_t* rel_bits, const int64_t* pred_idx, const int64_t* tgt_idx,
-                                    const float* match_cost, const int* out_offsets, int batch, int num_query, int num_rel,
-                                    float nonmatching_cost, int sample_negatives, int sample_nonmatching, float* loss_out,
-                                    float* grad_rel, float* grad_conn, void* workspace);
+/* Packed words for up to 256 predicates: rel_bits [batch, N, N, W] uint64 with W = ceil(num_rel / 64); bit p & 63 of word
+ * (s, o, p >> 6) of image b set iff (s, o, p) is one of the image's triplets, bits at positions >= num_rel zero (W = 1: the
+ * memory of the [batch, N, N] words above).  egtr_pack_relations_wide_u64: the contract of egtr_pack_relations_u64 (one
+ * memset + one launch, rel_bits fully overwritten, a row with an index out of range dropped, a duplicate counted once). 
+ * num_rel > 256: EGTR_E_UNSUPPORTED. */
+int egtr_pack_relations_wide_u64(egtr_stream_t stream, const int64_t* triplets, const int* offsets, int batch, int total,
+                                 int num_query, int num_rel, uint64_t* rel_bits);
+
+/* The relation target of both loss entries below: `target` read according to `target_format`.  The three forms run the same
+ * passes in the same order with the same arithmetic, so on the dense form of the same targets they return the same bits; a
+ * packed form loads one word per (subject, object) pair (a target is one bit of ONE word, the block count a popcount).
+ * EGTR_E_ARG: target NULL or a format outside 0 .. 2.  EGTR_E_UNSUPPORTED: num_rel above the format's limit. */
+#define EGTR_REL_TARGET_DENSE 0   /* DEVICE array of `batch` device pointers to the images' dense fp32 [N, N, R] targets */
+#define EGTR_REL_TARGET_WORDS 1   /* uint64 [batch, N, N] as egtr_pack_relations_u64 writes them, num_rel <= 64 */
+#define EGTR_REL_TARGET_WIDE  2   /* uint64 [batch, N, N, W] as egtr_pack_relations_wide_u64 writes them, num_rel <= 256 */
+
+/* Relation + connectivity losses of SceneGraphGenerationLoss in training mode (model/egtr.py:754-923 with
+ * rel_sample_negatives / rel_sample_nonmatching set), value AND gradient, without the reference's per-image nonzero() index
+ * lists, host-side counts and gathers:
+ *   loss_out[0] = loss_rel = mean over {true relations of the matched block} U {the k chosen false candidates of the block}
+ *                 U {the k chosen elements with an unmatched subject or object} of
+ *                 BCEWithLogits(pred_rel, target * w_a w_b),  w = 1 - sigmoid(matching cost)
+ *   loss_out[1] = loss_connectivity = mean BCEWithLogits(pred_conn, any_r target != 0)  over [batch, N, N]
+ *   grad_rel [batch, N, N, R], grad_conn [batch, N, N] = d loss / d logits (dense, zeros where unselected).
+ * pred_idx / tgt_idx / match_cost / out_offsets: the packed outputs of egtr_hungarian_match_f32 (out_offsets int32
+ * [batch + 1], device); nonmatching_cost: the criterion's constant (egtr:603-608).
+ * One sampling POLICY per candidate class (policy_neg: the false candidates of the matched block, count sample_negatives;
+ * policy_nm: the elements with an unmatched subject or object, count sample_nonmatching), per image with n_true true relations:
+ *   0 largest: the k = min(count n_true, n_class) largest logits (0 when n_true = 0) -- *_largest = True of the reference;
+ *   1 random:  a uniform random subset of that size;
+ *   2 all:     the whole class, k = n_class whatever n_true is; its count argument is ignored.
+ * (2, 2) selects the elements of egtr_relation_loss_all_f32 (its sums are formed in another order).
+ * The random choice: the k candidates with the largest KEY, key(flat) = lb32(lb32(flat ^ ka) + kb) over the 32-bit flat index
+ * flat = (qa N + qb) R + r in query order, lb32(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16,
+ * and (ka, kb) = the first two words of Philox4x32-10(counter = (image, class, lo32(stream), hi32(stream)), key = (lo32(seed),
+ * hi32(seed))), class 0 = block, 1 = outside.  Every step is a bijection of 32 bits: distinct elements have distinct keys, so a
+ * random class has no ties, draws no ticket and is a function of (seed, rng_stream, image, shape, matching) alone.
+ * Ties of a `largest` class: the candidates whose logit equals the k-th largest of an (image, problem) are taken in arrival
+ * order (the reference's topk leaves the order among ties unspecified: any rule conforms); deterministic != 0 takes the ones
+ * with the LOWEST flat index instead, one more pass over pred_rel, so the selected set -- and with it loss and gradient -- is a
+ * function of the inputs alone.
+ * workspace: egtr_relation_loss_workspace_bytes() bytes under either tie rule (it includes the tie counts int32 [batch, N, 2]).
+ * EGTR_E_ARG: a policy outside 0 .. 2 (before any HIP call).  EGTR_E_UNSUPPORTED: num_query * num_rel >= 2^22 or num_query >
+ * 4096; N N R >= 2^32 with a random class (the flat index is the key's 32-bit input); batch N N R >= 2^31 with a whole class
+ * (the selected count is a 32-bit int). */
+long long egtr_relation_loss_workspace_bytes(int batch, int num_query);
+int egtr_relation_loss_f32(egtr_stream_t stream, const float* pred_rel, const float* pred_conn, const void* target,
+                           int target_format, const int64_t* pred_idx, const int64_t* tgt_idx, const float* match_cost,
+                           const int* out_offsets, int batch, int num_query, int num_rel, float nonmatching_cost,
+                           int sample_negatives, int sample_nonmatching, float* loss_out, float* grad_rel, float* grad_conn,
+                           void* workspace, int policy_neg, int policy_nm, long long seed, long long rng_stream,
+                           int deterministic);
 
 /* The UN-SAMPLED relation loss (model/egtr.py:806-829 with both sample counts None: what the criterion computes in evaluation
  * mode, i.e. validation_loss, and in training with rel_sample_negatives = rel_sample_nonmatching = None):
@@ -559,86 +568,15 @@ int egtr_relation_loss_det_bits_f32(egtr_stream_t stream, const float* pred_rel,
  *   loss_out[1] = loss_connectivity, as above
  *   grad_rel = (sigmoid(pred_rel) - target * w_a w_b) / (batch N N R), grad_conn as above -- OPTIONAL: both NULL for the value
  *   alone (nothing of their size is written), one of them NULL is EGTR_E_ARG.
- * The arguments of egtr_relation_loss_f32 / egtr_relation_loss_bits_f32 without the two sample counts; a dense target is read
- * as a number in the loss and as `!= 0` for the connectivity.  Four launches (maps, all-elements pass, connectivity, finalize),
- * no atomics on values and no tickets: the same inputs give the same bits, and both entries return the same bits on the dense
- * form of the same targets.  workspace: egtr_relation_loss_all_workspace_bytes() bytes.  EGTR_E_UNSUPPORTED: num_rel > 64 on
- * the packed entry; on both, num_query * num_rel >= 2^22, num_query > 4096 or batch > 65535 (the first two limits are those of
- * the sampled entries above). */
+ * The arguments of egtr_relation_loss_f32 without the sample counts and policies; a dense target is read as a number in the
+ * loss and as `!= 0` for the connectivity.  Four launches (maps, all-elements pass, connectivity, finalize), no atomics on
+ * values and no tickets: the same inputs give the same bits.  workspace: egtr_relation_loss_all_workspace_bytes() bytes.
+ * EGTR_E_UNSUPPORTED: num_query * num_rel >= 2^22, num_query > 4096 or batch > 65535. */
 long long egtr_relation_loss_all_workspace_bytes(int batch, int num_query);
-int egtr_relation_loss_all_f32(egtr_stream_t stream, const float* pred_rel, const float* pred_conn,
-                               const float* const* target_rel, const int64_t* pred_idx, const int64_t* tgt_idx,
-                               const float* match_cost, const int* out_offsets, int batch, int num_query, int num_rel,
-                               float nonmatching_cost, float* loss_out, float* grad_rel, float* grad_conn, void* workspace);
-int egtr_relation_loss_all_bits_f32(egtr_stream_t stream, const float* pred_rel, const float* pred_conn,
-                                    const uint64_t* rel_bits, const int64_t* pred_idx, const int64_t* tgt_idx,
-                                    const float* match_cost, const int* out_offsets, int batch, int num_query, int num_rel,
-                                    float nonmatching_cost, float* loss_out, float* grad_rel, float* grad_conn,
-                                    void* workspace);
-
-/* Packed words for up to 256 predicates: rel_bits [batch, N, N, W] uint64 with W = ceil(num_rel / 64); bit p & 63 of word
- * (s, o, p >> 6) of image b set iff (s, o, p) is one of the image's triplets, bits at positions >= num_rel zero (W = 1: the
- * memory of the [batch, N, N] words above).  egtr_pack_relations_wide_u64: the contract of egtr_pack_relations_u64 (one
- * memset + one launch, rel_bits fully overwritten, a row with an index out of range dropped, a duplicate counted once).  The
- * three loss entries take the argument lists and workspaces of their _bits_ siblings and run the same passes in the same
- * order: each returns the bits of the dense entry on the dense form of the same target; a target is one bit of ONE word
- * (r >> 6), the block count a popcount over T T W words.  num_rel > 256: EGTR_E_UNSUPPORTED; every other limit is the dense
- * entries'. */
-int egtr_pack_relations_wide_u64(egtr_stream_t stream, const int64_t* triplets, const int* offsets, int batch, int total,
-                                 int num_query, int num_rel, uint64_t* rel_bits);
-int egtr_relation_loss_wide_bits_f32(egtr_stream_t stream, const float* pred_rel, const float* pred_conn,
-                                     const uint64_t* rel_bits, const int64_t* pred_idx, const int64_t* tgt_idx,
-                                     const float* match_cost, const int* out_offsets, int batch, int num_query, int num_rel,
-                                     float nonmatching_cost, int sample_negatives, int sample_nonmatching, float* loss_out,
-                                     float* grad_rel, float* grad_conn, void* workspace);
-int egtr_relation_loss_det_wide_bits_f32(egtr_stream_t stream, const float* pred_rel, const float* pred_conn,
-                                         const uint64_t* rel_bits, const int64_t* pred_idx, const int64_t* tgt_idx,
-                                         const float* match_cost, const int* out_offsets, int batch, int num_query,
-                                         int num_rel, float nonmatching_cost, int sample_negatives, int sample_nonmatching,
-                                         float* loss_out, float* grad_rel, float* grad_conn, void* workspace);
-int egtr_relation_loss_all_wide_bits_f32(egtr_stream_t stream, const float* pred_rel, const float* pred_conn,
-                                         const uint64_t* rel_bits, const int64_t* pred_idx, const int64_t* tgt_idx,
-                                         const float* match_cost, const int* out_offsets, int batch, int num_query,
-                                         int num_rel, float nonmatching_cost, float* loss_out, float* grad_rel,
-                                         float* grad_conn, void* workspace);
-
-/* One sampling POLICY per candidate class (policy_neg: the false candidates of the matched block; policy_nm: the elements with
- * an unmatched subject or object), per image with n_true / n_class as above:
- *   0 largest: the k = min(count n_true, n_class) largest logits (0 when n_true = 0) -- what the entries above do for both;
- *   1 random:  a uniform random subset of that size;
- *   2 all:     the whole class, k = n_class whatever n_true is; its count argument is ignored.
- * Selected = the true relations of the block U the k chosen of each class; loss, gradient, weights and the connectivity loss
- * are those of egtr_relation_loss_f32.  (0, 0) selects what the sampled entries select, (2, 2) the elements of the _all_ entries.
- * The random choice: the k candidates with the largest KEY, key(flat) = lb32(lb32(flat ^ ka) + kb) over the 32-bit flat index
- * flat = (qa N + qb) R + r in query order, lb32(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16,
- * and (ka, kb) = the first two words of Philox4x32-10(counter = (image, class, lo32(stream), hi32(stream)), key = (lo32(seed),
- * hi32(seed))), class 0 = block, 1 = outside.  Every step is a bijection of 32 bits: distinct elements have distinct keys, so a
- * random class has no ties, draws no ticket and is a function of (seed, rng_stream, image, shape, matching) alone.
- * deterministic != 0: the lowest-flat-index tie rule of the _det_ entries for a `largest` class.
- * The three entries take the arguments of egtr_relation_loss_f32 / _bits_f32 / _wide_bits_f32 first and return the same bits
- * on the same targets.  workspace: egtr_relation_loss_det_workspace_bytes() bytes (under either tie rule).
- * EGTR_E_ARG: a policy outside 0 .. 2 (before any HIP call).  EGTR_E_UNSUPPORTED: N N R >= 2^32 with a random class (the
- * flat index is the key's 32-bit input); batch N N R >= 2^31 with a whole class (the selected count is a 32-bit int);
- * otherwise the limits of the sibling entry. */
-int egtr_relation_loss_policy_f32(egtr_stream_t stream, const float* pred_rel, const float* pred_conn,
-                                  const float* const* target_rel, const int64_t* pred_idx, const int64_t* tgt_idx,
-                                  const float* match_cost, const int* out_offsets, int batch, int num_query, int num_rel,
-                                  float nonmatching_cost, int sample_negatives, int sample_nonmatching, float* loss_out,
-                                  float* grad_rel, float* grad_conn, void* workspace, int policy_neg, int policy_nm,
-                                  long long seed, long long rng_stream, int deterministic);
-int egtr_relation_loss_policy_bits_f32(egtr_stream_t stream, const float* pred_rel, const float* pred_conn,
-                                       const uint64_t* rel_bits, const int64_t* pred_idx, const int64_t* tgt_idx,
-                                       const float* match_cost, const int* out_offsets, int batch, int num_query, int num_rel,
-                                       float nonmatching_cost, int sample_negatives, int sample_nonmatching, float* loss_out,
-                                       float* grad_rel, float* grad_conn, void* workspace, int policy_neg, int policy_nm,
-                                       long long seed, long long rng_stream, int deterministic);
-int egtr_relation_loss_policy_wide_bits_f32(egtr_stream_t stream, const float* pred_rel, const float* pred_conn,
-                                            const uint64_t* rel_bits, const int64_t* pred_idx, const int64_t* tgt_idx,
-                                            const float* match_cost, const int* out_offsets, int batch, int num_query,
-                                            int num_rel, float nonmatching_cost, int sample_negatives, int sample_nonmatching,
-                                            float* loss_out, float* grad_rel, float* grad_conn, void* workspace,
-                                            int policy_neg, int policy_nm, long long seed, long long rng_stream,
-                                            int deterministic);
+int egtr_relation_loss_all_f32(egtr_stream_t stream, const float* pred_rel, const float* pred_conn, const void* target,
+                               int target_format, const int64_t* pred_idx, const int64_t* tgt_idx, const float* match_cost,
+                               const int* out_offsets, int batch, int num_query, int num_rel, float nonmatching_cost,
+                               float* loss_out, float* grad_rel, float* grad_conn, void* workspace);
 
 /* IoU matrix of the reference's native evaluator routine, lib/fpn/box_intersections_cpu/bbox.pyx: mode 0 =
  * bbox_overlaps (:21-61), mode 1 = bbox_intersections (:64-108).  boxes [num_boxes, 4], query_boxes [num_query, 4]

@@ -1,5 +1,5 @@
-"""Helper (no tests): the relation loss with one sampling POLICY per candidate class (csrc/loss.hip, egtr_relation_loss_policy_*)
-restated in numpy -- the random key (Philox4x32-10 + two rounds of a 32-bit mixer, csrc/rel_sample_key.h) and a float64
+"""Helper (no tests): the relation loss with one sampling POLICY per candidate class (csrc/loss.hip, policy_neg / policy_nm of
+egtr_relation_loss_f32) restated in numpy -- the random key (Philox4x32-10 + two rounds of a 32-bit mixer, csrc/rel_sample_key.h) and a float64
 expectation of ``mult`` / ``grad`` / ``loss_rel`` built on loss_restated._select / relation_expectation.  Shared by
 tests/test_relation_sampling_cpu.py and tests/test_gpu_relation_sampling.py.
 

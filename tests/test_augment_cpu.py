@@ -280,7 +280,7 @@ def test_null_arguments_are_rejected_without_a_gpu():
     """Argument validation happens before any HIP call, so it is checkable on a CPU-only box."""
     from egtr_amd import _lib
     h = _lib.lib()
-    assert h.egtr_abi_version() == 6
+    assert h.egtr_abi_version() == 7
     for entry in (h.egtr_preprocess_augment_f32, h.egtr_preprocess_augment_bf16):
         assert entry(None, None, None, 1, None, None, 8, 8, 0, 0, 0, 0, 0, 0, None, None, None) == -1
         # a first pass without its descriptors or its workspace, on otherwise non-null (never dereferenced) arguments

@@ -21,7 +21,7 @@ def test_entry_is_declared_exported_and_bound():
         assert re.search(r"\b%s\s*\(" % name, hdr) and name in _lib.SIGNATURES and hasattr(h, name)
     assert _lib.SIGNATURES[ENTRY] == _lib.SIGNATURES["egtr_detection_loss_f32"] + [ctypes.c_void_p]
     assert _lib._RESTYPES[QUERY] is ctypes.c_longlong
-    assert h.egtr_abi_version() == 6
+    assert h.egtr_abi_version() == 7
 
 
 def test_constants_of_the_binding_are_the_kernels():

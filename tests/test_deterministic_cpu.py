@@ -71,7 +71,7 @@ def test_float64_backward_is_refused_by_name_under_the_mode():
             K.ms_deform_attn_backward(v, shp, lsi, loc, at, torch.zeros(1, 3, 8, dtype=torch.float64), 64)
 
 
-# ---- the tie rule of egtr_relation_loss_det_*: restated with numpy ---------------------------------------------------------
+# ---- the tie rule of egtr_relation_loss_f32 with deterministic = 1: restated with numpy ------------------------------------
 # (tests/loss_restated.py; tests/test_gpu_deterministic.py imports the two names from here)
 from loss_restated import relation_selection, topk_lowest_index_first  # noqa: E402,F401
 

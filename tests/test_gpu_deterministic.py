@@ -237,7 +237,8 @@ def test_loss_ties_are_taken_lowest_index_first():
     # the switch reaches the kernels through the autograd Function as well
     with ops.deterministic():
         prg = pr.clone().requires_grad_(True)
-        l_rel, l_conn = ops.RelationLossFunction.apply(prg, pc, bits, pi, ti, mc, off, nm, K_TIE, K_TIE, True)
+        l_rel, l_conn = ops.RelationLossFunction.apply(prg, pc, bits, pi, ti, mc, off, nm, ("largest", K_TIE), ("largest", K_TIE), 0, 0,
+                                                       True)
         l_rel.backward()
     assert RT.same_bits(prg.grad.cpu(), results[True][1])
 

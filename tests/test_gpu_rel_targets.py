@@ -1,5 +1,5 @@
 """GPU (-m gpu): relation targets as triplets / bit-packed words -- the pack kernel against the CPU
-composition, egtr_relation_loss_bits_f32 bit-identical to egtr_relation_loss_f32 on the dense form of the same targets
+composition, egtr_relation_loss_f32 on the words bit-identical to itself on the dense form of the same targets
 and within the oracle's tolerance, one training step and one evaluation of the small model with both target forms."""
 import functools
 import json

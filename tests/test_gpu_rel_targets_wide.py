@@ -1,7 +1,7 @@
 """GPU (-m gpu): wide packed relation targets -- int64 [B, N, N, W] words, W = ceil(R / 64), 65 .. 256
-predicates: the pack kernel against the CPU composition; egtr_relation_loss_wide_bits_f32, its deterministic and its un-sampled
-sibling bit-identical to the dense entries on the dense form of the same targets; at W = 1 bit-identical to the narrow packed
-entries; the float64 oracle; and the 100-predicate small model with both target forms inside ONE step (training, validation and
+predicates: the pack kernel against the CPU composition; the loss entries on wide words, under both tie rules and un-sampled,
+bit-identical to the dense target format on the dense form of the same targets; at W = 1 bit-identical to the narrow packed
+format; the float64 oracle; and the 100-predicate small model with both target forms inside ONE step (training, validation and
 deterministic mode) with every dense materialisation made to raise.  The method, and the helpers ``distinct_logits``,
 ``matcher_flat`` and ``same_bits``, are those of tests/test_gpu_rel_targets.py."""
 import functools

@@ -1,5 +1,5 @@
 """GPU (-m gpu): the un-sampled relation loss (csrc/loss.hip: rel_all_prep, rel_loss_all, conn_loss, rel_loss_all_finalize; the
-C entries egtr_relation_loss_all_f32 / _bits_f32) against the float64 restatement of tests/relation_loss_all_restated.py (pinned
+C entries egtr_relation_loss_all_f32 on dense and packed targets) against the float64 restatement of tests/relation_loss_all_restated.py (pinned
 to the criterion's own composition, and its wrong neighbours shown to move, by tests/test_relation_loss_all_cpu.py), its
 bit-level properties, its value-only launch, and the routes that lead to it: the criterion in evaluation mode and in the
 un-sampled training configuration, ``DataParallelTrainer.validation_step``.

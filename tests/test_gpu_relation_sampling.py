@@ -1,9 +1,9 @@
-"""GPU (-m gpu): the relation loss with one sampling policy per candidate class (csrc/loss.hip, egtr_relation_loss_policy_*;
-DESIGN.md 4.11) against the float64 twin tests/relation_sampling_restated.py (its anchors: tests/test_relation_sampling_cpu.py).
+"""GPU (-m gpu): the relation loss with one sampling policy per candidate class (csrc/loss.hip, policy_neg / policy_nm of
+egtr_relation_loss_f32) against the float64 twin tests/relation_sampling_restated.py (its anchors: tests/test_relation_sampling_cpu.py).
 
 Bars, those of test_gpu_loss_selection.py: loss 1e-5 relative, gradient max(1e-7, 1e-6 max|grad_ref|), and grad != 0 <=> mult > 0
 exactly -- the selected SET is the twin's, element by element.  Where a `largest` class has candidates tied at its threshold the
-deterministic entry takes the twin's (lowest flat index first); the ticket entry may take others of the tied ones, so there the
+deterministic tie rule takes the twin's (lowest flat index first); the ticket rule may take others of the tied ones, so there the
 set is compared outside them and counted inside."""
 import random
 
@@ -200,7 +200,8 @@ def test_stream_and_seed_select_other_sets_and_the_old_entries_keep_their_bits()
     for key, s in sets.items():
         assert np.array_equal(s, RS.expectation(c, neg, nm, *key).mult > 0), key
     assert not np.array_equal(sets[5, 0], sets[5, 1]) and not np.array_equal(sets[5, 0], sets[6, 0])
-    # (largest, largest) through the policy entry: the set and the bits of the old deterministic entry (tie-free logits)
+    # (largest, largest) through the policy entry: the set and the bits of the old deterministic entry (tie-free logits).  Both
+    # sides are now the same entry with the same arguments and run the same kernel instantiation.
     pol = launch(c, (L, 2), (L, 3), det=True)
     assert same_bits(pol[1], before[4]) and same_bits(pol[2], before[5])
     assert rel_err(float(pol[0][0]), float(before[3][0])) < 1e-6

@@ -54,7 +54,7 @@ ROUTES = {
     "S": PRE + 2 * [LIN, GROUPED, MSDA, LIN, LN, (LIN, 2), LN_POS] + CLUSTER + HEADS,
     "S-train": (["egtr_level_geometry_f32"] + 2 * ENCODER_TRAIN + [LIN] + 3 * DECODER_TRAIN
                 + [(LIN, 4), "egtr_hungarian_match_f32", (LIN, 10), "egtr_rel_head_streams_f32",
-                   "egtr_rel_head_forward_bf16x6_save_f32", "egtr_detection_loss_f32", "egtr_relation_loss_det_f32",
+                   "egtr_rel_head_forward_bf16x6_save_f32", "egtr_detection_loss_f32", "egtr_relation_loss_f32",
                    COLSUM, WGRAD, COLSUM, WCOLSUM, WGRAD, (COLSUM, 2), "egtr_rel_head_backward_pairs_f32", (LIN_BWD, 8), COLSUM,
                    (LIN_BWD, 2), COLSUM]
                 + 3 * DECODER_TRAIN_BWD + [COLSUM] + 2 * ENCODER_TRAIN_BWD + [(WCOLSUM, 4)]),

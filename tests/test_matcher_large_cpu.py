@@ -90,7 +90,7 @@ def test_the_one_wave_entry_keeps_its_limit(h):
     st = h.egtr_hungarian_match_f32(None, p, p, p, p, p, p, 2, 1500, 1, 30, 1.0, 5.0, 2.0, 0, 0.0, 0.0, p, p, p, None, None,
                                     None, None)
     assert st == E_UNSUPPORTED
-    assert h.egtr_abi_version() == 6
+    assert h.egtr_abi_version() == 7
 
 
 def test_routing_predicate_on_both_sides_of_every_bound():

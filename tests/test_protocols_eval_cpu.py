@@ -231,4 +231,4 @@ def test_c_entry_rejects_bad_arguments_without_a_gpu():
     assert call(ok, B=0) == 0                                  # an empty batch is no error and no launch
     assert h.egtr_matched_topk_workspace_bytes(1, 8, 1025) == -1
     assert h.egtr_matched_topk_workspace_bytes(2, 201, 100) >= 2 * 100 * 8
-    assert h.egtr_abi_version() == 6
+    assert h.egtr_abi_version() == 7

@@ -3,6 +3,7 @@ built the reference's way (data/visual_genome.py:74-80), the evaluators' GT entr
 model, and the two C entries' argument checks."""
 import json
 import os
+import re
 import sys
 
 import numpy as np
@@ -187,8 +188,15 @@ def test_device_route_on_cpu_tensors_equal_with_triplet_targets(neg, nm):
 def test_new_entries_resolve_and_reject_null_arguments():
     from egtr_amd import _lib
     h = _lib.lib()
-    assert "egtr_pack_relations_u64" in _lib.SIGNATURES and "egtr_relation_loss_bits_f32" in _lib.SIGNATURES
+    assert "egtr_pack_relations_u64" in _lib.SIGNATURES and "egtr_relation_loss_f32" in _lib.SIGNATURES
     assert h.egtr_pack_relations_u64(None, None, None, 2, 3, 7, 5, None) == -1
-    assert h.egtr_relation_loss_bits_f32(None, None, None, None, None, None, None, None, 2, 7, 5, 1.0, 80, 80, None, None,
-                                         None, None) == -1
-    assert h.egtr_abi_version() == 6
+    words = 1                                                                # EGTR_REL_TARGET_WORDS: the packed target format
+    assert h.egtr_relation_loss_f32(None, None, None, None, words, None, None, None, None, 2, 7, 5, 1.0, 80, 80, None, None,
+                                    None, None, 0, 0, 0, 0, 0) == -1
+    # the packed form is an argument, not an entry of its own: four relation-loss names in the table and in the header
+    names = {"egtr_relation_loss_f32", "egtr_relation_loss_workspace_bytes", "egtr_relation_loss_all_f32",
+             "egtr_relation_loss_all_workspace_bytes"}
+    assert {n for n in _lib.SIGNATURES if n.startswith("egtr_relation_loss")} == names
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "include", "egtr_hip.h")) as f:
+        assert set(re.findall(r"\b(egtr_relation_loss\w*)\s*\(", f.read())) == names
+    assert h.egtr_abi_version() == 7

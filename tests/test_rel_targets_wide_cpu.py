@@ -1,6 +1,6 @@
 """CPU: wide packed relation targets -- int64 [B, N, N, W] words with W = ceil(R / 64) for up to 256
 predicates: ``pack_relations_wide`` / ``unpack_relations`` against a dense tensor built by hand, the W = 1 form against
-``pack_relations``, the argument checks of the four C entries (no GPU: host addresses that no kernel ever sees) and the
+``pack_relations``, the argument checks of the C entries (no GPU: host addresses that no kernel ever sees) and the
 criterion on CPU tensors at 100 predicates."""
 import ctypes
 import os
@@ -11,8 +11,9 @@ import torch
 
 N = 5
 RS = (1, 63, 64, 65, 100, 127, 128, 129, 191, 192, 193, 255, 256)
-NEW_ENTRIES = ("egtr_pack_relations_wide_u64", "egtr_relation_loss_wide_bits_f32", "egtr_relation_loss_det_wide_bits_f32",
-               "egtr_relation_loss_all_wide_bits_f32")
+LOSS_ENTRIES = ("egtr_relation_loss_workspace_bytes", "egtr_relation_loss_f32", "egtr_relation_loss_all_workspace_bytes",
+                "egtr_relation_loss_all_f32")
+DENSE, WORDS, WIDE = 0, 1, 2                                                             # EGTR_REL_TARGET_*
 E_ARG, E_UNSUPPORTED = -1, -3
 
 
@@ -90,24 +91,30 @@ def test_new_symbols_are_bound_and_declared():
     with open(os.path.join(here, "..", "include", "egtr_hip.h")) as f:
         header = f.read()
     h = _lib.lib()
-    for name in NEW_ENTRIES:
+    for name in ("egtr_pack_relations_wide_u64",) + LOSS_ENTRIES:
         assert name in _lib.SIGNATURES and hasattr(h, name)
-        assert re.search(r"\bint\s+" + name + r"\s*\(", header), name
-    sib = {"egtr_pack_relations_wide_u64": "egtr_pack_relations_u64", "egtr_relation_loss_wide_bits_f32": "egtr_relation_loss_bits_f32",
-           "egtr_relation_loss_det_wide_bits_f32": "egtr_relation_loss_det_bits_f32",
-           "egtr_relation_loss_all_wide_bits_f32": "egtr_relation_loss_all_bits_f32"}
-    for name, other in sib.items():
-        assert _lib.SIGNATURES[name] == _lib.SIGNATURES[other]                          # the siblings' argument lists
-    assert h.egtr_abi_version() == 6 and _lib.ABI_VERSION == 6
+        assert re.search(r"\b(int|long long)\s+" + name + r"\s*\(", header), name
+    assert _lib.SIGNATURES["egtr_pack_relations_wide_u64"] == _lib.SIGNATURES["egtr_pack_relations_u64"]
+    # the per-form, per-tie-rule and per-policy entries are gone: the four above are every relation-loss name there is
+    assert {n for n in _lib.SIGNATURES if n.startswith("egtr_relation_loss")} == set(LOSS_ENTRIES)
+    assert set(re.findall(r"\b(egtr_relation_loss\w*)\s*\(", header)) == set(LOSS_ENTRIES)
+    for code, macro in ((DENSE, "EGTR_REL_TARGET_DENSE"), (WORDS, "EGTR_REL_TARGET_WORDS"), (WIDE, "EGTR_REL_TARGET_WIDE")):
+        assert re.search(r"#define\s+" + macro + r"\s+%d\b" % code, header), macro
+    assert h.egtr_abi_version() == 7 and _lib.ABI_VERSION == 7
+
+
+def _host_pointer():
+    raw = ctypes.create_string_buffer(64 + 16)
+    return raw, (ctypes.addressof(raw) + 15) & ~15
 
 
 def test_c_entries_validate_without_a_gpu():
-    """NULL operands are EGTR_E_ARG, num_rel = 257 is EGTR_E_UNSUPPORTED, both before any HIP call; the narrow entries still
-    answer EGTR_E_UNSUPPORTED at 65."""
+    """NULL operands and an unknown target format are EGTR_E_ARG, num_rel above the format's limit (65 on words, 257 on wide
+    words) is EGTR_E_UNSUPPORTED, both before any HIP call: the packing entries, the sampled entry under each target format and
+    tie rule, the un-sampled entry under each target format."""
     from egtr_amd import _lib
     h = _lib.lib()
-    raw = ctypes.create_string_buffer(64 + 16)
-    p = (ctypes.addressof(raw) + 15) & ~15
+    raw, p = _host_pointer()
     pack = h.egtr_pack_relations_wide_u64
     assert pack(None, None, None, 2, 3, 7, 100, None) == E_ARG
     for ptrs in ((None, p, p), (p, None, p), (p, p, None)):
@@ -116,45 +123,80 @@ def test_c_entries_validate_without_a_gpu():
     for sizes in ((0, 3, 7, 100), (2, -1, 7, 100), (2, 3, 0, 100), (2, 3, 7, 0)):
         assert pack(None, p, p, *sizes, p) == E_ARG, sizes
     assert h.egtr_pack_relations_u64(None, p, p, 2, 3, 7, 65, p) == E_UNSUPPORTED
-    for name in ("egtr_relation_loss_wide_bits_f32", "egtr_relation_loss_det_wide_bits_f32"):
-        entry = getattr(h, name)
+    for fmt in (DENSE, WORDS, WIDE):
+        for deterministic in (0, 1):
+            _sampled_entry_validates(h.egtr_relation_loss_f32, p, fmt, deterministic)
+        _all_entry_validates(h.egtr_relation_loss_all_f32, p, fmt)
 
-        def call(ptrs=(p,) * 7, sizes=(2, 7, 100), out=(p, p, p, p), entry=entry):
-            return entry(None, *ptrs, *sizes, 1.0, 80, 80, *out)
-        assert call(ptrs=(None,) * 7, out=(None,) * 4) == E_ARG
-        for i in range(7):
-            assert call(ptrs=tuple(None if j == i else p for j in range(7))) == E_ARG, (name, i)
-        for i in range(4):
-            assert call(out=tuple(None if j == i else p for j in range(4))) == E_ARG, (name, i)
-        assert call(sizes=(2, 7, 257)) == E_UNSUPPORTED
-        assert call(sizes=(2, 7, 0)) == E_ARG and call(sizes=(0, 7, 100)) == E_ARG
-        assert call(sizes=(1, 4097, 100)) == E_UNSUPPORTED                   # the dense entries' limit on N
-    entry = h.egtr_relation_loss_all_wide_bits_f32
 
-    def call_all(ptrs=(p,) * 7, sizes=(2, 7, 100), out=(p, p, p, p)):
-        return entry(None, *ptrs, *sizes, 1.0, *out)
+def _sampled_entry_validates(entry, p, fmt, deterministic):
+    R = 100 if fmt == WIDE else 50
+
+    def call(ptrs=(p,) * 7, sizes=(2, 7, R), out=(p, p, p, p), fmt=fmt):
+        return entry(None, *ptrs[:3], fmt, *ptrs[3:], *sizes, 1.0, 80, 80, *out, 0, 0, 0, 0, deterministic)
+    assert call(ptrs=(None,) * 7, out=(None,) * 4) == E_ARG
+    for i in range(7):
+        assert call(ptrs=tuple(None if j == i else p for j in range(7))) == E_ARG, i
+    for i in range(4):
+        assert call(out=tuple(None if j == i else p for j in range(4))) == E_ARG, i
+    for bad in (-1, 3):                                                      # all other operands valid
+        assert call(fmt=bad) == E_ARG, bad
+    if fmt != DENSE:                                                         # (a valid call is never made: these are host addresses)
+        assert call(sizes=(2, 7, 65 if fmt == WORDS else 257)) == E_UNSUPPORTED
+    assert call(ptrs=(p, p, None, p, p, p, p), sizes=(2, 7, 257)) == E_ARG   # a NULL target comes before the limit
+    assert call(sizes=(2, 7, 0)) == E_ARG and call(sizes=(0, 7, R)) == E_ARG
+    assert call(sizes=(1, 4097, R)) == E_UNSUPPORTED                         # the limit on N, the same under every format
+
+
+def _all_entry_validates(entry, p, fmt):
+    R = 100 if fmt == WIDE else 50
+
+    def call_all(ptrs=(p,) * 7, sizes=(2, 7, R), out=(p, p, p, p), fmt=fmt):
+        return entry(None, *ptrs[:3], fmt, *ptrs[3:], *sizes, 1.0, *out)
     assert call_all(ptrs=(None,) * 7, out=(None,) * 4) == E_ARG
     for i in range(7):
         assert call_all(ptrs=tuple(None if j == i else p for j in range(7))) == E_ARG, i
     assert call_all(out=(None, p, p, p)) == E_ARG and call_all(out=(p, p, p, None)) == E_ARG
     assert call_all(out=(p, None, p, p)) == E_ARG and call_all(out=(p, p, None, p)) == E_ARG          # ONE NULL gradient
-    assert call_all(sizes=(2, 7, 257)) == E_UNSUPPORTED
-    assert call_all(sizes=(2, 7, 257), out=(p, None, None, p)) == E_UNSUPPORTED                        # value-only form
-    assert h.egtr_relation_loss_bits_f32(None, *(p,) * 7, 2, 7, 65, 1.0, 80, 80, p, p, p, p) == E_UNSUPPORTED
-    assert h.egtr_relation_loss_det_bits_f32(None, *(p,) * 7, 2, 7, 65, 1.0, 80, 80, p, p, p, p) == E_UNSUPPORTED
-    assert h.egtr_relation_loss_all_bits_f32(None, *(p,) * 7, 2, 7, 65, 1.0, p, p, p, p) == E_UNSUPPORTED
+    for bad in (-1, 3):
+        assert call_all(fmt=bad) == E_ARG, bad
+        assert call_all(fmt=bad, out=(p, None, None, p)) == E_ARG
+    if fmt != DENSE:
+        over = 65 if fmt == WORDS else 257
+        assert call_all(sizes=(2, 7, over)) == E_UNSUPPORTED
+        assert call_all(sizes=(2, 7, over), out=(p, None, None, p)) == E_UNSUPPORTED                   # value-only form
+
+
+class _Recorder:
+    """stands in for ``_lib.launch``: (name, target_format, policy_neg, policy_nm, deterministic) of every call, picked out
+    of the argument tuple by position (None where the un-sampled entry has no such argument)"""
+
+    def __init__(self):
+        self.calls = []
+
+    def __call__(self, name, *a, **k):
+        if name == "egtr_relation_loss_f32":
+            assert len(a) == 23
+            self.calls.append((name, a[3], a[18], a[19], a[22]))
+        else:
+            assert name == "egtr_relation_loss_all_f32" and len(a) == 16
+            self.calls.append((name, a[3], None, None, None))
+
+
+def _fake_library(monkeypatch):
+    from egtr_amd import _lib
+    rec = _Recorder()
+    monkeypatch.setattr(_lib, "launch", rec)
+    monkeypatch.setattr(_lib, "lib", lambda: type("L", (), {"egtr_relation_loss_workspace_bytes": staticmethod(lambda b, n: 16),
+                                                            "egtr_relation_loss_all_workspace_bytes": staticmethod(lambda b, n: 16)})())
+    return rec
 
 
 def test_launch_helpers_select_the_entry_by_the_rank_of_the_words(monkeypatch):
-    """4-D words take the wide entries, 3-D words the narrow ones; W != ceil(R / 64) is a RuntimeError (no GPU: the launch is
-    recorded, not made)."""
-    from egtr_amd import _lib
+    """4-D words are target format 2, 3-D words 1, a pointer table 0; ``deterministic`` arrives as 1; integer counts are the
+    policies (0, 0); W != ceil(R / 64) is a RuntimeError (no GPU: the launch is recorded, not made)."""
     from egtr_amd.kernels import heads
-    called = []
-    monkeypatch.setattr(_lib, "launch", lambda name, *a, **k: called.append(name))
-    monkeypatch.setattr(_lib, "lib", lambda: type("L", (), {"egtr_relation_loss_workspace_bytes": staticmethod(lambda b, n: 16),
-                                                            "egtr_relation_loss_det_workspace_bytes": staticmethod(lambda b, n: 16),
-                                                            "egtr_relation_loss_all_workspace_bytes": staticmethod(lambda b, n: 16)})())
+    rec = _fake_library(monkeypatch)
     monkeypatch.setattr(heads, "_chk", lambda t, *a, **k: t)
     B, R = 2, 100
     pr, pc = torch.zeros(B, N, N, R), torch.zeros(B, N, N, 1)
@@ -165,13 +207,45 @@ def test_launch_helpers_select_the_entry_by_the_rank_of_the_words(monkeypatch):
     heads.relation_loss_all_launch(pr, pc, wide, True, z, z, z, z, 1.0)
     heads.relation_loss_launch(pr, pc, narrow, True, z, z, z, z, 1.0, 80, 80)
     heads.relation_loss_all_launch(pr, pc, narrow, True, z, z, z, z, 1.0)
-    assert called == ["egtr_relation_loss_wide_bits_f32", "egtr_relation_loss_det_wide_bits_f32",
-                      "egtr_relation_loss_all_wide_bits_f32", "egtr_relation_loss_bits_f32", "egtr_relation_loss_all_bits_f32"]
+    heads.relation_loss_launch(pr, pc, z, False, z, z, z, z, 1.0, 80, 80, deterministic=True)
+    heads.relation_loss_all_launch(pr, pc, z, False, z, z, z, z, 1.0)
+    heads.relation_loss_policy_launch(pr, pc, narrow, True, z, z, z, z, 1.0, ("random", 80), ("all", None))
+    S, A = "egtr_relation_loss_f32", "egtr_relation_loss_all_f32"
+    assert rec.calls == [(S, WIDE, 0, 0, 0), (S, WIDE, 0, 0, 1), (A, WIDE, None, None, None), (S, WORDS, 0, 0, 0),
+                         (A, WORDS, None, None, None), (S, DENSE, 0, 0, 1), (A, DENSE, None, None, None), (S, WORDS, 1, 2, 0)]
     for bad in (torch.zeros(B, N, N, 1, dtype=torch.int64), torch.zeros(B, N, N, 3, dtype=torch.int64)):
         with pytest.raises(RuntimeError, match="wide rel_bits"):
             heads.relation_loss_launch(pr, pc, bad, True, z, z, z, z, 1.0, 80, 80)
         with pytest.raises(RuntimeError, match="wide rel_bits"):
             heads.relation_loss_all_launch(pr, pc, bad, True, z, z, z, z, 1.0)
+
+
+def test_relation_losses_passes_the_deterministic_mode_as_the_flag(monkeypatch):
+    """``ops.relation_losses`` on CPU tensors, the launch recorded: inside ``ops.deterministic()`` the entry's flag is 1, outside
+    it is 0 (the route table of tests/test_gpu_routes.py names the entry, which is the same under both rules); the sampler
+    state is not touched."""
+    from egtr_amd import ops
+    from egtr_amd.kernels import heads
+    rec = _fake_library(monkeypatch)
+    monkeypatch.setattr(heads, "_chk", lambda t, *a, **k: t)
+    monkeypatch.setattr(ops, "_chk", lambda t, *a, **k: t)
+    B, R = 2, 7
+    pr, pc = torch.zeros(B, N, N, R), torch.zeros(B, N, N, 1)
+    targets = [{"rel": torch.zeros(N, N, R)} for _ in range(B)]
+    indices = [(torch.tensor([0, 2]), torch.tensor([1, 0]))] * B
+    costs = [torch.zeros(2)] * B
+    before = ops.relation_sampler_state()
+    prev = ops.set_deterministic(False)
+    try:
+        ops.relation_losses(pr, pc, targets, indices, costs, 1.0, 80, 80)
+        with ops.deterministic():
+            ops.relation_losses(pr, pc, targets, indices, costs, 1.0, 80, 80)
+        ops.relation_losses(pr, pc, targets, indices, costs, 1.0, 80, 80)
+    finally:
+        ops.set_deterministic(prev)
+    S = "egtr_relation_loss_f32"
+    assert rec.calls == [(S, DENSE, 0, 0, 0), (S, DENSE, 0, 0, 1), (S, DENSE, 0, 0, 0)]
+    assert ops.relation_sampler_state() == before
 
 
 @pytest.mark.parametrize("neg,nm,training", [(None, None, True), (80, 80, True), (80, 80, False)])

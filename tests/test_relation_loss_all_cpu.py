@@ -4,6 +4,8 @@ composition (the last branch of ``loss_relations``: the reference's code path), 
 inputs the GPU tests use, the argument validation of the C entries, the ValueError of ``ops.relation_losses`` and
 ``DataParallelTrainer.validation_step`` / ``validation_epoch_end``."""
 import ctypes
+import os
+import re
 import types
 
 import numpy as np
@@ -118,20 +120,28 @@ def lib():
 
 
 def test_c_entries_exist_and_validate_without_a_gpu(lib):
-    """The three symbols; NULL operands, non-positive sizes and ONE NULL gradient are EGTR_E_ARG, num_rel = 65 on the packed entry is
+    """The two symbols; NULL operands, non-positive sizes, ONE NULL gradient and an unknown target format are EGTR_E_ARG under
+    every target format (0 dense, 1 words, 2 wide words), num_rel = 65 on packed words and 257 on wide words is
     EGTR_E_UNSUPPORTED -- all before any HIP call (the pointers below are host addresses no kernel ever sees)."""
     from egtr_amd import _lib
-    for n in ("egtr_relation_loss_all_f32", "egtr_relation_loss_all_bits_f32", "egtr_relation_loss_all_workspace_bytes"):
+    for n in ("egtr_relation_loss_all_f32", "egtr_relation_loss_all_workspace_bytes"):
         assert n in _lib.SIGNATURES and hasattr(lib, n)
-    assert lib.egtr_abi_version() == 6 and _lib.ABI_VERSION == 6
+    # one entry, the target form an argument: no other un-sampled name in the table or in the header
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "include", "egtr_hip.h")) as f:
+        header = f.read()
+    for names in ([n for n in _lib.SIGNATURES if n.startswith("egtr_relation_loss_all")],
+                  re.findall(r"\b(egtr_relation_loss_all\w*)\s*\(", header)):
+        assert sorted(set(names)) == ["egtr_relation_loss_all_f32", "egtr_relation_loss_all_workspace_bytes"]
+    assert lib.egtr_abi_version() == 7 and _lib.ABI_VERSION == 7
     assert lib.egtr_status_string(E_UNSUPPORTED) and lib.egtr_status_string(E_ARG) != lib.egtr_status_string(E_UNSUPPORTED)
     assert lib.egtr_relation_loss_all_workspace_bytes(4, 200) >= 4 * 200 * 200 + 4 * 200 * 8
     assert lib.egtr_relation_loss_all_workspace_bytes(0, 200) == 0 and lib.egtr_relation_loss_all_workspace_bytes(4, -1) == 0
     raw = ctypes.create_string_buffer(64 + 16)
     p = (ctypes.addressof(raw) + 15) & ~15
-    for entry in (lib.egtr_relation_loss_all_f32, lib.egtr_relation_loss_all_bits_f32):
-        def call(ptrs=(p,) * 7, sizes=(2, 7, 5), out=(p, p, p, p)):
-            return entry(None, *ptrs, *sizes, 1.0, *out)
+    entry = lib.egtr_relation_loss_all_f32
+    for fmt in (0, 1, 2):
+        def call(ptrs=(p,) * 7, sizes=(2, 7, 5), out=(p, p, p, p), fmt=fmt):
+            return entry(None, *ptrs[:3], fmt, *ptrs[3:], *sizes, 1.0, *out)
         assert call(ptrs=(None,) * 7, out=(None,) * 4) == E_ARG
         for i in range(7):                                        # each operand on its own
             assert call(ptrs=tuple(None if j == i else p for j in range(7))) == E_ARG, i
@@ -141,8 +151,11 @@ def test_c_entries_exist_and_validate_without_a_gpu(lib):
         assert call(out=(p, p, None, p)) == E_ARG
         for sizes in ((0, 7, 5), (2, 0, 5), (2, 7, 0), (-1, 7, 5)):
             assert call(sizes=sizes) == E_ARG, sizes
-    assert lib.egtr_relation_loss_all_bits_f32(None, *(p,) * 7, 1, 6, 65, 1.0, p, p, p, p) == E_UNSUPPORTED
-    assert lib.egtr_relation_loss_all_bits_f32(None, *(p,) * 7, 1, 6, 65, 1.0, p, None, None, p) == E_UNSUPPORTED
+        for bad in (-1, 3):                                       # an unknown format, every other operand valid
+            assert call(fmt=bad) == E_ARG and call(fmt=bad, out=(p, None, None, p)) == E_ARG, bad
+    for fmt, over in ((1, 65), (2, 257)):
+        assert entry(None, p, p, p, fmt, p, p, p, p, 1, 6, over, 1.0, p, p, p, p) == E_UNSUPPORTED
+        assert entry(None, p, p, p, fmt, p, p, p, p, 1, 6, over, 1.0, p, None, None, p) == E_UNSUPPORTED
 
 
 def test_relation_losses_with_exactly_one_sample_count_raises():

@@ -149,7 +149,7 @@ def test_keyed_selection_is_uniform_to_second_order(seed, ks):
 
 # ------------------------------------------------------------------------------------------------------- entries without a GPU
 E_ARG, E_UNSUPPORTED = -1, -3
-ENTRIES = ("egtr_relation_loss_policy_f32", "egtr_relation_loss_policy_bits_f32", "egtr_relation_loss_policy_wide_bits_f32")
+TARGET_FORMATS = (0, 1, 2)     # EGTR_REL_TARGET_DENSE / _WORDS / _WIDE
 
 
 def _plausible():
@@ -157,31 +157,36 @@ def _plausible():
     return raw, (ctypes.addressof(raw) + 15) & ~15
 
 
-@pytest.mark.parametrize("entry", ENTRIES)
-def test_policy_entries_reject_bad_arguments_before_any_hip_call(entry):
+@pytest.mark.parametrize("deterministic", [0, 1])
+@pytest.mark.parametrize("target_format", TARGET_FORMATS)
+def test_policy_entries_reject_bad_arguments_before_any_hip_call(target_format, deterministic):
     from egtr_amd import _lib
-    fn = getattr(_lib.lib(), entry)
+    fn = _lib.lib().egtr_relation_loss_f32
     keep, p = _plausible()
 
-    def call(ptrs=None, N=4, R=3, neg=0, nm=0, pol=(1, 2), B=1):
+    def call(ptrs=None, N=4, R=3, neg=0, nm=0, pol=(1, 2), B=1, fmt=target_format, ws=p):
         a = [p] * 8 if ptrs is None else ptrs
-        return fn(None, a[0], a[1], a[2], a[3], a[4], a[5], a[6], B, N, R, 1.0, neg, nm, a[7], p, p, p, pol[0], pol[1], 5, 0, 0)
+        return fn(None, a[0], a[1], a[2], fmt, a[3], a[4], a[5], a[6], B, N, R, 1.0, neg, nm, a[7], p, p, ws, pol[0], pol[1], 5,
+                  0, deterministic)
 
     for missing in range(8):     # pred_rel, pred_conn, target, pred_idx, tgt_idx, match_cost, out_offsets, loss_out
         assert call([None if i == missing else p for i in range(8)]) == E_ARG, missing
-    assert fn(None, p, p, p, p, p, p, p, 1, 4, 3, 1.0, 0, 0, p, p, p, None, 1, 2, 5, 0, 0) == E_ARG     # workspace
+    assert call(ws=None) == E_ARG                                                                        # workspace
     for pol in ((3, 0), (0, 3), (-1, 1), (2, 7)):
         assert call(pol=pol) == E_ARG, pol
+    for bad in (-1, 3):                                                  # an unknown target format, all else valid
+        assert call(fmt=bad) == E_ARG and call(fmt=bad, pol=(0, 0)) == E_ARG, bad
     assert call(neg=-1) == E_ARG and call(B=0) == E_ARG
     # the flat index of a random class is 32 bits; the selected count of a whole class a 32-bit int
-    limit = 65 if entry.endswith("policy_bits_f32") else (257 if "wide" in entry else None)
+    limit = {0: None, 1: 65, 2: 257}[target_format]
     if limit is not None:
-        assert call(R=limit) == E_UNSUPPORTED
+        assert call(R=limit) == E_UNSUPPORTED and call(R=limit, pol=(0, 0)) == E_UNSUPPORTED
         assert call(R=limit, pol=(0, 5)) == E_ARG           # the policy check comes first
-    else:
+    if target_format != 1:                                   # (256 predicates: not in one word)
         assert call(N=4096, R=256, pol=(1, 0)) == E_UNSUPPORTED      # N N R = 2^32 with a random class
         assert call(N=4096, R=256, pol=(0, 2)) == E_UNSUPPORTED      # ... and >= 2^31 with a whole one
-        assert call(N=4096, R=1024) == E_UNSUPPORTED                  # the siblings' limit N R < 2^22
+    if target_format == 0:
+        assert call(N=4096, R=1024) == E_UNSUPPORTED                  # the limit N R < 2^22
     del keep
 
 

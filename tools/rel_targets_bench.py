@@ -1,16 +1,19 @@
 """Relation targets, dense against bit-packed, on one GPU.  Prints one JSON line.
 
 At N = 200, R = 50, B = 4 with 20 triplets per image (the training shape of bench.py), in one process:
-  dense_us / packed_us   stream time of one call of egtr_relation_loss_f32 / egtr_relation_loss_bits_f32 on the same
-                         logits, matcher outputs and targets: device events around --iters back-to-back calls, warm,
-                         the two entries in alternating blocks, median over --blocks blocks (and every block's figure)
-  parent_dense_us        the same for egtr_relation_loss_f32 of ANOTHER build of the library (--parent-lib: the parent
-                         commit's, built apart), in the same alternation: the yardstick of "nothing got slower"
+  dense_us / packed_us   stream time of one call of egtr_relation_loss_f32 with target format 0 (dense) / 1 (packed words) on
+                         the same logits, matcher outputs and targets: device events around --iters back-to-back calls, warm,
+                         the two forms in alternating blocks, median over --blocks blocks (and every block's figure)
+  parent_dense_us        the same for egtr_relation_loss_f32 of ANOTHER build of the library (--parent-lib: an ABI-6 build,
+                         where the dense form was an entry of its own), in the same alternation: the yardstick of "nothing
+                         got slower"
+  launch_host_us         host time of one ``ops.relation_loss_launch`` call (allocations, argument marshalling and the
+                         entry's launches, not waited for), median and range over --blocks x --iters calls
   pack_us                one egtr_pack_relations_u64 call (memset + launch) on triplets already on the device
   h2d_*_us               the host -> device copy of the batch's triplets + offsets (one buffer) against the copy of four
                          dense [N, N, R] fp32 targets, from pinned and from pageable memory: host clock around copies that
                          end in a synchronise, median of --blocks
-  results_identical      loss_out, grad_rel and grad_conn of the two entries compared bit for bit on these inputs
+  results_identical      loss_out, grad_rel and grad_conn of the two forms compared bit for bit on these inputs
 
     python tools/rel_targets_bench.py [--iters 50] [--blocks 7] [--parent-lib PATH] [--out profiles/rel_targets_bench.json]"""
 import argparse
@@ -99,20 +102,27 @@ def main():
     grad_rel, grad_conn = torch.empty_like(pred_rel), torch.empty_like(pred_conn)
     ws = torch.empty(int(h.egtr_relation_loss_workspace_bytes(B, N)), dtype=torch.uint8, device=dev)
 
-    def entry(fn, target):
+    def entry(fn, target, *form):
+        """``form``: what this build's entry takes between the target and the matcher's outputs (the target format) and
+        after the workspace (both policies `largest`, seed, stream, arrival-order ties); nothing for the ABI-6 prototype"""
+        head, tail = form[:1], form[1:]
+
         def call():
-            st = fn(_lib._stream(), pred_rel.data_ptr(), pred_conn.data_ptr(), target.data_ptr(), pi.data_ptr(),
+            st = fn(_lib._stream(), pred_rel.data_ptr(), pred_conn.data_ptr(), target.data_ptr(), *head, pi.data_ptr(),
                     ti.data_ptr(), mc.data_ptr(), off.data_ptr(), B, N, R, nm, SAMPLE, SAMPLE, loss.data_ptr(),
-                    grad_rel.data_ptr(), grad_conn.data_ptr(), ws.data_ptr())
+                    grad_rel.data_ptr(), grad_conn.data_ptr(), ws.data_ptr(), *tail)
             if st != 0:
                 raise RuntimeError(f"status {st}")
         return call
 
-    runs = {"dense_us": entry(h.egtr_relation_loss_f32, ptrs), "packed_us": entry(h.egtr_relation_loss_bits_f32, bits)}
-    if args.parent_lib:
+    runs = {"dense_us": entry(h.egtr_relation_loss_f32, ptrs, 0, 0, 0, 0, 0, 0),
+            "packed_us": entry(h.egtr_relation_loss_f32, bits, 1, 0, 0, 0, 0, 0)}
+    if args.parent_lib:   # the parent is by definition the OLD interface: its prototype is written out, not borrowed
         parent = ctypes.CDLL(args.parent_lib)
-        parent.egtr_relation_loss_f32.argtypes = _lib.SIGNATURES["egtr_relation_loss_f32"]
-        parent.egtr_relation_loss_f32.restype = ctypes.c_int
+        vp, ci = ctypes.c_void_p, ctypes.c_int
+        parent.egtr_relation_loss_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ctypes.c_float, ci, ci, vp, vp,
+                                                  vp, vp]
+        parent.egtr_relation_loss_f32.restype = ci
         runs["parent_dense_us"] = entry(parent.egtr_relation_loss_f32, ptrs)
 
     d = ops.relation_loss_launch(pred_rel, pred_conn, ptrs, False, pi, ti, mc, off, nm, SAMPLE, SAMPLE)
@@ -137,6 +147,16 @@ def main():
     for k, v in blocks.items():
         res[k] = round(statistics.median(v), 2)
         res[k + "_blocks"] = [round(x, 2) for x in v]
+
+    # host time of the binding: the clock around one call that is not waited for, the queue empty before it
+    def launch_host_us():
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        ops.relation_loss_launch(pred_rel, pred_conn, ptrs, False, pi, ti, mc, off, nm, SAMPLE, SAMPLE)
+        return (time.perf_counter() - t0) * 1e6
+    host = sorted(launch_host_us() for _ in range(args.blocks * args.iters))
+    res["launch_host_us"] = round(statistics.median(host), 2)
+    res["launch_host_us_range"] = [round(host[0], 2), round(host[-1], 2)]
 
     # host -> device copies: triplets + offsets in one buffer against four dense targets
     n_trip = 2 * ((B + 4) // 4) + 3 * B * K_PER_IMAGE

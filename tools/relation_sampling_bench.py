@@ -3,8 +3,8 @@
 the main output set and five auxiliary ones -- forward and backward, B = 4, N = 200, R = 50, about 20 objects and 25 relations
 per image, ``rel_triplets`` targets.
 
-For each configuration the policy kernels (egtr_relation_loss_policy_*) against the route the criterion took for the SAME
-configuration before they existed:
+For each configuration the policy kernels (egtr_relation_loss_f32 with a policy other than `largest`) against the route the
+criterion took for the SAME configuration before they existed:
 
   random / random, 80 / 80   device sampler           vs  the reference's composition (nonzero() lists + random.sample)
   largest / None (whole)     policy kernels           vs  _loss_relations_device (masked topk, one host wait)

@@ -1,7 +1,7 @@
 """The relation losses of a validation batch, kernel route against the tensor composition, on one GPU.
 
 In evaluation mode the criterion's relation loss is un-sampled: BCE over all N N R elements.  ``ops.RELATION_LOSS_ALL`` selects
-between one HIP pipeline per output set (egtr_relation_loss_all_bits_f32, value-only under no_grad) and the per-image tensor
+between one HIP pipeline per output set (egtr_relation_loss_all_f32 on packed words, value-only under no_grad) and the per-image tensor
 composition of the reference (dense target, permuting gathers, ``torch.nonzero``).  Two legs in ONE process, alternating, at
 B = 4, N = 200, R = 50, six output sets, ``rel_triplets`` targets (the words are packed once per call, as the criterion's forward
 does):
